@@ -2,7 +2,11 @@
 """bench.py -- k-NN mapping throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--targets M --refs N --dims D --neighbors K]
-                    [--metric euclidean|cosine|canberra]
+                    [--metric euclidean|cosine|canberra] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps and K timed steps, and prints one JSON line whose `ms_per_step` is the time of
+one timed step.  --dump-outputs DIR writes the k-NN lists of the last timed step (see dump_outputs).  Everything else
+the benchmark measures or checks runs with --full only (listed below).
 
 A step = one full k-NN build of the workload: pack the (sharded) references, fused distance + top-k filter on the
 matrix pipe, float64 refine + certification, and for N>1 the RCCL exchange + merge (nabo_sharded_query).  Inputs
@@ -18,16 +22,19 @@ N>1 runs however the file is launched:
   * plain `python bench.py --gpus N` (no launcher environment) drives the N devices from THIS process: one communicator
     per GPU (nabo_comm_create_all = ncclCommInitAll) and one host thread per rank (nabo_amd.ShardedGroup).  Fewer than
     N visible GPUs is an error (exit code 2), never a silent one-GPU run.
-The N>1 headline is the layout BASELINE configs[3] names -- references sharded N ways, one piece per rank; the
-2 x N/2 layout (two reference pieces x N/2 target slices; N >= 4) and pure target slicing (every
-rank holds all the references and answers its own m/N rows: no exchange) are measured in the same invocation as the
-`alt_layout` / `alt_layout_target_slices` blocks and must give the same bits.  (NABO_BENCH_LOOPBACK=N rehearses all of
-it with N shard-ranks on ONE GPU through the loopback transport.)
+The N>1 headline is the layout BASELINE configs[3] names -- references sharded N ways, one piece per rank; with --full
+the 2 x N/2 layout (two reference pieces x N/2 target slices; N >= 4) and pure target slicing
+(every rank holds all the references and answers its own m/N rows: no exchange) are measured in the same invocation as
+the `alt_layout` / `alt_layout_target_slices` blocks and must give the same bits.  (NABO_BENCH_LOOPBACK=N rehearses all
+of it with N shard-ranks on ONE GPU through the loopback transport.)
 
-The default N=1 line also carries (outside the timed region): `canberra` -- the reference's default target<->reference
-metric (nabo/_mapping.py:122-124) on the same 1M x 1M workload, checked against the oracle on sampled rows;
-`alt`, `alt_f16x3` -- the fp32-MFMA filter / the f16x3 split as the first pass on the same step (same bits required); `cpu_baseline` -- the oracle on this
-box's host cores (OpenMP and single thread) and the reference-style end-to-end run of BASELINE configs[0].
+With --full the line also carries (outside the timed region): `sampled_rows_equal_oracle` -- the result checked for
+valid, sorted rows and against the oracle on sampled rows (null without --full); and at N=1 `canberra` -- the
+reference's default target<->reference metric (nabo/_mapping.py:122-124) on the same 1M x 1M workload, checked against
+the oracle on sampled rows; `alt`, `alt_f16x3` -- the fp32-MFMA filter / the f16x3 split as the first pass on the same
+step (same bits required); `config4_one_gpu` -- BASELINE configs[4] on this one GPU; `cpu_baseline` -- the oracle on
+the host's cores (OpenMP and single thread) and the reference-style end-to-end run of BASELINE configs[0].
+--no-extras / --no-cpu-baseline leave parts of that out again.
 """
 import argparse
 import json
@@ -127,6 +134,22 @@ def pmc_record(kind, workload, digest):
         return dict(rec, measured_in_this_run=False)
     return {"stale": True, "source": rec.get("source"), "src_digest_of_record": rec.get("src_digest"),
             "measured_in_this_run": False}
+
+
+DUMP_BYTES = 64 * 10**6        # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, gi, gd):
+    """--dump-outputs: what a caller of the step receives -- the k-NN indices and distances (m x k) -- as float64
+    indices.npy / distances.npy (indices < 2^53, so exact), with rows.npy naming the target rows they hold.  All rows
+    when they fit in DUMP_BYTES, else a fixed seeded sample of rows in ascending order (the same rows every run)."""
+    m, k = gi.shape
+    per_row = 8 * (2 * k + 1)
+    fit = (DUMP_BYTES - 4096) // per_row               # (4096: the three .npy headers)
+    rows = np.arange(m) if m <= fit else np.sort(np.random.default_rng(15).choice(m, fit, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("rows", rows), ("indices", gi[rows]), ("distances", gd[rows])):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 class Layout:
@@ -260,9 +283,16 @@ def main():
     ap.add_argument("--metric", choices=["euclidean", "cosine", "canberra"], default="euclidean",
                     help="cosine is an extension (BASELINE configs[4]); canberra is the reference's target<->reference "
                          "metric; the headline workload is euclidean")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the canberra / alt / alt_layout / C1 blocks (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the oracle check, the other filters / layouts / metric, BASELINE configs[4] and the CPU "
+                         "baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the k-NN lists of the last timed step to DIR as float64 .npy files")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the canberra / alt / alt_layout / C1 blocks")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     # ---- how was this file launched?  (decided BEFORE anything touches a GPU) --------------------------------------
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -318,18 +348,23 @@ def main():
             "candidates": int(lay.xstats[-1][0]["candidates"]) if lay.xstats else None,
             "second_round_rows": int(max(x[0]["uncertified"] for x in lay.xstats)) if lay.xstats else None}
 
-    # self-check outside the timed region: valid, sorted rows; a row sample against the oracle
+    # outside the timed region: the last step's result, when something below needs it
+    check = os.environ.get("NABO_BENCH_CHECK") == "1" and kind != "single"
     gi = gd = None
-    sampled = None
-    if not ablate:
+    if a.dump_outputs or (not ablate and (a.full or check)):
         gi, gd = lay.result()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, gi, gd)
+    # self-check (--full): valid, sorted rows; a row sample against the oracle
+    sampled = None
+    if a.full and not ablate:
         assert gi.min() >= 0 and gi.max() < n and (np.diff(gd[:: max(1, m // 4096)], axis=1) >= 0).all()
         if rank == 0:
             import oracle
             rows = np.random.default_rng(12).choice(m, min(32, m), replace=False)
             oi, od = oracle.knn(X[rows], Yfull, k, metric_id, 0.25, nthreads=max(1, min(os.cpu_count() or 1, 16)))
             sampled = bool(np.array_equal(gi[rows], oi) and np.array_equal(gd[rows], od))
-    if os.environ.get("NABO_BENCH_CHECK") == "1" and kind != "single":
+    if check:
         # rehearsal check: the sharded result must equal one unsharded index on the same data
         ref_ix = nabo_amd.KnnIndex(n, d, metric=metric_id, dist_factor=0.25, device=dev).set_ref(Yfull)
         ri, rd = ref_ix.query(X, k)
@@ -340,7 +375,7 @@ def main():
 
     # the other layout of the same ranks, same invocation, same bits required (every rank takes part)
     alt_layout = None
-    want_alt = (ranks >= 2 and R == ranks and a.metric != "canberra" and not a.no_extras and not ablate
+    want_alt = (a.full and ranks >= 2 and R == ranks and a.metric != "canberra" and not a.no_extras and not ablate
                 and not os.environ.get("NABO_REF_SHARDS"))
     alt_slices = None
     if want_alt:
@@ -432,7 +467,7 @@ def main():
             line["alt_layout"] = alt_layout
         if alt_slices is not None:
             line["alt_layout_target_slices"] = alt_slices
-        extras = kind == "single" and not a.no_extras and not ablate
+        extras = a.full and kind == "single" and not a.no_extras and not ablate
         if extras and a.metric == "euclidean" and not os.environ.get("NABO_L2_MODE"):
             line["alt"] = alt_block(nabo_amd, _knn, "f32" if "f16" in kern else "f16x3", dev, n, m, d, k, lay.dY, lay.dXb, gi, gd, lay.sync)
             if "one-product" in kern:           # ... and the f16x3 split as the first pass (round 2's default)
@@ -441,7 +476,7 @@ def main():
             line["canberra"] = canberra_block(nabo_amd, _knn, _lib, dev, n, m, d, k, lay.dY, lay.dXb, X, Yfull, lay.sync)
         if extras and a.metric == "euclidean" and (m, n) == (1000000, 1000000) and os.environ.get("NABO_BENCH_CONFIG4", "1") != "0":
             line["config4_one_gpu"] = config4_block()
-        if not a.no_cpu_baseline and kind == "single":
+        if a.full and not a.no_cpu_baseline and kind == "single":
             line["cpu_baseline"] = cpu_baseline(d, k, metric_id)
             if extras:
                 line["cpu_baseline"]["c1_end_to_end"] = c1_end_to_end(gpu=True)

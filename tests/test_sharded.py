@@ -369,7 +369,7 @@ def test_bench_sharded_code_path_with_loopback_ranks():
     shard-ranks on ONE GPU; the result is compared with an unsharded index inside bench.py (NABO_BENCH_CHECK)."""
     env = dict(os.environ, NABO_BENCH_LOOPBACK="4", NABO_BENCH_CHECK="1")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "1", "--warmup", "1", "--targets", "20001",
-           "--refs", "50000", "--no-cpu-baseline", "--no-extras"]
+           "--refs", "50000", "--full", "--no-cpu-baseline", "--no-extras"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stdout[-3000:]
     assert "sharded == unsharded: True" in r.stdout and '"candidates_per_shard"' in r.stdout, r.stdout[-3000:]
@@ -396,7 +396,7 @@ def test_bench_prints_the_baseline_layout_as_headline_and_the_2d_layout_beside_i
     import json
     env = dict(os.environ, NABO_BENCH_LOOPBACK="8", NABO_BENCH_CHECK="1")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "1", "--warmup", "1", "--targets", "30001",
-           "--refs", "60000", "--no-cpu-baseline"]
+           "--refs", "60000", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stdout[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -419,7 +419,7 @@ def test_bench_plain_launch_drives_its_ranks_from_one_process():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "NABO_BENCH_LOOPBACK")}
     env.update(NABO_BENCH_FORCE_THREADS="1", NABO_BENCH_CHECK="1")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--targets", "20001",
-           "--refs", "50000", "--no-cpu-baseline", "--no-extras"]
+           "--refs", "50000", "--full", "--no-cpu-baseline", "--no-extras"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stdout[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -435,7 +435,7 @@ def test_bench_under_the_launcher_creates_its_communicator_without_torch():
     env = dict(os.environ, NABO_BENCH_FORCE_COMM="1", NABO_BENCH_CHECK="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-           "--targets", "20001", "--refs", "50000", "--no-cpu-baseline", "--no-extras"]
+           "--targets", "20001", "--refs", "50000", "--full", "--no-cpu-baseline", "--no-extras"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stdout[-3000:]
     assert "sharded == unsharded: True" in r.stdout and '"sharded"' in r.stdout, r.stdout[-3000:]

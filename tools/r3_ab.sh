@@ -4,7 +4,7 @@
 set -e
 TAG=$1; shift
 O=$PWD/gpurun_out/$TAG; mkdir -p $O
-B="--no-extras --no-cpu-baseline"
+B="--full --no-extras --no-cpu-baseline"
 for v in "$@"; do
   if [ "$v" = product ]; then unset NABO_KNN_SO; else export NABO_KNN_SO=$PWD/tools/ab/$v.so; fi
   python bench.py $B --steps 5 --warmup 2 > $O/bench_$v.json 2> $O/bench_$v.err || echo "bench $v FAILED"

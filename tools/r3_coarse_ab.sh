@@ -5,7 +5,7 @@
 #   e.g.  bash tools/r3_coarse_ab.sh ab exp exp:NABO_DEBUG_ABLATE=1 exp:NABO_L2C_GEO=a exp:NABO_COARSE_KERNEL_Q=1 exp:NABO_L2_MODE=f16x3
 TAG=$1; shift
 O=$PWD/gpurun_out/$TAG; mkdir -p $O
-B="--no-extras --no-cpu-baseline --steps 3 --warmup 1"
+B="--full --no-extras --no-cpu-baseline --steps 3 --warmup 1"
 for spec in "$@"; do
   v=${spec%%:*}; envs=""; [ "$spec" != "$v" ] && envs=$(echo "${spec#*:}" | tr ',' ' ')
   so=""; [ "$v" != product ] && so="NABO_KNN_SO=$PWD/tools/ab/$v.so"

@@ -3,7 +3,7 @@
 set -e
 TAG=${1:-r3d}
 O=$PWD/gpurun_out/$TAG; mkdir -p $O
-B="--no-extras --no-cpu-baseline"
+B="--full --no-extras --no-cpu-baseline"
 for ord in 1 0; do
   export NABO_L2Q_ORDER=$ord
   python bench.py $B --steps 5 --warmup 2 > $O/bench_order$ord.json 2> $O/bench_order$ord.err || echo "bench order=$ord FAILED"

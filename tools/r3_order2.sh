@@ -2,7 +2,7 @@
 set -e
 TAG=${1:-r3e}
 O=$PWD/gpurun_out/$TAG; mkdir -p $O
-B="--no-extras --no-cpu-baseline"
+B="--full --no-extras --no-cpu-baseline"
 run() {   # label, env...
   local label=$1; shift
   env "$@" python bench.py $B --steps 5 --warmup 2 > $O/bench_$label.json 2> $O/bench_$label.err || echo "bench $label FAILED"

@@ -1,7 +1,7 @@
 set -e
 TAG=${1:-r3f}
 O=$PWD/gpurun_out/$TAG; mkdir -p $O
-B="--no-extras --no-cpu-baseline"
+B="--full --no-extras --no-cpu-baseline"
 for f in 0 1 2 3 7 0; do
   NABO_L2Q_ORDER=$f python bench.py $B --steps 4 --warmup 2 2> $O/err_$f.txt | python -c "
 import sys,json

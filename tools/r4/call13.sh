@@ -8,8 +8,8 @@ for shape in "100000 100000" "30000 30000" "49152 100000" "150000 100000" "20000
 done
 for so in tools/ab/base.so ""; do
   tag=$( [ -z "$so" ] && echo product || basename $so .so )
-  NABO_KNN_SO=$so timeout -k 10 200 python bench.py --steps 6 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_1M_$tag.json 2> $O/bench_1M_$tag.err
-  NABO_KNN_SO=$so timeout -k 10 200 python bench.py --targets 100000 --refs 100000 --steps 10 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_100k_$tag.json 2>> $O/bench_1M_$tag.err
+  NABO_KNN_SO=$so timeout -k 10 200 python bench.py --full --steps 6 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_1M_$tag.json 2> $O/bench_1M_$tag.err
+  NABO_KNN_SO=$so timeout -k 10 200 python bench.py --full --targets 100000 --refs 100000 --steps 10 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_100k_$tag.json 2>> $O/bench_1M_$tag.err
   python - <<PY
 import json
 for f in ("bench_1M","bench_100k"):

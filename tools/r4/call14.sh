@@ -5,7 +5,7 @@ for shape in "100000 100000" "76000 50000" "120000 1000000" "110000 30000" "6000
   timeout -k 10 300 python tools/sweep_plan.py $shape 50 15 default one_round=0 > $O/sweep_$(echo $shape | tr ' ' 'x').txt 2>&1
   echo "== $shape"; cut -c1-250 $O/sweep_$(echo $shape | tr ' ' 'x').txt
 done
-timeout -k 10 200 python bench.py --targets 100000 --refs 100000 --steps 10 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_100k.json 2> $O/bench.err
+timeout -k 10 200 python bench.py --full --targets 100000 --refs 100000 --steps 10 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_100k.json 2> $O/bench.err
 python - <<PY
 import json
 d=json.loads(open("$O/bench_100k.json").read().strip().splitlines()[-1]); print("bench_100k ms/step %.2f kernel %.2f"%(d["ms_per_step"], d["roofline"]["kernel_ms"]), d["phases_ms"], d["sampled_rows_equal_oracle"])

@@ -5,9 +5,9 @@ NABO_KNN_SO=$so timeout -k 10 300 python -m pytest tests -m gpu -x -q -k "one_pr
 done
 for so in "" tools/ab/load1.so tools/ab/load2.so ""; do
   tag=$( [ -z "$so" ] && echo product || basename $so .so )
-  NABO_KNN_SO=$so timeout -k 10 200 python bench.py --steps 8 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_1M_$tag.json 2> $O/bench_$tag.err
-  NABO_KNN_SO=$so timeout -k 10 200 python bench.py --metric cosine --dims 100 --neighbors 50 --steps 2 --warmup 1 --no-extras --no-cpu-baseline > $O/bench_cosine_$tag.json 2>> $O/bench_$tag.err
-  NABO_KNN_SO=$so timeout -k 10 200 python bench.py --targets 100000 --refs 100000 --steps 10 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_100k_$tag.json 2>> $O/bench_$tag.err
+  NABO_KNN_SO=$so timeout -k 10 200 python bench.py --full --steps 8 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_1M_$tag.json 2> $O/bench_$tag.err
+  NABO_KNN_SO=$so timeout -k 10 200 python bench.py --full --metric cosine --dims 100 --neighbors 50 --steps 2 --warmup 1 --no-extras --no-cpu-baseline > $O/bench_cosine_$tag.json 2>> $O/bench_$tag.err
+  NABO_KNN_SO=$so timeout -k 10 200 python bench.py --full --targets 100000 --refs 100000 --steps 10 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_100k_$tag.json 2>> $O/bench_$tag.err
   python - <<PY
 import json
 for f in ("bench_1M","bench_cosine","bench_100k"):

@@ -2,12 +2,12 @@
 # of the product build), geometry B as two 4-wave workgroups per CU, the pipelined row reads of the Canberra counting pass.
 O=$PWD/gpurun_out/${TAG:-r4c4}; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc=$? $(tail -1 $O/pytest.log)"
-timeout -k 10 200 python bench.py --steps 8 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_1M.json 2> $O/bench.err; echo "bench rc=$?"
-timeout -k 10 200 python bench.py --targets 100000 --refs 100000 --steps 10 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_100k.json 2>> $O/bench.err
-timeout -k 10 200 python bench.py --metric cosine --dims 100 --neighbors 50 --steps 2 --warmup 1 --no-extras --no-cpu-baseline > $O/bench_cosine.json 2>> $O/bench.err
+timeout -k 10 200 python bench.py --full --steps 8 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_1M.json 2> $O/bench.err; echo "bench rc=$?"
+timeout -k 10 200 python bench.py --full --targets 100000 --refs 100000 --steps 10 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_100k.json 2>> $O/bench.err
+timeout -k 10 200 python bench.py --full --metric cosine --dims 100 --neighbors 50 --steps 2 --warmup 1 --no-extras --no-cpu-baseline > $O/bench_cosine.json 2>> $O/bench.err
 timeout -k 10 200 python tools/bench_shard.py 8 2>> $O/bench.err | tail -1 > $O/shard_share.txt
 timeout -k 10 300 python tools/bench_canberra.py 1000000 1000000 50 15 > $O/canberra_1M.json 2>> $O/bench.err
-NABO_BENCH_LOOPBACK=8 NABO_BENCH_CHECK=1 timeout -k 10 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_loopback8.json 2> $O/bench_loopback8.err; echo "loopback rc=$?"
+NABO_BENCH_LOOPBACK=8 NABO_BENCH_CHECK=1 timeout -k 10 300 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_loopback8.json 2> $O/bench_loopback8.err; echo "loopback rc=$?"
 python - <<'PY'
 import json,glob,os
 O=os.environ.get("TAG","r4c4")

@@ -5,7 +5,7 @@ timeout -k 10 600 python -m pytest tests -m gpu -x -q -k "canberra or Canberra" 
 NABO_KNN_SO=tools/ab/cbb_m0per.so timeout -k 10 600 python -m pytest tests -m gpu -x -q -k "canberra or Canberra" > $O/pytest_canberra_m0per.log 2>&1; echo "pytest m0per rc=$? $(tail -1 $O/pytest_canberra_m0per.log)"
 for so in tools/ab/cbb_base.so "" tools/ab/cbb_m0per.so tools/ab/cbb_dmaw8.so tools/ab/cbb_base.so ""; do
   tag=$( [ -z "$so" ] && echo product || basename $so .so )
-  NABO_KNN_SO=$so timeout -k 10 200 python bench.py --metric canberra --steps 2 --warmup 1 --no-extras --no-cpu-baseline > $O/canberra_$tag.json 2> $O/canberra_$tag.err
+  NABO_KNN_SO=$so timeout -k 10 200 python bench.py --full --metric canberra --steps 2 --warmup 1 --no-extras --no-cpu-baseline > $O/canberra_$tag.json 2> $O/canberra_$tag.err
   python -c "
 import json; d=json.loads(open('$O/canberra_$tag.json').read().strip().splitlines()[-1]); print('$tag', round(d['ms_per_step'],1), round(d['roofline']['kernel_ms'],1), d['sampled_rows_equal_oracle'])"
 done
