@@ -95,7 +95,9 @@ int nabo_index_destroy(nabo_index *ix);
  * (tournament seeds, percent of the planned length; 0 = off), "merge_lists" (several lists per row are merged by their
  * filter keys before the float64 step), "one_round" (fewer column-workgroups than slots: splits chosen to fill one round of
  * workgroups), "pieces" (experiments builds: the same query cut into equal chunks of the (column, tile) space; a no-op otherwise), "l2c_geo" (0 = A, 1 = B,
- * 2 = C), "l2_r1", "split_refs_max", "cosine_centre" (takes effect at the next set_ref).  Unknown names: NABO_E_INVALID.
+ * 2 = C), "l2_r1", "split_refs_max", "cosine_centre" (takes effect at the next set_ref), "coarse_kernel_q" (the one-product
+ * operands through the l2q kernel instead of l2c), "order_flags" (experiments builds: locality-ordered streaming; refused
+ * with NABO_E_UNSUPPORTED otherwise).  Unknown names: NABO_E_INVALID.
  * The library reads TWO environment variables, once, in nabo_index_create: NABO_L2_MODE = f32 | f16x3 (which Euclidean /
  * cosine filter runs first; default: the one-product pass) and NABO_CANBERRA_MODE = exact | swar | bits; the sharded
  * transport reads NABO_COMM_TIMEOUT_S and NABO_RCCL_LIB. */
