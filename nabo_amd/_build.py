@@ -12,24 +12,19 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libnabo_knn.so")
 SOURCES = ["api.hip", "pack.hip", "l2_topk.hip", "l2q_topk.hip", "l2c_topk.hip", "refine.hip", "canberra.hip", "canberra_f32.hip", "canberra_bits.hip", "score_null.hip", "csr_build.hip", "sharded.hip", "multi.hip", "host_graph.hip"]
-# kernels of the experiments build only (-DNABO_EXPERIMENTS, tools/ab: measured slower than the product's and kept for A/B runs):
-# the f16x3 split on the 32x32x16 MFMA shape per wave / with LDS-shared tiles, locality-ordered streaming
-EXPERIMENT_SOURCES = ["l2h_topk.hip", "l2s_topk.hip", "order.hip"]
 # per-file extra flags: -fno-honor-nans for the fp32 score kernel (scores are finite or +inf by construction; without it
 # every fminf tree starts with two v_max canonicalisations, and on gfx950 the fp32 MFMA cannot overlap vector-ALU work);
-# (NOT for l2h_topk.hip: its masked / padding cells carry an inf - inf = NaN low part, and the filter relies on NaN
-# comparing false -- with the flag 4 of 1000 rows lose their certificate);
 # canberra_f32.hip with LLVM's iterative-ilp scheduler: the counting loop is four independent packed-f16 chains per
 # dimension pair, and the default scheduler leaves 156 hazard s_nop in it (none with this one): kernel 45.4 -> 40.8 ms at
 # 100k x 100k, 3.79 -> 3.43 s at 1M x 1M;
 # the same scheduler for l2_topk.hip (hit path and filter are plain vector code around the fenced MFMA chains): 1M x 1M
-# kernel 755 -> 735 ms; no effect on l2h_topk.hip (372 ms either way);
+# kernel 755 -> 735 ms;
 # keep MFMA accumulators in arch VGPRs so the C-in (||y||^2 block) needs no
 # v_accvgpr_write and the filter reads the scores without v_accvgpr_read (see l2_topk.hip)
-FILE_FLAGS = {"l2_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"], "l2h_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "l2q_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+FILE_FLAGS = {"l2_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"], "l2q_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
               # l2c_topk.hip: its scores are finite or +inf by construction (pack_ctiles_kernel<.,.,1>), so the filter's minimum tree
               # needs no NaN canonicalisation (two v_max per row-block otherwise)
-              "l2c_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"], "l2s_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+              "l2c_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
               "canberra_f32.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]}
 HEADERS = [os.path.join(CSRC, "knn_common.h"), os.path.join(CSRC, "topk_lists.h"), os.path.join(HERE, "..", "include", "nabo_knn.h")]
 ARCH = "gfx950"
@@ -83,7 +78,7 @@ def build(force=False, verbose=False, extra=None, out=None):
 def _build(force, verbose, extra, objdir):
     os.makedirs(objdir, exist_ok=True)
     jobs, objs = [], []
-    for s in SOURCES + (EXPERIMENT_SOURCES if "-DNABO_EXPERIMENTS" in extra else []):
+    for s in SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(objdir, s.replace(".hip", ".o"))
         objs.append(obj)

@@ -34,7 +34,6 @@ hipError_t pack_cquery_launch(const double *X, int64_t m, int g, const double *c
                               int64_t ntiles_total, unsigned char *out, double *xnorm, bool layout16, hipStream_t st,
                               const uint32_t *perm = nullptr, int nseg = 3);
 int l2q_pick_kc(int g);
-int l2q_pick_kc1(int g);
 // the one-product first pass (l2c_topk.hip; operands packed with layout16, nseg = 1)
 hipError_t l2c_topk_launch(int kc, int geo, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
                            int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
@@ -54,25 +53,6 @@ void l2c_topk_geometry(int kc, int lkeep_want, int pin, int *rows_per_wg, int *w
 hipError_t l2q_topk_launch(int kc, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
                            int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
                            int64_t pad_tile, hipStream_t st, const int32_t *wave_start = nullptr);
-#ifdef NABO_EXPERIMENTS
-// kernels of the experiments build only (tools/ab; measured slower than the product's, kept for A/B runs -- DESIGN.md 4.1b-d):
-// the f16x3 split on v_mfma_f32_32x32x16_f16 (l2h_topk.hip), the same with reference tiles shared through an LDS ring
-// (l2s_topk.hip), locality order of the streamed cells (order.hip)
-hipError_t l2h_topk_launch(int kc, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
-                           int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
-                           int64_t pad_tile, hipStream_t st);
-void l2h_topk_geometry(int kc, int *rows_per_wg, int *wg_per_cu, int *lkeep_max);
-int loc_key_bits(int g);
-hipError_t loc_sort_temp_bytes(int64_t n, int nb, size_t *bytes);
-hipError_t loc_order_launch(const double *V, int64_t n, int g, const double *centre, uint32_t *keys_a, uint32_t *pos_a,
-                            uint32_t *keys_sorted, uint32_t *perm, void *temp, size_t temp_bytes, hipStream_t st);
-hipError_t wave_start_launch(const uint32_t *tkeys, int64_t m, int rows_per_wave, const uint32_t *rkeys, int64_t n,
-                             int64_t n_waves, int32_t *start, hipStream_t st);
-hipError_t l2s_topk_launch(int kc, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S, int gx,
-                           int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau, hipStream_t st);
-void l2s_topk_geometry(int kc, int *rows_per_wg, int *wg_per_cu, int *lkeep_max);
-int l2s_pick_kc(int g);
-#endif
 void l2q_topk_geometry(int kc, int *rows_per_wg, int *wg_per_cu, int *lkeep_max);
 hipError_t pairwise_launch(const double *X, int64_t m, const double *Y, int64_t n, int g, int metric, double f,
                            double *D, hipStream_t st);
@@ -227,7 +207,7 @@ int pick_ksteps(int g)
 // Tuning options of an index (nabo_index_set_option; the defaults are the product's behaviour).  EVERY setting returns the
 // same bits -- an option chooses how a launch is cut or which filter pass answers a row, never what the answer is.  The
 // library reads two environment variables, once, in nabo_index_create: NABO_L2_MODE and NABO_CANBERRA_MODE (which first
-// filter); -DNABO_EXPERIMENTS builds (tools/ab) also take every option below as NABO_OPT_<NAME>.
+// filter); experiments builds (tools/ab) also take every option below as NABO_OPT_<NAME> (options_from_env).
 struct Options {
     int splits = 0;            // reference splits of a filter launch (0: the cost model decides)
     int tail_split = 1;        // the last, partially filled round of workgroups gets its own split count
@@ -239,15 +219,15 @@ struct Options {
     int wide_retry = 1;        //   rows the 32-entry lists fail get 64-entry lists before the exact kernels
     int refine_overlap = 1;    // the refine of the main launch's rows runs beside the filter's tail launch
     int prepass = 100;         // tournament seeds: percent of the planned length (0: lists start from +inf)
-    int pieces = 0;            // (-DNABO_EXPERIMENTS builds) fewer column-workgroups than slots: the launch cut into equal pieces of (column, tile) space -- measured slower than uniform splits; a no-op in the product build
+    int pieces = 0;            // accepted, no effect (the launch cut into pieces lost to uniform splits and was removed)
     int merge_lists = 1;       // several lists per row are merged by their filter keys before the float64 re-evaluation
     int one_round = 1;         // fewer column-workgroups than slots: splits (+ a tail launch) chosen to fill ONE round of workgroups
     int l2c_geo = -1;          // pin the one-product kernel's geometry: 0 = A, 1 = B, 2 = C (-1: by list length)
     int l2_r1 = -1;            // fp32 filter: one row-block per wave (-1 auto, 0 never, 1 always)
     int split_refs_max = 0;    // lower the 2^25-references-per-split bound (tests see the rule at ordinary sizes)
     int cosine_centre = 1;     // cosine: centre the unit rows before packing (takes effect at the next set_ref)
-    int coarse_kernel_q = 0;   // experiments: the one-product operands through the l2q kernel
-    int order_flags = 0;       // experiments: locality-ordered streaming (order.hip)
+    int coarse_kernel_q = 0;   // the one-product operands through the l2q kernel instead of l2c
+    int order_flags = 0;       // refused by nabo_index_set_option (locality-ordered streaming was removed)
 };
 
 struct OptionName { const char *name; int Options::*field; };
@@ -284,6 +264,8 @@ void options_from_env(Options &o)
 }
 #endif
 
+constexpr int RERUN_WIDE = 2;     // nabo_index::rerun: the set of the frame that sends rows to the 64-entry lists
+
 }  // namespace
 
 struct nabo_index {
@@ -309,12 +291,10 @@ struct nabo_index {
     bool shard_mode = false;       // set by nabo_sharded_query around its local queries: no masked tail (see tail_len)
 
     // Euclidean / cosine filter.  mode 0: fp32 MFMA only (l2_topk.hip); mode 1: f16x3 split on the f16 matrix pipe
-    // (K-concatenated operands, kc steps of 16 slots; g < 64): l2h_topk.hip (per-wave streaming) or, when shared is set
-    // and kc <= 10, l2s_topk.hip (reference tiles shared through an LDS ring) -- and the fp32 kernel for everything else
+    // (l2q_topk.hip: K-concatenated operands in the layout16 packing, kc steps of 16 slots; g < 64) -- and the fp32 kernel
+    // for everything else
     int mode = 0;
     int kc = 0;
-    bool shared = false;
-    bool q16 = false;              // l2q_topk.hip (16x16x32 MFMA shape; operands in the layout16 packing)
     // One-product first pass (l2q kernel on [hi | norm | error] operands of kc1 steps, pack_ctiles_kernel<.,.,1>): rows it
     // cannot certify go through the f16x3 pass (no_coarse), then the 64-entry lists, then the exact kernels.
     // Passes of a query, each on the rows the one before could not certify (pass_level while query_impl recurses):
@@ -333,12 +313,6 @@ struct nabo_index {
     double fscale = 1.0;           // power-of-two input scale of the fp32 path: max |y~| * fscale in (1/2, 1]
     int ksteps = 0;
     DevBuf centre, ypk, ycpk, ycpk1, normmax;
-    // locality order (order.hip; l2q kernel only): reference keys / permutation (resident), target keys / permutation and
-    // the waves' start tiles (per query), sort scratch
-    bool order = false;            // decided at creation (NABO_L2Q_ORDER=0 streams in caller order: same results)
-    int order_flags = 0;
-    bool ref_ordered = false;      // the packed f16 tiles are in key order
-    DevBuf rkeys, rperm, tkeys, tperm, wstart, okeys, opos, otemp;
     bool packed_f32 = false, packed_c16 = false, packed_c1 = false;
     int64_t ref_tiles = 0, ref_tiles_alloc = 0;
     double ymax_sqrt = 0.0, ymax_sqrt_c = 0.0;
@@ -352,12 +326,14 @@ struct nabo_index {
     int cb_mode = 0;              // NABO_CANBERRA_MODE at creation: 0 by size, 1 exact kernel only, 2 SWAR count, 3 bitmaps
 
     // query workspace
-    DevBuf xfail, tmpi, tmpd, exact_d, fails2;
-    DevBuf xfailp[2], tmpip[2], tmpdp[2], failsp[2], seedp[2], failseed;      // the same for passes 1 and 2 (the passes nest)
+    // Rows a pass could not certify, rerun one link down the pass chain (rerun_failed_rows): their row numbers, targets,
+    // the inner call's results and seeds.  One set per frame -- level 0, level 1, and [RERUN_WIDE] for the frame that sends
+    // rows to the 64-entry lists -- so that nested frames never share one; the modified-Canberra re-solve and set_ref's
+    // sample gather borrow [RERUN_WIDE].
+    struct RerunBufs { DevBuf rows, x, idx, dist, seed; } rerun[3];
+    DevBuf exact_d, failseed;
     DevBuf taupre, taupre2;                   // tournament seeds of the main / tail launch of the one-product pass [rows][S]
     DevBuf cand_key, cand_key2, cand_mi, cand_mt, cand_mi2, cand_mt2;   // filter keys of the lists; merged lists (merge_lists_kernel)
-    DevBuf piecebuf;                          // a launch cut into pieces: pieces | ranges (int32)
-    std::vector<int> piece_host;              // ... its host image (alive until the query's last synchronisation)
     int64_t pre_tiles_last = 0;               // reference tiles per split the last query's tournament looked at (0: none)
     int cand_slack = 3;                       // candidate mode on the one-product pass: kept entries beyond the emitted ones
     int64_t pass_rows[3] = {0, 0, 0};         // rows of the last query sent to the seeded pass / the f16x3 pass / the 64-entry lists
@@ -411,15 +387,13 @@ void index_set_cand_slack(nabo_index *ix, int s) { ix->cand_slack = s < 0 ? 0 : 
 //   mode (NABO_L2_MODE at nabo_index_create): unset / "f16x1" -- the DEFAULT chain: one-product pass (l2c_topk.hip, g <= 125)
 //   -> seeded one-product pass -> f16x3 split (l2q_topk.hip, g < 64 and k' <= 28) or fp32-MFMA filter (l2_topk.hip) ->
 //   64-entry lists -> exact float64 kernels;  "f16x3": the f16x3 split is the first pass;  "f32": the fp32-MFMA filter is.
-//   (-DNABO_EXPERIMENTS builds also know "f16x3h", "f16x3s", "f16x1h": the 32x32x16 kernels of l2h_topk.hip / l2s_topk.hip.)
+//   (The match is on the prefix: "f16x3h" / "f16x3s" select the f16x3 chain, any other string the default one.)
 static void index_init_filters(nabo_index *ix, const char *md)
 {
     const int g = ix->g;
     ix->mode = 0;
     ix->kc = ix->kc1 = 0;
-    ix->shared = ix->coarse = ix->order = false;
-    ix->q16 = true;
-    ix->order_flags = 0;
+    ix->coarse = false;
     ix->ksteps = 0;
     if (ix->metric == NABO_METRIC_MOD_CANBERRA) return;
     ix->ksteps = pick_ksteps(g);           // -1: g > NABO_MAX_COMPS, every query takes the exact float64 route
@@ -428,16 +402,8 @@ static void index_init_filters(nabo_index *ix, const char *md)
     if (!f32 && nabo::l2q_pick_kc(g) > 0) {
         ix->mode = 1;                       // an f16x3 kernel exists for this g (g < 64)
         ix->kc = nabo::l2q_pick_kc(g);
-#ifdef NABO_EXPERIMENTS
-        ix->shared = md && strcmp(md, "f16x3s") == 0 && nabo::l2s_pick_kc(g) == ix->kc;
-        ix->q16 = !(md && (strcmp(md, "f16x3h") == 0 || strcmp(md, "f16x3s") == 0 || strcmp(md, "f16x1h") == 0));
-        // locality order (order.hip; option "order_flags", bit flags: 1 references, 2 targets in key order, 4 home pre-pass):
-        // cuts the list updates by 30 % and the kernel is 20 % SLOWER on it (profiles/r3_order_experiment.txt)
-        ix->order_flags = ix->q16 ? ix->opt.order_flags : 0;
-        ix->order = (ix->order_flags & 1) != 0;
-#endif
-        ix->kc1 = ix->q16 ? nabo::l2c_pick_kc(g) : nabo::l2q_pick_kc1(g);
-        ix->coarse = !ix->shared && ix->kc1 > 0 && !f16x3;
+        ix->kc1 = nabo::l2c_pick_kc(g);
+        ix->coarse = ix->kc1 > 0 && !f16x3;
     } else if (!f32 && !f16x3 && nabo::l2c_pick_kc(g) > 0) {
         // 64 <= g <= 125: no f16x3 kernel is instantiated, but the one-product operands (g + 3 slots: four steps of 32)
         // are -- the one-product pass runs first, the fp32-MFMA filter takes the rows it cannot certify
@@ -467,22 +433,6 @@ static int note_row_pass(nabo_index *ix, const uint32_t *d_rows, int64_t nf, uin
     return NABO_OK;
 }
 
-#ifdef NABO_EXPERIMENTS
-// Locality order of `n` rows of V (order.hip): sorted keys and the permutation, on the index's stream.
-static int order_rows(nabo_index *ix, const double *V, int64_t n, DevBuf &keys, DevBuf &perm)
-{
-    int rc;
-    size_t tb = 0;
-    HIP_TRY(nabo::loc_sort_temp_bytes(n, nabo::loc_key_bits(ix->g), &tb));
-    if ((rc = ix->okeys.reserve((size_t)n * 4)) || (rc = ix->opos.reserve((size_t)n * 4)) || (rc = keys.reserve((size_t)n * 4)) ||
-        (rc = perm.reserve((size_t)n * 4)) || (rc = ix->otemp.reserve(tb + 16)))
-        return rc;
-    HIP_TRY(nabo::loc_order_launch(V, n, ix->g, ix->centre.as<double>(), ix->okeys.as<uint32_t>(), ix->opos.as<uint32_t>(),
-                                   keys.as<uint32_t>(), perm.as<uint32_t>(), ix->otemp.p, tb, ix->stream));
-    return NABO_OK;
-}
-#endif
-
 // Pack the resident references for the fp32-MFMA kernel (want = 0), the f16x3 kernels (1: K-concatenated f16 tiles) or
 // the one-product pass of the l2q kernel (2).
 static int ensure_packed(nabo_index *ix, int want)
@@ -511,32 +461,16 @@ static int ensure_packed(nabo_index *ix, int want)
     if (want == 2) {
         if ((rc = ix->ycpk1.reserve((size_t)ix->ref_tiles_alloc * ix->kc1 * 1024 + 128))) return rc;
         ix->hscale = scale = std::ldexp(1.0, e2 + 12);
-        ix->ref_ordered = false;
-#ifdef NABO_EXPERIMENTS
-        if (ix->order) {             // (the same keys, hence the same permutation, as the f16x3 operands of the second pass)
-            if ((rc = order_rows(ix, ix->dYp, ix->n, ix->rkeys, ix->rperm))) return rc;
-            ix->ref_ordered = true;
-        }
-#endif
         HIP_TRY(nabo::pack_cref_launch(ix->dYp, ix->n, ix->g, ix->centre.as<double>(), ix->hscale, ix->kc1,
                                        ix->ref_tiles_alloc, ix->dmask, ix->ycpk1.as<unsigned char>(),
-                                       ix->normmax.as<unsigned int>(), ix->q16, st,
-                                       ix->ref_ordered ? ix->rperm.as<uint32_t>() : nullptr, 1));
+                                       ix->normmax.as<unsigned int>(), true, st, nullptr, 1));
     } else if (want_h) {
         if ((rc = ix->ycpk.reserve((size_t)ix->ref_tiles_alloc * ix->kc * 1024 + 128))) return rc;
         // |v| <= 2^12 after scaling (f16 overflows at 65504; targets carry a factor 2)
         ix->hscale = scale = std::ldexp(1.0, e2 + 12);
-        ix->ref_ordered = false;
-#ifdef NABO_EXPERIMENTS
-        if (ix->order) {
-            if ((rc = order_rows(ix, ix->dYp, ix->n, ix->rkeys, ix->rperm))) return rc;
-            ix->ref_ordered = true;
-        }
-#endif
         HIP_TRY(nabo::pack_cref_launch(ix->dYp, ix->n, ix->g, ix->centre.as<double>(), ix->hscale, ix->kc,
                                        ix->ref_tiles_alloc, ix->dmask, ix->ycpk.as<unsigned char>(),
-                                       ix->normmax.as<unsigned int>(), ix->q16, st,
-                                       ix->ref_ordered ? ix->rperm.as<uint32_t>() : nullptr));
+                                       ix->normmax.as<unsigned int>(), true, st));
     } else {
         const int Q = (ix->ksteps + 3) / 4;
         const size_t tile_bytes = ((size_t)Q * 256 + 32) * sizeof(float);
@@ -650,15 +584,9 @@ int nabo_index_set_option(nabo_index *ix, const char *name, int64_t value)
     if (!ix || !name) return fail(NABO_E_INVALID, "NULL argument");
     if (ix->async_busy) return fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
     if (!option_set(ix->opt, name, value)) return fail(NABO_E_INVALID, "unknown option '%s'", name);
-    if (strcmp(name, "order_flags") == 0) {
-#ifdef NABO_EXPERIMENTS
-        ix->order_flags = ix->q16 ? (int)value : 0;
-        ix->order = (ix->order_flags & 1) != 0;
-        ix->packed_f32 = ix->packed_c16 = ix->packed_c1 = false;
-#else
+    if (strcmp(name, "order_flags") == 0) {      // (locality-ordered streaming was measured slower and removed)
         ix->opt.order_flags = 0;
-        return fail(NABO_E_UNSUPPORTED, "option '%s' exists in -DNABO_EXPERIMENTS builds only", name);
-#endif
+        return fail(NABO_E_UNSUPPORTED, "option '%s' (locality-ordered streaming, once in experiments builds only) was removed", name);
     }
     return NABO_OK;
 }
@@ -781,16 +709,17 @@ int nabo_index_set_ref(nabo_index *ix, const double *Y, int32_t y_on_device, con
                     const int B = nabo::cbb_buckets();
                     int64_t ns = ix->n < 2048 ? ix->n : 2048;          // (32 sample values per bucket; the sort is host time inside set_ref)
                     const int64_t stride = ix->n / ns;
-                    std::vector<double> smp((size_t)ns * G), col((size_t)ns), edges((size_t)G * (B - 1));
+                    std::vector<double> smp((size_t)ns * G), edges((size_t)G * (B - 1));
                     {   // the sample rows: gathered on the device, ONE contiguous copy back (a strided 2-D copy of 2048 short rows
                         // to pageable memory took milliseconds)
                         std::vector<uint32_t> rows_h((size_t)ns);
                         for (int64_t i = 0; i < ns; ++i) rows_h[(size_t)i] = (uint32_t)(i * stride);
-                        if ((rc = ix->fails2.reserve((size_t)ns * sizeof(uint32_t)))) return rc;
-                        if ((rc = ix->xfail.reserve((size_t)ns * G * sizeof(double)))) return rc;
-                        HIP_TRY(hipMemcpyAsync(ix->fails2.p, rows_h.data(), (size_t)ns * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-                        HIP_TRY(nabo::gather_rows_launch(ix->dY, ix->fails2.as<uint32_t>(), ns, G, ix->xfail.as<double>(), st));
-                        HIP_TRY(hipMemcpyAsync(smp.data(), ix->xfail.p, (size_t)ns * G * sizeof(double), hipMemcpyDeviceToHost, st));
+                        nabo_index::RerunBufs &b = ix->rerun[RERUN_WIDE];
+                        if ((rc = b.rows.reserve((size_t)ns * sizeof(uint32_t)))) return rc;
+                        if ((rc = b.x.reserve((size_t)ns * G * sizeof(double)))) return rc;
+                        HIP_TRY(hipMemcpyAsync(b.rows.p, rows_h.data(), (size_t)ns * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+                        HIP_TRY(nabo::gather_rows_launch(ix->dY, b.rows.as<uint32_t>(), ns, G, b.x.as<double>(), st));
+                        HIP_TRY(hipMemcpyAsync(smp.data(), b.x.p, (size_t)ns * G * sizeof(double), hipMemcpyDeviceToHost, st));
                         HIP_TRY(hipStreamSynchronize(st));
                     }
                     // (one sort per dimension: a few host threads -- 50 sorts of 2048 values were 3.9 ms of every set_ref)
@@ -821,7 +750,6 @@ int nabo_index_set_ref(nabo_index *ix, const double *Y, int32_t y_on_device, con
                         }
                         if (!threaded) edges_of(0, G);           // (also after a failed thread start: every dimension again)
                     }
-                    (void)col;
                     if ((rc = ix->cbedges.reserve(edges.size() * sizeof(double)))) return rc;
                     if ((rc = ix->cbtab.reserve(nabo::cbb_table_bytes(ix->n, G)))) return rc;
                     if ((rc = ix->cbvalid.reserve(nabo::cbb_valid_bytes(ix->n)))) return rc;
@@ -867,77 +795,16 @@ int nabo_index_set_mask(nabo_index *ix, const uint8_t *ref_mask)
 struct L2Plan {
     int epl = 1, L = 32;                 // emitted candidate lists hold L = 32 epl entries
     bool use_h = false;                  // an f16 kernel runs (one-product or f16x3 operands); false: the fp32-MFMA filter
-    bool use_c = false;                  // experiments: the shared-tile f16x3 kernel
     bool use_1 = false;                  // one-product operands
     bool on_l2c = false;                 // ... on the l2c kernel (geo: its geometry)
     bool r1 = false;                     // fp32 filter: one row-block per wave
-    int geo = -1, kcq = 0, slack1 = 0, cslack = 0;
+    int geo = -1, kcq = 0, cslack = 0;
     int rows_per_wg = 256, wg_per_cu = 1, lkeep_max = 32, lkeep = 16, want = 16;
     int S = 1, S2 = 1;                   // reference splits of the main / tail launch
-    bool forced = false;                 // the split count is the caller's (option "splits")
     bool one_round = false;              // fewer column-workgroups than slots: splits (+ a tail launch on long streams) fill one round
-    bool pieces = false;                 // the launch is cut into pieces (cut_pieces): piece_wgs workgroups of ~piece_len tiles, S = lists per row
-    int piece_wgs = 0;
-    int64_t piece_len = 0;
     int64_t gx = 0, gx_main = 0, gx_tail = 0, rows_pad = 0, tps = 0, tps2 = 0;
     char kernel[160] = "";
 };
-
-// A launch with fewer column-workgroups (gx) than the chip has slots, cut into pieces: the linear space (column, reference
-// tile) of gx x T tiles goes to n_wg <= slots workgroups in equal chunks of ~C tiles (at least min_len: every piece warms
-// its lists up on its own), a chunk that crosses a column boundary is two pieces, and a boundary that would leave a sliver of
-// a column (< tiny tiles) is moved onto the column boundary.  Out: pieces (column, slot, t0, t1) in workgroup order,
-// wg_first [chunks + 1] (which pieces a chunk holds), count [gx] pieces per column, *n_wg_out pieces in all (one workgroup
-// each, l2c_topk.hip); returns the largest count (= lists per row, S).
-static int cut_pieces(int64_t gx, int64_t T, int64_t slots, int64_t min_len, int max_per_col, std::vector<int> *pieces,
-                      std::vector<int> *wg_first, std::vector<int> *count, int *n_wg_out, int64_t *len_out)
-{
-    const int64_t total = gx * T;
-    // (a column is cut at most floor(T / C) + 2 ways: chunks long enough that a row never has more than max_per_col lists)
-    if (max_per_col >= 3 && min_len < (T + max_per_col - 3) / (max_per_col - 2)) min_len = (T + max_per_col - 3) / (max_per_col - 2);
-    int64_t n_wg = total / (min_len > 0 ? min_len : 1);
-    if (n_wg > slots) n_wg = slots;
-    if (n_wg < gx) n_wg = gx < slots ? gx : slots;
-    if (n_wg < 1) n_wg = 1;
-    int64_t C = (total + n_wg - 1) / n_wg;
-    C = (C + 3) & ~(int64_t)3;
-    if (C > T && gx >= n_wg) C = T;                       // (one column per workgroup at most when there is nothing to balance)
-    const int64_t tiny = std::max<int64_t>(8, std::min<int64_t>(T / 4, C / 6));
-    std::vector<int64_t> cutpos;                          // chunk boundaries in linear tile space
-    cutpos.push_back(0);
-    for (int64_t b = C; b < total; b += C) {
-        int64_t bb = b;
-        const int64_t pos = bb % T;
-        if (pos != 0 && pos < tiny) bb -= pos;
-        else if (pos != 0 && T - pos < tiny) bb += T - pos;
-        if (bb > cutpos.back() && bb < total) cutpos.push_back(bb);
-    }
-    cutpos.push_back(total);
-    if (pieces) pieces->clear();
-    if (wg_first) wg_first->clear();
-    std::vector<int> cnt((size_t)gx, 0);
-    int np = 0, smax = 0;
-    for (size_t w = 0; w + 1 < cutpos.size(); ++w) {
-        if (wg_first) wg_first->push_back(np);
-        int64_t lin = cutpos[w];
-        while (lin < cutpos[w + 1]) {
-            const int64_t col = lin / T, t0 = lin % T;
-            const int64_t t1 = std::min<int64_t>(T, t0 + (cutpos[w + 1] - lin));
-            const int slot = cnt[(size_t)col]++;
-            if (pieces) { pieces->push_back((int)col); pieces->push_back(slot); pieces->push_back((int)t0); pieces->push_back((int)t1); }
-            ++np;
-            if (slot + 1 > smax) smax = slot + 1;
-            lin += t1 - t0;
-        }
-    }
-    if (wg_first) wg_first->push_back(np);
-    if (count) *count = cnt;
-    if (n_wg_out) *n_wg_out = np;                          // one workgroup per piece (chunks + column crossings)
-    if (len_out) *len_out = C;
-    return smax;
-}
-// shortest chunk of a cut launch, in reference tiles (30k x 30k, d = 50: four pieces of 234 tiles per column beat six and eight)
-static const int64_t PIECE_MIN_TILES = 192;
 
 static int plan_l2(const nabo_index *ix, int64_t m, int k, int drop, bool cand_mode, L2Plan *P)
 {
@@ -945,23 +812,15 @@ static int plan_l2(const nabo_index *ix, int64_t m, int k, int drop, bool cand_m
     const int epl = ((kk <= 24 && !ix->wide_retry) || cand_mode) ? 1 : 2;
     const int L = 32 * epl;
     int rows_per_wg = 256, wg_per_cu = 1, lkeep_max = L;
-    bool use_h = false, use_c = false;                   // use_h: an f16x3 kernel runs; use_c: the shared-tile one
+    bool use_h = false;                                  // an f16x3 kernel runs
     if (ix->mode == 1 && epl == 1) {
-#ifdef NABO_EXPERIMENTS
-        if (ix->shared) {
-            nabo::l2s_topk_geometry(ix->kc, &rows_per_wg, &wg_per_cu, &lkeep_max);
-            use_c = (cand_mode ? kk : kk + 4) <= lkeep_max;
-        }
-        if (!use_c && !ix->q16) nabo::l2h_topk_geometry(ix->kc, &rows_per_wg, &wg_per_cu, &lkeep_max);
-        else
-#endif
-        if (!use_c) nabo::l2q_topk_geometry(ix->kc, &rows_per_wg, &wg_per_cu, &lkeep_max);
+        nabo::l2q_topk_geometry(ix->kc, &rows_per_wg, &wg_per_cu, &lkeep_max);
         use_h = (cand_mode ? kk : kk + 4) <= lkeep_max;   // needs at least 4 entries of slack
     }
     // The one-product first pass (kc1-step operands; see nabo_index::coarse) -- on the l2c kernel, in the geometry that
     // serves the list length the pass wants (l2c_topk.hip: two waves per SIMD up to 23 kept entries, 32-entry lists,
-    // 64-entry lists for k' > 24), unless the locality order, the 32x32x16 experiment or an A/B run sends the operands
-    // through the l2q / l2h kernel (those serve 32-entry lists and g < 64 only).
+    // 64-entry lists for k' > 24), unless option coarse_kernel_q sends the operands through the l2q kernel (32-entry lists
+    // and g < 64 only).
     const bool pass1 = ix->coarse && !(ix->coarse_weak && ix->opt.coarse_adapt != 0) && ix->pass_level < 2 &&
                        !ix->wide_retry && (!cand_mode || kk + 3 <= 32);
     // (k' > 24, the 64-entry lists: six entries more -- there a row the first pass fails is expensive, the pass behind the
@@ -973,15 +832,14 @@ static int plan_l2(const nabo_index *ix, int64_t m, int k, int drop, bool cand_m
     if (epl == 1 && want > 32) want = 32;                // (the emitted lists hold 32 epl entries)
     if (epl == 2) want = want < 33 ? 33 : (want > 64 ? 64 : want);
     int geo = -1;
-    if (pass1 && ix->q16 && ix->order_flags == 0 && ix->opt.coarse_kernel_q == 0 && kk + 4 <= L) {
+    if (pass1 && ix->opt.coarse_kernel_q == 0 && kk + 4 <= L) {
         geo = nabo::l2c_geometry(ix->kc1, want, ix->opt.l2c_geo);
         if (epl == 1 && geo == 2) geo = 0;               // (NABO_L2C_GEO=c with 32-entry emitted lists: geometry A)
     }
     const bool on_l2c = geo >= 0;
-    const bool use_1 = on_l2c || (pass1 && use_h && !use_c);
+    const bool use_1 = on_l2c || (pass1 && use_h);
     if (on_l2c) {
         use_h = true;
-        use_c = false;
         nabo::l2c_topk_geometry(ix->kc1, want, ix->opt.l2c_geo, &rows_per_wg, &wg_per_cu, &lkeep_max);
         if (geo == 0) { rows_per_wg = 4 * 128; lkeep_max = 32; }
     }
@@ -1034,31 +892,17 @@ static int plan_l2(const nabo_index *ix, int64_t m, int k, int drop, bool cand_m
     int S2 = 1;
     int S = ix->opt.splits;
     const bool forced = S > 0;
-    bool pieces = false;
-    int piece_wgs = 0;
-    int64_t piece_len = 0;
-#ifdef NABO_EXPERIMENTS                                     // (measured slower than uniform splits: section 4.6 of DESIGN.md; tools/ab builds only)
-    if (!forced && on_l2c && ix->opt.pieces != 0 && ix->pass_level == 0 && !ix->wide_retry && gx < slots &&
-        ix->ref_tiles >= 64 && ix->ref_tiles * 32 < NABO_LIST_SPLIT_REFS &&
-        (ix->opt.split_refs_max < 64 || ix->ref_tiles * 32 < ix->opt.split_refs_max)) {
-        const int sp = cut_pieces(gx, ix->ref_tiles, slots, PIECE_MIN_TILES, 1024 / L, nullptr, nullptr, nullptr, &piece_wgs, &piece_len);
-        if (sp * L <= 1024) {                             // (merge / refine handle up to 1024 candidates per row)
-            pieces = true;
-            S = sp;
-        }
-    }
-#endif
     // Fewer column-workgroups than slots, one-product kernel, lists merged before the float64 step (so a row's list count
     // costs the refine nothing): ONE round of workgroups at full occupancy -- all the columns with floor(slots / gx) uniform
     // splits when that fills at least 80 % of the slots.  On LONG reference streams (>= 8192 tiles) also one split more on
     // the floor(slots / S) columns that fit, the columns left over as a tail launch with more splits (the main / tail pair
     // of the long queries): 120k x 1M: 256 x 2 + 57 x 8, 13.3 instead of 16.1 ms.  On short streams a tail costs more than
     // the idle slots (100k x 100k: 256 x 2 + 5 x 16 behind the main launch 2.44 ms, beside it on the second stream 2.55,
-    // 261 x 1 2.42), and so does cutting the (column, tile) space into equal chunks ("pieces", off): workgroups of a uniform
+    // 261 x 1 2.42), and so did cutting the (column, tile) space into equal chunks ("pieces", removed): workgroups of a uniform
     // split stream the same tiles at the same time and share them in L2, unaligned pieces do not (49k x 100k: kernel
     // 1.99 ms as 603 pieces, 1.10 ms as 128 x 4).
     bool one_round = false;
-    if (!forced && !pieces && on_l2c && ix->opt.one_round != 0 && ix->opt.merge_lists != 0 && ix->pass_level == 0 && !ix->wide_retry &&
+    if (!forced && on_l2c && ix->opt.one_round != 0 && ix->opt.merge_lists != 0 && ix->pass_level == 0 && !ix->wide_retry &&
         gx < slots) {
         int64_t s_cap = ix->ref_tiles / 16 > 0 ? ix->ref_tiles / 16 : 1;     // >= 16 tiles per split
         if (s_cap > 1024 / L) s_cap = 1024 / L;
@@ -1081,7 +925,7 @@ static int plan_l2(const nabo_index *ix, int64_t m, int k, int drop, bool cand_m
         }
         one_round = occ >= 0.8 || gx_tail > 0;               // (otherwise the cost model below decides)
     }
-    if (!forced && !pieces && !one_round) {
+    if (!forced && !one_round) {
         S = 1;
         if (gx < slots) {
             // Fewer workgroups than the chip holds: pick the split count from a cost model.  A workgroup costs
@@ -1091,8 +935,7 @@ static int plan_l2(const nabo_index *ix, int64_t m, int k, int drop, bool cand_m
             int64_t s_hi = ix->ref_tiles / 16 > 0 ? ix->ref_tiles / 16 : 1;
             if (s_hi > 1024 / L) s_hi = 1024 / L;
             // ms per reference tile and workgroup, measured: 105 ms / 31250 tiles (fp32, 256 rows, 25 k-steps); 1.2 us f16x3
-            const double t_tile = use_c ? 0.7e-3 * ix->kc / 10.0 : use_h ? 1.1e-3 * kcq / 10.0
-                                                                    : 3.36e-3 * (rows_per_wg / 256.0) * (ix->ksteps / 25.0);
+            const double t_tile = use_h ? 1.1e-3 * kcq / 10.0 : 3.36e-3 * (rows_per_wg / 256.0) * (ix->ksteps / 25.0);
             double best = 1e30;
             for (int s2 = 1; s2 <= (int)s_hi; ++s2) {
                 const double rounds = (double)((gx * s2 + slots - 1) / slots);
@@ -1134,30 +977,24 @@ static int plan_l2(const nabo_index *ix, int64_t m, int k, int drop, bool cand_m
         if (S < s_min) S = (int)s_min;
         if (gx_tail > 0 && S2 < s_min) S2 = (int)s_min;
     }
-    const int64_t tps = pieces ? ix->ref_tiles : (ix->ref_tiles + S - 1) / S;      // (pieces: the longest a piece can be)
+    const int64_t tps = (ix->ref_tiles + S - 1) / S;
     const int64_t tps2 = (ix->ref_tiles + S2 - 1) / S2;
-    if ((!pieces && tps * S > ix->ref_tiles_alloc) || tps2 * S2 > ix->ref_tiles_alloc)
+    if (tps * S > ix->ref_tiles_alloc || tps2 * S2 > ix->ref_tiles_alloc)
         return fail(NABO_E_INVALID, "internal: split padding exceeds allocation");
 
     P->epl = epl; P->L = L;
-    P->use_h = use_h; P->use_c = use_c; P->use_1 = use_1; P->on_l2c = on_l2c; P->r1 = r1;
-    P->geo = geo; P->kcq = kcq; P->slack1 = slack1; P->cslack = cslack;
+    P->use_h = use_h; P->use_1 = use_1; P->on_l2c = on_l2c; P->r1 = r1;
+    P->geo = geo; P->kcq = kcq; P->cslack = cslack;
     P->rows_per_wg = rows_per_wg; P->wg_per_cu = wg_per_cu; P->lkeep_max = lkeep_max; P->lkeep = lkeep; P->want = want;
-    P->S = S; P->S2 = S2; P->forced = forced;
-    P->pieces = pieces; P->piece_wgs = piece_wgs; P->piece_len = piece_len; P->one_round = one_round;
+    P->S = S; P->S2 = S2; P->one_round = one_round;
     P->gx = gx; P->gx_main = gx_main; P->gx_tail = gx_tail; P->rows_pad = rows_pad; P->tps = tps; P->tps2 = tps2;
-    {
-        // (the locality-ordered stream and NABO_COARSE_KERNEL_Q run the one-product operands through the l2q kernel)
-        if (use_1 && ix->q16 && !on_l2c)
-            snprintf(P->kernel, sizeof(P->kernel), "l2q_topk_kernel<%d,1,33> (v_mfma_f32_16x16x32_f16, one-product f16 filter with the split error as an operand slot)", kcq);
-        else if (use_1 && ix->q16) snprintf(P->kernel, sizeof(P->kernel), "l2c_topk_kernel<%d,%s> (v_mfma_f32_16x16x32_f16, one-product f16 filter with the split error as an operand slot)", kcq / 2, geo == 1 ? "1,23,6,32,4,2" : geo == 2 ? "2,65,4,64,4,1" : "1,33,8,64,4,1");
-        else if (use_1) snprintf(P->kernel, sizeof(P->kernel), "l2h_topk_kernel<%d,4,1,33> (v_mfma_f32_32x32x16_f16, one-product f16 filter with the split error as an operand slot)", kcq);
-        else if (use_c) snprintf(P->kernel, sizeof(P->kernel), "l2s_topk_kernel<%d> (v_mfma_f32_32x32x16_f16, K-concatenated f16x3 split, LDS tile ring)", ix->kc);
-        else if (use_h && ix->q16) snprintf(P->kernel, sizeof(P->kernel), "l2q_topk_kernel<%d,1,33> (v_mfma_f32_16x16x32_f16, K-concatenated f16x3 split)", ix->kc);
-        else if (use_h) snprintf(P->kernel, sizeof(P->kernel), "l2h_topk_kernel<%d,4,1,33> (v_mfma_f32_32x32x16_f16, K-concatenated f16x3 split)", ix->kc);
-        else snprintf(P->kernel, sizeof(P->kernel), "l2_topk_kernel<%d,%d,%d,%d> (v_mfma_f32_32x32x2_f32)", ix->ksteps,
-                      r1 ? 1 : (epl == 1 ? 2 : 1), epl, epl == 1 ? 33 : 65);
-    }
+    // (option coarse_kernel_q runs the one-product operands through the l2q kernel)
+    if (use_1 && !on_l2c)
+        snprintf(P->kernel, sizeof(P->kernel), "l2q_topk_kernel<%d,1,33> (v_mfma_f32_16x16x32_f16, one-product f16 filter with the split error as an operand slot)", kcq);
+    else if (use_1) snprintf(P->kernel, sizeof(P->kernel), "l2c_topk_kernel<%d,%s> (v_mfma_f32_16x16x32_f16, one-product f16 filter with the split error as an operand slot)", kcq / 2, geo == 1 ? "1,23,6,32,4,2" : geo == 2 ? "2,65,4,64,4,1" : "1,33,8,64,4,1");
+    else if (use_h) snprintf(P->kernel, sizeof(P->kernel), "l2q_topk_kernel<%d,1,33> (v_mfma_f32_16x16x32_f16, K-concatenated f16x3 split)", ix->kc);
+    else snprintf(P->kernel, sizeof(P->kernel), "l2_topk_kernel<%d,%d,%d,%d> (v_mfma_f32_32x32x2_f32)", ix->ksteps,
+                  r1 ? 1 : (epl == 1 ? 2 : 1), epl, epl == 1 ? 33 : 65);
     return NABO_OK;
 }
 
@@ -1178,6 +1015,582 @@ static int query_impl(nabo_index *ix, const double *X, int32_t x_on_device, int6
     const int rc = query_body(ix, X, x_on_device, m, k, drop_first, out_idx, out_dist, out_on_device, cand_mode, out_bound);
     --ix->depth;
     return rc;
+}
+
+// What every route of a query reads (query_body stages it), and what the route leaves for finish_query.
+struct Query {
+    const double *dX = nullptr;      // [m, g] targets on the device
+    int64_t m = 0;
+    int k = 0, drop = 0, kk = 0;     // kk = k + drop
+    int epl = 1, L = 32;             // emitted candidate lists hold L = 32 epl entries
+    int64_t *d_oidx = nullptr;       // [m, k] results on the device
+    double *d_odist = nullptr;
+    bool cand_mode = false;
+    double *out_bound = nullptr;
+    bool top = false;                // this call owns the per-row pass record
+    std::vector<uint32_t> pass_map;  // top-level rows of the batch an inner call works on
+    unsigned int n_fail = 0;         // set by the route: counters[0], [1], [3] of nabo_index_last_stats
+    int S = 1;
+    int64_t n_wg = 0;
+    bool timing_only = false;        // debug_ablate: the route stopped behind the filter and set ms[1] itself
+};
+
+// Rows of the exact kernels' distance workspace: ~1 GiB of float64 rows, at least one, at most `rows` and `cap`.
+static int reserve_exact_ws(nabo_index *ix, uint64_t rows, uint64_t cap, unsigned int *d_rows)
+{
+    uint64_t r = (1ull << 30) / ((uint64_t)ix->n * sizeof(double));
+    if (r < 1) r = 1;
+    if (r > rows) r = rows;
+    if (r > cap) r = cap;
+    *d_rows = (unsigned int)r;
+    return ix->exact_d.reserve((size_t)r * ix->n * sizeof(double));
+}
+
+// Shapes outside the instantiated filter kernels: the exact float64 kernels answer every row.
+static int query_exact(nabo_index *ix, Query &q)
+{
+    hipStream_t st = ix->stream;
+    int rc;
+    unsigned int d_rows = 0;
+    if (q.top) ix->row_pass.assign((size_t)q.m, (uint8_t)NABO_PASS_EXACT);
+    if (q.m > 0xFFFFFFF0ll) return fail(NABO_E_UNSUPPORTED, "m=%lld: fewer than 2^32-16 rows per call", (long long)q.m);
+    if ((rc = ix->fails.reserve((size_t)q.m * sizeof(uint32_t)))) return rc;
+    if ((rc = reserve_exact_ws(ix, (uint64_t)q.m, 65528, &d_rows))) return rc;
+    HIP_TRY(nabo::iota_launch(ix->fails.as<uint32_t>(), q.m, st));
+    for (int i = 1; i <= 3; ++i) HIP_TRY(hipEventRecord(ix->ev[i], st));
+    HIP_TRY(nabo::exact_rows_launch(q.dX, ix->dY, ix->n, ix->g, ix->metric, ix->f, ix->dmask, ix->fails.as<uint32_t>(),
+                                    (unsigned int)q.m, q.k, q.drop, ix->base, ix->mlistbuf.as<uint32_t>(), tail_len(ix),
+                                    q.d_oidx, q.d_odist, ix->exact_d.as<double>(), d_rows, st));
+    HIP_TRY(hipEventRecord(ix->ev[4], st));
+    q.n_fail = (unsigned int)q.m;
+    q.S = 0;
+    snprintf(ix->kernel, sizeof(ix->kernel), "exact_dist_rows_kernel + exact_select_rows_kernel (float64 brute force)");
+    return NABO_OK;
+}
+
+// One of the two launches of a filter pass (plan_l2): the main launch, and the tail round of workgroups with its own split
+// count.  Each has its own candidate lists, tournament seeds and merged lists.
+struct L2Part {
+    int64_t gx, row0, rows;          // column-workgroups, first target row, target rows (padded)
+    int S;                           // reference splits
+    int64_t tps;                     // reference tiles per split
+    DevBuf *idx, *tau, *key, *mi, *mt, *pre;    // lists: indices, thresholds, filter keys; merged lists; tournament seeds
+    bool merge = false;              // merge_lists_kernel reduces the S lists of a row to one of `keep` entries (lout slots)
+    int keep = 0, lout = 0;
+    int64_t end(int64_t m) const { return row0 + rows < m ? row0 + rows : m; }
+};
+
+// The filter kernels of a pass, main launch then tail: the one-product kernel behind its tournament seeds (l2c_topk.hip),
+// or the f16x3 (l2q_topk.hip) / fp32 (l2_topk.hip) filter.  *beside: ev_main was recorded between the two launches -- the
+// refine of the main launch's rows runs on the second stream beside the tail launch.
+static int l2_filter(nabo_index *ix, const Query &q, const L2Plan &P, L2Part (&part)[2], const float *seeds, bool *beside)
+{
+    hipStream_t st = ix->stream;
+    int rc;
+    const int64_t pad_tile = ix->ref_tiles_alloc - 1;
+    const bool first = ix->pass_level == 0 && !ix->wide_retry;
+    const unsigned char *xh = ix->xpk.as<unsigned char>();
+    const unsigned char *yh = P.use_1 ? ix->ycpk1.as<unsigned char>() : ix->ycpk.as<unsigned char>();
+    *beside = false;
+    if (!P.on_l2c) {
+        for (L2Part &p : part) {
+            if (p.gx == 0) continue;
+            if (P.use_h)
+                HIP_TRY(nabo::l2q_topk_launch(P.kcq, xh, yh, (int)p.tps, p.S, (int)p.gx, p.row0 / 32, P.lkeep, p.idx->as<uint32_t>(),
+                                              nullptr, p.tau->as<float>(), pad_tile, st));
+            else
+                HIP_TRY(nabo::l2_topk_launch(ix->ksteps, P.r1 ? -1 : q.epl, ix->xpk.as<float>(), ix->ypk.as<float>(), (int)p.tps,
+                                             p.S, (int)p.gx, p.row0 / 32, P.lkeep, p.idx->as<uint32_t>(), nullptr,
+                                             p.tau->as<float>(), st));
+        }
+        return NABO_OK;
+    }
+    // Tournament seeds (l2c_topk.hip: l2c_pre_kernel): every (row, split) list starts from an upper bound of its
+    // lkeep-th smallest score among the split's first references instead of +inf -- not for a pass that has its
+    // seeds already.  Option prepass: 0 off, otherwise percent of the planned length (same bits always).
+    const int pre_pct = seeds ? 0 : ix->opt.prepass;
+    const float *seed[2] = {seeds, seeds};
+    int stride[2] = {0, 0};
+    if (first) ix->pre_tiles_last = 0;
+    for (int i = 0; i < 2 && pre_pct > 0; ++i) {
+        L2Part &p = part[i];
+        int pt = 0, gt = 2;
+        nabo::l2c_pre_plan(P.kcq, P.lkeep, (int)p.tps, pre_pct, &pt, &gt);
+        if (pt <= 0 || p.gx == 0) continue;
+        if ((rc = p.pre->reserve((size_t)p.rows * p.S * sizeof(float)))) return rc;
+        HIP_TRY(nabo::l2c_pre_launch(P.kcq, P.lkeep, xh, yh, (int)p.tps, p.S, p.rows, p.row0 / 32, pt, gt, pad_tile, st, q.m,
+                                     p.pre->as<float>()));
+        seed[i] = p.pre->as<float>();
+        stride[i] = p.S;
+        if (i == 0 && first) ix->pre_tiles_last = pt;
+    }
+    for (int i = 0; i < 2; ++i) {
+        L2Part &p = part[i];
+        if (p.gx == 0) continue;
+        HIP_TRY(nabo::l2c_topk_launch(P.kcq, P.geo, xh, yh, (int)p.tps, p.S, (int)p.gx, p.row0 / 32, P.lkeep,
+                                      p.idx->as<uint32_t>(), p.merge ? p.key->as<float>() : nullptr, p.tau->as<float>(),
+                                      pad_tile, st, q.m, seed[i], stride[i], p.row0));
+        // the tail launch (a fraction of a round, reference splits) leaves most CUs idle: the refine of the main
+        // launch's rows (an HBM gather) runs beside it on the second stream
+        if (i == 0 && part[1].gx > 0 && !q.cand_mode && ix->opt.refine_overlap != 0) {
+            HIP_TRY(hipEventRecord(ix->ev_main, st));
+            *beside = true;
+        }
+    }
+    return NABO_OK;
+}
+
+// The float64 re-evaluation of a pass's lists (refine.hip), main launch then tail, each behind the merge of its lists
+// where the pass merges them: certified rows and the fail list, or in candidate mode candidates and bounds.  beside: the
+// main launch's part runs on the second stream (l2_filter).
+static int l2_refine(nabo_index *ix, const Query &q, const L2Plan &P, L2Part (&part)[2], bool beside, float *fail_seed)
+{
+    hipStream_t st = ix->stream;
+    // rounding-error coefficient of the filter score, relative to (||x|| + max||y||)^2
+    // (f16x3: one fp32 accumulation per product term, 16 per step, plus the dropped lo*lo term and the
+    // representation error of the hi + lo split)
+    // (one-product pass: the hi x lo, lo x hi and lo x lo terms are INSIDE its score -- the error slot of
+    // pack_ctiles_kernel<.,.,1> -- so the same accumulation / representation coefficient applies to its kc1 steps)
+    const double err_coef = P.use_h ? 1.05 * ((16.0 * P.kcq + 8.0) * std::ldexp(1.0, -24) + std::ldexp(1.0, -20) + std::ldexp(1.0, -21))
+                                    : 1.05 * (2.0 * ix->ksteps + 4.0) * std::ldexp(1.0, -24);
+    const double tau_scale = P.use_h ? 1.0 / (ix->hscale * ix->hscale) : 1.0 / (ix->fscale * ix->fscale);
+    const double ymax_sqrt = P.use_h ? ix->ymax_sqrt_c : ix->ymax_sqrt;
+    const int metric = ix->metric == NABO_METRIC_COSINE ? 2 : 0;
+    const int64_t n_valid = ix->n - ix->n_masked;
+    auto merge = [&](L2Part &p, hipStream_t s) {
+        return nabo::merge_lists_launch(p.idx->as<uint32_t>(), p.key->as<float>(), p.tau->as<float>(), p.end(q.m) - p.row0, p.S,
+                                        q.L, p.keep, p.lout, p.mi->as<uint32_t>(), p.mt->as<float>(), s);
+    };
+    // what the float64 step reads: the filter's lists, or ONE merged list per row
+    struct Lists { const uint32_t *idx; const float *tau; int S, L; } lists[2];
+    for (int i = 0; i < 2; ++i) {
+        const L2Part &p = part[i];
+        lists[i] = p.merge ? Lists{p.mi->as<uint32_t>(), p.mt->as<float>(), 1, p.lout} : Lists{p.idx->as<uint32_t>(), p.tau->as<float>(), p.S, q.L};
+    }
+    if (q.cand_mode) {
+        for (L2Part &p : part)
+            if (p.merge) HIP_TRY(merge(p, st));
+        for (int i = 0; i < 2; ++i)
+            if (part[i].gx > 0)
+                HIP_TRY(nabo::refine_cand_launch(q.dX, part[i].row0, part[i].end(q.m), ix->dY, ix->g, lists[i].idx, lists[i].tau,
+                                                 lists[i].S, lists[i].L, ix->xnorm.as<double>(), err_coef, ymax_sqrt, tau_scale,
+                                                 q.k, ix->base, n_valid, q.d_oidx, q.d_odist, q.out_bound, st, metric, P.lkeep));
+        return NABO_OK;
+    }
+    for (int i = 0; i < 2; ++i) {
+        L2Part &p = part[i];
+        if (p.gx == 0) continue;
+        hipStream_t s = st;
+        if (i == 0 && beside) {
+            s = ix->stream2;
+            HIP_TRY(hipStreamWaitEvent(s, ix->ev_main, 0));
+        }
+        if (p.merge) HIP_TRY(merge(p, s));
+        HIP_TRY(nabo::refine_launch(q.dX, p.row0, p.end(q.m), ix->dY, ix->g, lists[i].idx, lists[i].tau, lists[i].S, lists[i].L,
+                                    ix->xnorm.as<double>(), err_coef, ymax_sqrt, tau_scale, q.k, q.drop, ix->base, n_valid, ix->mlistbuf.as<uint32_t>(),
+                                    tail_len(ix), q.d_oidx, q.d_odist, ix->fails.as<uint32_t>(), ix->failcnt.as<unsigned int>(),
+                                    s, metric, 0.0, 0.0f, p.merge ? p.keep : P.lkeep, nullptr, nullptr, fail_seed));
+        if (i == 0 && beside) HIP_TRY(hipEventRecord(ix->ev_ref, s));
+    }
+    if (beside) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ref, 0));
+    return NABO_OK;
+}
+
+// The q.n_fail rows of this batch the pass could not certify (ix->fails) go on as a dense batch through query_impl one
+// link down the pass chain: at pass level `level` (seeds: level 1's per-row thresholds) or, with `wide`, on 64-entry lists.
+// They are gathered into the buffer set `b` of this frame, recorded as pass `code` (pass_rows[slot]), solved and scattered
+// back; q.n_fail becomes the rows that still needed the exact kernels.  The inner call reuses ev[0..5]: phases 0-2 of
+// this one are kept for finish_query.
+static int rerun_failed_rows(nabo_index *ix, Query &q, int level, bool wide, uint8_t code, int slot, nabo_index::RerunBufs &b,
+                             const float *seeds)
+{
+    hipStream_t st = ix->stream;
+    const int64_t nf = q.n_fail;
+    int rc;
+    float ms_first[3] = {0, 0, 0};
+    for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms_first[i], ix->ev[i], ix->ev[i + 1]));
+    if ((rc = b.rows.reserve((size_t)nf * sizeof(uint32_t))) || (rc = b.x.reserve((size_t)nf * ix->g * sizeof(double))) ||
+        (rc = b.idx.reserve((size_t)nf * q.k * sizeof(int64_t))) || (rc = b.dist.reserve((size_t)nf * q.k * sizeof(double))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(b.rows.p, ix->fails.p, (size_t)nf * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if (seeds) {
+        if ((rc = b.seed.reserve((size_t)nf * sizeof(float)))) return rc;
+        HIP_TRY(hipMemcpyAsync(b.seed.p, seeds, (size_t)nf * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(nabo::gather_rows_launch(q.dX, b.rows.as<uint32_t>(), nf, ix->g, b.x.as<double>(), st));
+    if ((rc = note_row_pass(ix, b.rows.as<uint32_t>(), nf, code, q.pass_map))) return rc;      // (synchronises the stream)
+    const int level_saved = ix->pass_level;
+    const float *seed_saved = ix->seed_tau;
+    const std::vector<uint32_t> *map_saved = ix->row_map;
+    ix->pass_level = level;
+    ix->wide_retry = wide;                           // (only ever entered from a frame on 32-entry lists)
+    ix->seed_tau = seeds ? b.seed.as<float>() : nullptr;
+    ix->row_map = &q.pass_map;
+    rc = query_impl(ix, b.x.as<double>(), 1, nf, q.k, q.drop, b.idx.as<int64_t>(), b.dist.as<double>(), 1, false, nullptr);
+    ix->pass_level = level_saved;
+    ix->wide_retry = false;
+    ix->seed_tau = seed_saved;
+    ix->row_map = map_saved;
+    if (rc) return rc;
+    ix->pass_rows[slot] = nf;
+    q.n_fail = (unsigned int)ix->counters[0];
+    HIP_TRY(nabo::scatter_rows_launch(b.idx.as<int64_t>(), b.dist.as<double>(), b.rows.as<uint32_t>(), nf, q.k, q.d_oidx,
+                                      q.d_odist, st));
+    HIP_TRY(hipEventRecord(ix->ev[3], st));          // (ev[0..5] were reused by the inner call)
+    memcpy(ix->ms_keep, ms_first, sizeof(ms_first));
+    ix->ms_keep_valid = true;
+    return NABO_OK;
+}
+
+// Euclidean / cosine: plan_l2 -> pack the targets -> filter -> float64 refine and certificate; the rows the pass could not
+// certify go one link down the pass chain (rerun_failed_rows) or to the exact kernels.
+static int query_l2(nabo_index *ix, Query &q)
+{
+    hipStream_t st = ix->stream;
+    const int g = ix->g;
+    const int64_t m = q.m;
+    int rc;
+    const double *dXp = q.dX;                        // what the filter packs
+    if (ix->metric == NABO_METRIC_COSINE) {
+        if ((rc = ix->xnbuf.reserve((size_t)m * g * sizeof(double)))) return rc;
+        HIP_TRY(nabo::normalise_rows_launch(q.dX, m, g, ix->xnbuf.as<double>(), st));
+        dXp = ix->xnbuf.as<double>();
+    }
+    L2Plan P;
+    if ((rc = plan_l2(ix, m, q.k, q.drop, q.cand_mode, &P))) return rc;
+    if (ix->pass_level == 0 && !ix->wide_retry) {
+        ix->pass_rows[0] = ix->pass_rows[1] = ix->pass_rows[2] = 0;
+        snprintf(ix->kernel, sizeof(ix->kernel), "%s", P.kernel);
+    }
+    if ((rc = ensure_packed(ix, P.use_1 ? 2 : P.use_h ? 1 : 0))) return rc;
+    if (q.top) ix->row_pass.assign((size_t)m, (uint8_t)(P.use_1 ? NABO_PASS_ONE_PRODUCT : NABO_PASS_SECOND));
+    const int64_t rows_main = P.gx_main * P.rows_per_wg;
+    L2Part part[2] = {
+        {P.gx_main, 0, rows_main, P.S, P.tps, &ix->cand_idx, &ix->cand_tau, &ix->cand_key, &ix->cand_mi, &ix->cand_mt, &ix->taupre},
+        {P.gx_tail, rows_main, P.gx_tail * P.rows_per_wg, P.S2, P.tps2, &ix->cand_idx2, &ix->cand_tau2, &ix->cand_key2,
+         &ix->cand_mi2, &ix->cand_mt2, &ix->taupre2}};
+    // Several lists per row (reference splits, the tail round): the l2c kernel also emits the entries' filter keys and
+    // merge_lists_kernel reduces the lists to the ONE a single stream would have kept (refine.hip)
+    // (first pass only: a seeded pass WANTS every list re-evaluated -- its rows have more than one list's worth of
+    // references below their seeds: cosine d = 100, k = 50 with the merge there: 86 instead of 16 ms of later passes)
+    // ... the SEEDED pass keeps up to 128: what lies below a seed is "a few more than one list", and
+    // 128 candidates are two per lane for the float64 step where S x 32 were four to sixteen per lane, each walking
+    // its own row (100k x 100k: refine of 108 rows' 1024 candidates 0.41 ms)
+    const bool seeded_merge = ix->pass_level == 1 && !ix->wide_retry;          // (32- and 64-entry lists alike)
+    const bool merging = P.on_l2c && ix->opt.merge_lists != 0 && !ix->wide_retry && (ix->pass_level == 0 || seeded_merge);
+    const size_t xtile_bytes = P.use_h ? (size_t)P.kcq * 1024 : (size_t)((ix->ksteps + 3) / 4) * 256 * sizeof(float);
+    if ((rc = ix->xpk.reserve((size_t)(P.rows_pad / 32) * xtile_bytes))) return rc;
+    if ((rc = ix->xnorm.reserve((size_t)m * sizeof(double)))) return rc;
+    for (L2Part &p : part) {
+        if (p.gx == 0) continue;
+        p.merge = merging && p.S > 1;
+        p.keep = seeded_merge ? (p.S * q.L < 128 ? p.S * q.L : 128) : P.lkeep;
+        p.lout = seeded_merge ? p.keep : q.L;
+        if ((rc = p.idx->reserve((size_t)p.rows * p.S * q.L * sizeof(uint32_t) + 16))) return rc;
+        if ((rc = p.tau->reserve((size_t)p.rows * p.S * sizeof(float) + 16))) return rc;
+        if (p.merge && ((rc = p.key->reserve((size_t)p.rows * p.S * q.L * sizeof(float))) ||
+                        (rc = p.mi->reserve((size_t)p.rows * p.lout * sizeof(uint32_t))) ||
+                        (rc = p.mt->reserve((size_t)p.rows * sizeof(float)))))
+            return rc;
+    }
+    if ((rc = ix->fails.reserve((size_t)m * sizeof(uint32_t)))) return rc;
+    if ((rc = ix->failcnt.reserve(sizeof(unsigned int)))) return rc;
+    HIP_TRY(hipMemsetAsync(ix->failcnt.p, 0, sizeof(unsigned int), st));
+    if (P.use_h)
+        HIP_TRY(nabo::pack_cquery_launch(dXp, m, g, ix->centre.as<double>(), ix->hscale, P.kcq, P.rows_pad / 32,
+                                         ix->xpk.as<unsigned char>(), ix->xnorm.as<double>(), true, st, nullptr, P.use_1 ? 1 : 3));
+    else
+        HIP_TRY(nabo::pack_query_launch(dXp, m, g, ix->centre.as<double>(), ix->fscale, ix->ksteps, P.rows_pad / 32,
+                                        ix->xpk.as<float>(), ix->xnorm.as<double>(), st));
+    HIP_TRY(hipEventRecord(ix->ev[1], st));
+    // the l2c kernel ran: its failed rows can go through a seeded pass
+    const bool seedable = P.on_l2c && !q.cand_mode && ix->opt.seeded_pass != 0;
+    bool beside = false;
+    if ((rc = l2_filter(ix, q, P, part, (seedable && ix->pass_level == 1) ? ix->seed_tau : nullptr, &beside))) return rc;
+    HIP_TRY(hipEventRecord(ix->ev[2], st));
+    if (nabo::debug_ablate() != 0) {     // experiments builds only: kernel-timing runs, results are garbage
+        for (int i = 3; i <= 5; ++i) HIP_TRY(hipEventRecord(ix->ev[i], st));
+        HIP_TRY(hipStreamSynchronize(st));
+        float tt = 0;
+        HIP_TRY(hipEventElapsedTime(&tt, ix->ev[1], ix->ev[2]));
+        ix->ms[1] = tt;
+        q.timing_only = true;
+        return NABO_OK;
+    }
+    float *fail_seed = nullptr;          // seeds for a seeded pass of the rows that fail (pass 0 on the l2c kernel)
+    if (seedable && ix->pass_level == 0) {
+        if ((rc = ix->failseed.reserve((size_t)m * sizeof(float)))) return rc;
+        fail_seed = ix->failseed.as<float>();
+    }
+    if ((rc = l2_refine(ix, q, P, part, beside, fail_seed))) return rc;
+    HIP_TRY(hipEventRecord(ix->ev[3], st));
+    q.S = P.S;
+    q.n_wg = P.gx_main * P.S + P.gx_tail * P.S2;
+    if (q.cand_mode) {
+        HIP_TRY(hipEventRecord(ix->ev[4], st));
+        return NABO_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(&q.n_fail, ix->failcnt.p, sizeof(q.n_fail), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (P.use_1 && q.n_fail > 0) {
+        // Rows this one-product pass could not certify: from level 0 on the l2c kernel to the SEEDED one-product pass
+        // (level 1: every row starts from the threshold refine.hip derived from its failed certificate), otherwise to
+        // the f16x3 pass (level 2), which sends what IT cannot certify on to the 64-entry lists / the exact kernels.
+        const int here = ix->pass_level, next = (here == 0 && fail_seed) ? 1 : 2;
+        if ((rc = rerun_failed_rows(ix, q, next, false, next == 1 ? NABO_PASS_SEEDED : NABO_PASS_SECOND, next - 1, ix->rerun[here],
+                                    next == 1 ? fail_seed : nullptr)))
+            return rc;
+        if (here == 0 && m >= 1024 && ix->pass_rows[1] > m / 4) ix->coarse_weak = true;
+    } else if (q.n_fail >= 16 && q.epl == 1 && !ix->wide_retry && ix->opt.wide_retry != 0) {
+        // Second chance: rows the 32-entry lists could not certify (ties / near-ties reaching past the kept
+        // entries) go through the same filter once more with 64-entry lists before anything is brute-forced.
+        if ((rc = rerun_failed_rows(ix, q, ix->pass_level, true, NABO_PASS_WIDE, 2, ix->rerun[RERUN_WIDE], nullptr))) return rc;
+    } else if (q.n_fail > 0) {
+        unsigned int d_rows = 0;
+        if ((rc = reserve_exact_ws(ix, q.n_fail, 65535, &d_rows))) return rc;
+        if ((rc = note_row_pass(ix, ix->fails.as<uint32_t>(), q.n_fail, (uint8_t)NABO_PASS_EXACT, q.pass_map))) return rc;
+        HIP_TRY(nabo::exact_rows_launch(q.dX, ix->dY, ix->n, g, ix->metric, ix->f, ix->dmask, ix->fails.as<uint32_t>(), q.n_fail,
+                                        q.k, q.drop, ix->base, ix->mlistbuf.as<uint32_t>(), tail_len(ix), q.d_oidx, q.d_odist,
+                                        ix->exact_d.as<double>(), d_rows, st));
+    }
+    HIP_TRY(hipEventRecord(ix->ev[4], st));
+    return NABO_OK;
+}
+
+// ---- the launch plan of a modified-Canberra query (a pure function of the index's shape and the query's, like plan_l2) ----
+// Splits of the exact kernel (canberra_topk_kernel, gx workgroups of 64 rows): ~1024 workgroups in all, at most one split
+// per 64-reference chunk and 16.
+static int cb_exact_splits(int64_t gx, int64_t n_chunks)
+{
+    if (gx >= 512) return 1;
+    int64_t S = (1024 + gx - 1) / gx;
+    if (S > n_chunks) S = n_chunks;
+    return S > 16 ? 16 : (int)S;
+}
+
+// Time of a counting-pass launch of gx workgroups cut s ways, `slots` resident at once: full-length rounds of workgroups,
+// and ~8 % more bound evaluations per extra split (every list warms up on its own): measured on 100k x 100k, d = 50
+static double cb_split_cost(int64_t gx, int64_t slots, int s)
+{
+    return (double)((gx * s + slots - 1) / slots) / s * (1.0 + 0.08 * (s - 1));
+}
+
+static int cb_best_split(int64_t gx, int64_t slots, int s_max, double *cost)
+{
+    int best_s = 1;
+    double best = 1e30;
+    for (int s = 1; s <= s_max; ++s) {
+        const double c = cb_split_cost(gx, slots, s);
+        if (c < best - 1e-9) { best = c; best_s = s; }
+    }
+    *cost = best;
+    return best_s;
+}
+
+struct CbPlan {
+    int64_t gx_exact = 0;            // exact kernel: workgroups (64 rows each) and reference splits
+    int S_exact = 1;
+    bool bits = false;               // counting pass on bitmaps (canberra_bits.hip), else the SWAR count (canberra_f32.hip)
+    int lists = 1;                   // candidate lists per (row, split): one per wave
+    int Sf = 1, S2 = 1;              // counting pass: reference splits of the main launch / the tail round
+    int64_t rows_main = 0;           // ... target rows of the main launch (the rest: the tail round)
+};
+
+static void plan_canberra(const nabo_index *ix, int64_t m, int epl, CbPlan *C)
+{
+    const int64_t n_chunks = (ix->n + 63) / 64;
+    C->gx_exact = (m + 63) / 64;
+    const int S = ix->opt.splits > 0 ? ix->opt.splits : cb_exact_splits(C->gx_exact, n_chunks);
+    C->S_exact = S > 16 ? 16 : S;
+    // counting-pass geometry: rpw rows per workgroup, every (row, split) ends with `lists` candidate lists.  Splits fill
+    // the chip when there are few rows and trim the last, partially filled round of workgroups when there are many.
+    C->bits = ix->cb_bits && epl == 1;               // (the bitmap kernel is instantiated for 32-entry lists)
+    C->lists = nabo::cbf_lists_per_split();
+    const int rpw = C->bits ? nabo::cbb_rows_per_wg() : nabo::cbf_rows_per_wg(epl);
+    const int64_t gxf = (m + rpw - 1) / rpw;
+    // resident workgroups: SWAR pass -- one-wave workgroups, 2 per SIMD; bitmap pass -- ONE 8-wave workgroup per CU
+    // (its LDS copy of the table rows + eight waves' lists fill the CU's LDS)
+    const int64_t slots = C->bits ? (int64_t)ix->n_cu : (int64_t)ix->n_cu * 8;
+    int s_max = 1024 / (C->lists * 32 * epl);        // refine handles <= 1024 candidates per row
+    if (C->bits) {                                   // splits are ranges of 2048-reference blocks, >= 2 each
+        const int64_t nb2 = ((ix->n + 2047) / 2048) / 2;
+        if (s_max > nb2) s_max = (int)nb2;
+    } else if (s_max > n_chunks / (8 * C->lists)) s_max = (int)(n_chunks / (8 * C->lists));
+    if (s_max < 1) s_max = 1;
+    double cost = 0;
+    int Sf = ix->opt.splits > 0 ? ix->opt.splits : cb_best_split(gxf, slots, s_max, &cost);
+    if (Sf > s_max) Sf = s_max;
+    // "tail round": with many rows the last, partially filled round of workgroups gets its own (larger) split factor so
+    // that it takes a fraction of a round -- same idea as in the Euclidean launch
+    C->S2 = 1;
+    C->rows_main = m;
+    if (ix->opt.splits <= 0 && ix->opt.tail_split != 0 && gxf > slots && gxf % slots != 0 && s_max >= 2) {
+        const int64_t tail = gxf % slots;
+        double best_t = 0;
+        const int best_s = cb_best_split(tail, slots, s_max, &best_t);
+        if (best_s > 1 && (double)(gxf / slots) + best_t < cb_split_cost(gxf, slots, Sf) - 1e-9) {
+            C->rows_main = (gxf - tail) * rpw;
+            C->S2 = best_s;
+            Sf = 1;
+        }
+    }
+    C->Sf = Sf;
+}
+
+// The counting pass -> float64 refine + certificate -> exact re-solve of the uncertified rows.  *done stays false when
+// the targets do not fit fp32: the exact kernel then answers every row.
+static int canberra_filter(nabo_index *ix, Query &q, const CbPlan &C, bool *done)
+{
+    hipStream_t st = ix->stream;
+    const int g = ix->g, gp = ix->cb_gp;
+    const int64_t m = q.m, n_valid = ix->n - ix->n_masked;
+    int rc;
+    float slack, plateau;
+    nabo::cbf_constants(g, &slack, &plateau);
+    if (C.bits) snprintf(ix->kernel, sizeof(ix->kernel), "cbb_filter_kernel<%d> (bit-sliced count on %d-bucket bitmaps + fp32 lower bound)", gp, nabo::cbb_buckets());
+    else snprintf(ix->kernel, sizeof(ix->kernel), "cbf_filter_kernel<%d> (7-bit integer count + fp32 lower bound)", gp);
+    struct { int64_t row0, rows; int SL; DevBuf *idx, *tau; } part[2] = {
+        {0, C.rows_main, C.Sf * C.lists, &ix->cand_idx, &ix->cand_tau},
+        {C.rows_main, m - C.rows_main, C.S2 * C.lists, &ix->cand_idx2, &ix->cand_tau2}};
+    if ((rc = ix->xpk.reserve((size_t)m * gp * 2 * sizeof(float)))) return rc;
+    if ((rc = ix->xh.reserve((size_t)m * gp * 2))) return rc;
+    for (auto &p : part)
+        if (p.rows > 0 && ((rc = p.idx->reserve((size_t)p.rows * p.SL * q.L * sizeof(uint32_t))) ||
+                           (rc = p.tau->reserve((size_t)p.rows * p.SL * sizeof(float) + 16))))
+            return rc;
+    if ((rc = ix->fails.reserve((size_t)m * sizeof(uint32_t)))) return rc;
+    const bool dbg_counts = (nabo::debug_ablate() & 4) != 0;
+    if (dbg_counts) HIP_TRY(hipMemsetAsync(ix->cand_tau.as<float>() + (size_t)C.rows_main * part[0].SL, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(ix->cbflag.p, 0, 4 * sizeof(unsigned int), st));
+    unsigned int *d_failcnt = ix->cbflag.as<unsigned int>() + 1, *d_flag = ix->cbflag.as<unsigned int>();
+    HIP_TRY(nabo::cbf_pack_targets_launch(q.dX, m, g, gp, ix->f, ix->xpk.as<float>(), d_flag, st));
+    if (C.bits) {
+        if ((rc = ix->cbrow.reserve((size_t)m * gp * sizeof(uint16_t)))) return rc;
+        HIP_TRY(nabo::cbb_pack_targets_launch(q.dX, m, g, gp, ix->f, ix->cbedges.as<double>(), ix->cbrow.as<uint16_t>(), st));
+    } else {
+        HIP_TRY(nabo::cbf_pack_targets8_launch(q.dX, m, g, gp, ix->f, ix->cbscale.as<double>(), ix->xh.p, st));
+    }
+    HIP_TRY(hipEventRecord(ix->ev[1], st));
+    for (auto &p : part) {
+        if (p.rows == 0) continue;
+        const float *xq = ix->xpk.as<float>() + (size_t)p.row0 * gp * 2;
+        if (C.bits)
+            HIP_TRY(nabo::cbb_filter_launch(gp, xq, ix->cbrow.as<uint16_t>() + (size_t)p.row0 * gp, p.rows, ix->yrow.as<float>(),
+                                            ix->cbtab.as<uint32_t>(), ix->cbvalid.as<uint32_t>(), ix->n, g, p.SL / C.lists,
+                                            p.idx->as<uint32_t>(), p.tau->as<float>(), st));
+        else
+            HIP_TRY(nabo::cbf_filter_launch(gp, q.epl, xq, ix->xh.as<unsigned char>() + (size_t)p.row0 * gp * 2, p.rows,
+                                            ix->yrow.as<float>(), ix->ych.p, ix->n, g, ix->dmask, p.SL / C.lists,
+                                            p.idx->as<uint32_t>(), p.tau->as<float>(), st));
+    }
+    HIP_TRY(hipEventRecord(ix->ev[2], st));
+    if (dbg_counts) {
+        unsigned int c2[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(c2, ix->cand_tau.as<float>() + (size_t)C.rows_main * part[0].SL, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        fprintf(stderr, "[nabo debug] canberra filter (main launch): splits=%d survivors=%u (%.1f per row) batches=%u\n",
+                C.Sf, c2[0], (double)c2[0] / (double)C.rows_main, c2[1]);
+    }
+    for (auto &p : part)
+        if (p.rows > 0)
+            HIP_TRY(nabo::refine_launch(q.dX, p.row0, p.row0 + p.rows, ix->dY, g, p.idx->as<uint32_t>(), p.tau->as<float>(), p.SL,
+                                        q.L, nullptr, 0.0, 0.0, 1.0, q.k, q.drop, ix->base, n_valid, ix->mlistbuf.as<uint32_t>(),
+                                        tail_len(ix), q.d_oidx, q.d_odist, ix->fails.as<uint32_t>(), d_failcnt, st, 1, ix->f,
+                                        plateau));
+    HIP_TRY(hipEventRecord(ix->ev[3], st));
+    unsigned int hf[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(hf, ix->cbflag.p, sizeof(hf), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hf[0] != 0) return NABO_OK;                  // targets do not fit fp32
+    q.n_fail = hf[1];
+    if (q.top) {
+        ix->row_pass.assign((size_t)m, (uint8_t)NABO_PASS_CANBERRA);
+        if ((rc = note_row_pass(ix, ix->fails.as<uint32_t>(), q.n_fail, (uint8_t)NABO_PASS_EXACT, q.pass_map))) return rc;
+    }
+    if (q.n_fail > 0) {                              // (the buffers of the 64-entry-list rerun: this route has none)
+        const int64_t nf = q.n_fail;
+        const int S3 = cb_exact_splits((nf + 63) / 64, (ix->n + 63) / 64);
+        nabo_index::RerunBufs &b = ix->rerun[RERUN_WIDE];
+        if ((rc = b.x.reserve((size_t)nf * g * sizeof(double))) || (rc = ix->cand_d.reserve((size_t)nf * S3 * q.L * sizeof(double))) ||
+            (rc = ix->cand_idx2.reserve((size_t)nf * S3 * q.L * sizeof(uint32_t))) ||
+            (rc = b.idx.reserve((size_t)nf * q.k * sizeof(int64_t))) || (rc = b.dist.reserve((size_t)nf * q.k * sizeof(double))))
+            return rc;
+        HIP_TRY(nabo::gather_rows_launch(q.dX, ix->fails.as<uint32_t>(), nf, g, b.x.as<double>(), st));
+        HIP_TRY(nabo::canberra_topk_launch(q.epl, b.x.as<double>(), nf, ix->yt.as<double>(), ix->n, g, ix->f, ix->dmask, S3,
+                                           ix->cand_d.as<double>(), ix->cand_idx2.as<uint32_t>(), st));
+        HIP_TRY(nabo::merge_local_launch(ix->cand_d.as<double>(), ix->cand_idx2.as<uint32_t>(), nf, S3 * q.L, q.k, q.drop,
+                                         ix->base, b.idx.as<int64_t>(), b.dist.as<double>(), nullptr, st));
+        HIP_TRY(nabo::scatter_rows_launch(b.idx.as<int64_t>(), b.dist.as<double>(), ix->fails.as<uint32_t>(), nf, q.k,
+                                          q.d_oidx, q.d_odist, st));
+    }
+    HIP_TRY(hipEventRecord(ix->ev[4], st));
+    *done = true;
+    return NABO_OK;
+}
+
+// Modified Canberra: the counting pass where the references have one (canberra_filter), otherwise -- or when too few
+// references are unmasked -- the exact kernel for every row.
+static int query_canberra(nabo_index *ix, Query &q)
+{
+    hipStream_t st = ix->stream;
+    int rc;
+    CbPlan C;
+    plan_canberra(ix, q.m, q.epl, &C);
+    snprintf(ix->kernel, sizeof(ix->kernel), "canberra_topk_kernel (float64)");
+    if (q.top) ix->row_pass.assign((size_t)q.m, (uint8_t)NABO_PASS_EXACT);
+    const int64_t n_valid = ix->n - ix->n_masked;
+    bool done = false;
+    if (ix->cb_f32 && n_valid >= q.kk && (rc = canberra_filter(ix, q, C, &done))) return rc;
+    q.S = done ? C.Sf : C.S_exact;
+    q.n_wg = C.gx_exact * q.S;
+    if (done) return NABO_OK;
+    const int S = C.S_exact;
+    if ((rc = ix->cand_d.reserve((size_t)q.m * S * q.L * sizeof(double))) ||
+        (rc = ix->cand_idx.reserve((size_t)q.m * S * q.L * sizeof(uint32_t))))
+        return rc;
+    HIP_TRY(hipEventRecord(ix->ev[1], st));
+    HIP_TRY(nabo::canberra_topk_launch(q.epl, q.dX, q.m, ix->yt.as<double>(), ix->n, ix->g, ix->f, ix->dmask, S,
+                                       ix->cand_d.as<double>(), ix->cand_idx.as<uint32_t>(), st));
+    HIP_TRY(hipEventRecord(ix->ev[2], st));
+    HIP_TRY(nabo::merge_local_launch(ix->cand_d.as<double>(), ix->cand_idx.as<uint32_t>(), q.m, S * q.L, q.k, q.drop, ix->base,
+                                     q.d_oidx, q.d_odist, nullptr, st));
+    HIP_TRY(hipEventRecord(ix->ev[3], st));
+    if (n_valid < q.kk)
+        HIP_TRY(nabo::masked_tail_launch(q.dX, q.m, ix->dY, ix->g, ix->metric, ix->f, ix->mlistbuf.as<uint32_t>(), tail_len(ix),
+                                         (int)n_valid, q.k, q.drop, ix->base, q.d_oidx, q.d_odist, st));
+    HIP_TRY(hipEventRecord(ix->ev[4], st));
+    return NABO_OK;
+}
+
+// Copy-out, the phases of the query (ev[0..5] -> ms[0..4]) and its counters.  A query that reran rows one level down
+// (rerun_failed_rows) kept its phases 0-2 from before the inner call, whose total stands in for phase 3.
+static int finish_query(nabo_index *ix, const Query &q, int64_t *out_idx, double *out_dist, int32_t out_on_device)
+{
+    hipStream_t st = ix->stream;
+    if (!out_on_device) {
+        const size_t ob = (size_t)q.m * q.k * 8;
+        HIP_TRY(hipMemcpyAsync(out_idx, q.d_oidx, ob, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out_dist, q.d_odist, ob, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipEventRecord(ix->ev[5], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float t = 0;
+    for (int i = 0; i < 4; ++i) {
+        HIP_TRY(hipEventElapsedTime(&t, ix->ev[i], ix->ev[i + 1]));
+        ix->ms[i] = t;
+    }
+    HIP_TRY(hipEventElapsedTime(&t, ix->ev[0], ix->ev[5]));
+    ix->ms[4] = t;
+    if (ix->ms_keep_valid) {
+        ix->ms_keep_valid = false;
+        HIP_TRY(hipEventElapsedTime(&t, ix->ev[3], ix->ev[5]));
+        for (int i = 0; i < 3; ++i) ix->ms[i] = ix->ms_keep[i];
+        ix->ms[3] = ix->ms_inner + t;              // inner pass (its own total) + scatter / copy-out
+        ix->ms[4] = ix->ms[0] + ix->ms[1] + ix->ms[2] + ix->ms[3];
+    }
+    ix->ms_inner = ix->ms[4];
+    ix->counters[0] = q.n_fail; ix->counters[1] = q.S; ix->counters[2] = q.L; ix->counters[3] = q.n_wg;
+    return NABO_OK;
 }
 
 static int query_body(nabo_index *ix, const double *X, int32_t x_on_device, int64_t m, int32_t k, int32_t drop_first,
@@ -1202,698 +1615,32 @@ static int query_body(nabo_index *ix, const double *X, int32_t x_on_device, int6
     int rc = use_device(ix->device);
     if (rc) return rc;
     hipStream_t st = ix->stream;
-    const int g = ix->g;
-    const int64_t n_valid = ix->n - ix->n_masked;
-
+    Query q;
+    q.m = m; q.k = k; q.drop = drop; q.kk = kk;
+    q.epl = ((kk <= 24 && !ix->wide_retry) || cand_mode) ? 1 : 2;
+    q.L = 32 * q.epl;
+    q.cand_mode = cand_mode; q.out_bound = out_bound;
+    q.top = ix->depth == 1 && !cand_mode;
     // operands / results on device
-    const double *dX = X;
+    q.dX = X;
     if (!x_on_device) {
-        const size_t xb = (size_t)m * g * sizeof(double);
+        const size_t xb = (size_t)m * ix->g * sizeof(double);
         if ((rc = ix->xbuf.reserve(xb))) return rc;
         HIP_TRY(hipMemcpyAsync(ix->xbuf.p, X, xb, hipMemcpyHostToDevice, st));
-        dX = ix->xbuf.as<double>();
+        q.dX = ix->xbuf.as<double>();
     }
-    int64_t *d_oidx = out_idx;
-    double *d_odist = out_dist;
-    const size_t ob = (size_t)m * k * 8;
+    q.d_oidx = out_idx;
+    q.d_odist = out_dist;
     if (!out_on_device) {
-        if ((rc = ix->oidx.reserve(ob))) return rc;
-        if ((rc = ix->odist.reserve(ob))) return rc;
-        d_oidx = ix->oidx.as<int64_t>();
-        d_odist = ix->odist.as<double>();
+        const size_t ob = (size_t)m * k * 8;
+        if ((rc = ix->oidx.reserve(ob)) || (rc = ix->odist.reserve(ob))) return rc;
+        q.d_oidx = ix->oidx.as<int64_t>();
+        q.d_odist = ix->odist.as<double>();
     }
-    const int epl = ((kk <= 24 && !ix->wide_retry) || cand_mode) ? 1 : 2;
-    const int L = 32 * epl;
-    unsigned int n_fail = 0;
-    int S = 1;
-    int64_t n_wg = 0;
     HIP_TRY(hipEventRecord(ix->ev[0], st));
-    const bool top = ix->depth == 1 && !cand_mode;   // this call owns the per-row pass record
-    std::vector<uint32_t> pass_map;                  // top-level rows of the batch an inner call works on
-
-    if (exact_route) {
-        if (top) ix->row_pass.assign((size_t)m, (uint8_t)NABO_PASS_EXACT);
-        uint64_t d_rows = (1ull << 30) / ((uint64_t)ix->n * sizeof(double));
-        if (d_rows < 1) d_rows = 1;
-        if (d_rows > (uint64_t)m) d_rows = (uint64_t)m;
-        if (d_rows > 65528) d_rows = 65528;
-        if (m > 0xFFFFFFF0ll) return fail(NABO_E_UNSUPPORTED, "m=%lld: fewer than 2^32-16 rows per call", (long long)m);
-        if ((rc = ix->fails.reserve((size_t)m * sizeof(uint32_t)))) return rc;
-        if ((rc = ix->exact_d.reserve((size_t)d_rows * ix->n * sizeof(double)))) return rc;
-        HIP_TRY(nabo::iota_launch(ix->fails.as<uint32_t>(), m, st));
-        HIP_TRY(hipEventRecord(ix->ev[1], st));
-        HIP_TRY(hipEventRecord(ix->ev[2], st));
-        HIP_TRY(hipEventRecord(ix->ev[3], st));
-        HIP_TRY(nabo::exact_rows_launch(dX, ix->dY, ix->n, g, ix->metric, ix->f, ix->dmask, ix->fails.as<uint32_t>(),
-                                        (unsigned int)m, k, drop, ix->base, ix->mlistbuf.as<uint32_t>(), tail_len(ix),
-                                        d_oidx, d_odist, ix->exact_d.as<double>(), (unsigned int)d_rows, st));
-        HIP_TRY(hipEventRecord(ix->ev[4], st));
-        n_fail = (unsigned int)m;
-        S = 0;
-        snprintf(ix->kernel, sizeof(ix->kernel), "exact_dist_rows_kernel + exact_select_rows_kernel (float64 brute force)");
-    } else if (ix->metric != NABO_METRIC_MOD_CANBERRA) {
-        const bool cosine = ix->metric == NABO_METRIC_COSINE;
-        const double *dXp = dX;                           // what the filter packs
-        if (cosine) {
-            if ((rc = ix->xnbuf.reserve((size_t)m * g * sizeof(double)))) return rc;
-            HIP_TRY(nabo::normalise_rows_launch(dX, m, g, ix->xnbuf.as<double>(), st));
-            dXp = ix->xnbuf.as<double>();
-        }
-        L2Plan P;
-        if ((rc = plan_l2(ix, m, k, drop, cand_mode, &P))) return rc;
-        const bool use_h = P.use_h, use_c = P.use_c, use_1 = P.use_1, on_l2c = P.on_l2c, forced = P.forced;
-        const int geo = P.geo, kcq = P.kcq, slack1 = P.slack1, lkeep = P.lkeep, rows_per_wg = P.rows_per_wg, S2 = P.S2;
-        const int epl_launch = P.r1 ? -1 : epl;
-        const int64_t gx_main = P.gx_main, gx_tail = P.gx_tail, rows_pad = P.rows_pad, tps = P.tps, tps2 = P.tps2;
-        const int Q = (ix->ksteps + 3) / 4;
-        S = P.S;
-        (void)forced; (void)slack1;
-        if (ix->pass_level == 0 && !ix->wide_retry) {
-            ix->pass_rows[0] = ix->pass_rows[1] = ix->pass_rows[2] = 0;
-            snprintf(ix->kernel, sizeof(ix->kernel), "%s", P.kernel);
-        }
-        if ((rc = ensure_packed(ix, use_1 ? 2 : use_h ? 1 : 0))) return rc;
-        if (top) ix->row_pass.assign((size_t)m, (uint8_t)(use_1 ? NABO_PASS_ONE_PRODUCT : NABO_PASS_SECOND));
-        const int64_t rows_main = gx_main * rows_per_wg, rows_tail = gx_tail * rows_per_wg;
-        const size_t xtile_bytes = use_h ? (size_t)kcq * 1024 : (size_t)Q * 256 * sizeof(float);
-        if ((rc = ix->xpk.reserve((size_t)(rows_pad / 32) * xtile_bytes))) return rc;
-        if ((rc = ix->xnorm.reserve((size_t)m * sizeof(double)))) return rc;
-        if ((rc = ix->cand_idx.reserve((size_t)rows_main * S * L * sizeof(uint32_t) + 16))) return rc;
-        if ((rc = ix->cand_tau.reserve((size_t)rows_main * S * sizeof(float) + 16))) return rc;
-        if (gx_tail > 0) {
-            if ((rc = ix->cand_idx2.reserve((size_t)rows_tail * S2 * L * sizeof(uint32_t)))) return rc;
-            if ((rc = ix->cand_tau2.reserve((size_t)rows_tail * S2 * sizeof(float)))) return rc;
-        }
-        if ((rc = ix->fails.reserve((size_t)m * sizeof(uint32_t)))) return rc;
-        if ((rc = ix->failcnt.reserve(sizeof(unsigned int)))) return rc;
-        HIP_TRY(hipMemsetAsync(ix->failcnt.p, 0, sizeof(unsigned int), st));
-        // locality order (order.hip): the l2q kernel streams key-ordered references; the targets are packed in key order
-        // too and every wave starts its stream at its rows' neighbourhood
-        const bool ordered = use_h && !use_c && ix->q16 && ix->ref_ordered;
-        const bool t_ordered = use_h && !use_c && ix->q16 && (ix->order_flags & 2) != 0;
-        const uint32_t *rperm = nullptr, *tperm = nullptr;
-        const int32_t *wstart = nullptr;
-#ifdef NABO_EXPERIMENTS
-        if (ordered) rperm = ix->rperm.as<uint32_t>();
-        if (t_ordered) {
-            if ((rc = order_rows(ix, dXp, m, ix->tkeys, ix->tperm))) return rc;
-            tperm = ix->tperm.as<uint32_t>();
-        }
-        if (ordered && t_ordered && (ix->order_flags & 4) != 0) {
-            const int64_t n_waves = rows_pad / 128;
-            if ((rc = ix->wstart.reserve((size_t)n_waves * 4))) return rc;
-            HIP_TRY(nabo::wave_start_launch(ix->tkeys.as<uint32_t>(), m, 128, ix->rkeys.as<uint32_t>(), ix->n, n_waves,
-                                            ix->wstart.as<int32_t>(), st));
-            wstart = ix->wstart.as<int32_t>();
-        }
-#else
-        (void)ordered; (void)t_ordered;
-#endif
-        if (use_h)
-            HIP_TRY(nabo::pack_cquery_launch(dXp, m, g, ix->centre.as<double>(), ix->hscale, kcq, rows_pad / 32,
-                                             ix->xpk.as<unsigned char>(), ix->xnorm.as<double>(), ix->q16, st, tperm,
-                                             use_1 ? 1 : 3));
-        else
-            HIP_TRY(nabo::pack_query_launch(dXp, m, g, ix->centre.as<double>(), ix->fscale, ix->ksteps, rows_pad / 32,
-                                            ix->xpk.as<float>(), ix->xnorm.as<double>(), st));
-        HIP_TRY(hipEventRecord(ix->ev[1], st));
-        bool seedable = false;               // the l2c kernel ran: its failed rows can go through a seeded pass
-        bool refine_beside_tail = false;
-        bool merge_main = false, merge_tail = false;
-        int merge_keep = 0, merge_L = 0, keep_tail = 0;
-        bool merge_seeded = false;
-        int64_t pieces_wgs = 0;
-        float *key_main = nullptr, *key_tail = nullptr;
-#ifdef NABO_EXPERIMENTS
-        if (use_c) {
-            if (gx_main > 0)
-                HIP_TRY(nabo::l2s_topk_launch(ix->kc, ix->xpk.as<unsigned char>(), ix->ycpk.as<unsigned char>(), (int)tps, S,
-                                              (int)gx_main, 0, lkeep, ix->cand_idx.as<uint32_t>(), nullptr,
-                                              ix->cand_tau.as<float>(), st));
-            if (gx_tail > 0)
-                HIP_TRY(nabo::l2s_topk_launch(ix->kc, ix->xpk.as<unsigned char>(), ix->ycpk.as<unsigned char>(), (int)tps2, S2,
-                                              (int)gx_tail, rows_main / 32, lkeep, ix->cand_idx2.as<uint32_t>(), nullptr,
-                                              ix->cand_tau2.as<float>(), st));
-        } else
-#endif
-        if (use_h && ix->q16) {
-            const unsigned char *ytiles = use_1 ? ix->ycpk1.as<unsigned char>() : ix->ycpk.as<unsigned char>();
-            // the l2q kernel on the one-product operands: A/B runs, and the locality-ordered stream (its home pre-pass)
-            const bool coarse_on_q = !on_l2c;
-            seedable = use_1 && !coarse_on_q && !cand_mode && ix->opt.seeded_pass != 0;
-            const float *seeds = (seedable && ix->pass_level == 1) ? ix->seed_tau : nullptr;
-            // Several lists per row (reference splits, pieces, the tail round): the l2c kernel also emits the entries' filter
-            // keys and merge_lists_kernel reduces the lists to the ONE a single stream would have kept (refine.hip)
-            // (first pass only: a seeded pass WANTS every list re-evaluated -- its rows have more than one list's worth of
-            // references below their seeds: cosine d = 100, k = 50 with the merge there: 86 instead of 16 ms of later passes)
-            // ... the SEEDED pass keeps up to 128: what lies below a seed is "a few more than one list", and
-            // 128 candidates are two per lane for the float64 step where S x 32 were four to sixteen per lane, each walking
-            // its own row (100k x 100k: refine of 108 rows' 1024 candidates 0.41 ms)
-            const bool seeded_merge = ix->pass_level == 1 && !ix->wide_retry;          // (32- and 64-entry lists alike)
-            const bool merging = on_l2c && ix->opt.merge_lists != 0 && !ix->wide_retry && (ix->pass_level == 0 || seeded_merge);
-            merge_seeded = seeded_merge;
-            merge_keep = seeded_merge ? (S * L < 128 ? S * L : 128) : lkeep;
-            merge_L = seeded_merge ? merge_keep : L;
-            merge_main = merging && S > 1 && gx_main > 0;
-            merge_tail = merging && S2 > 1 && gx_tail > 0;
-            if (merge_main) {
-                if ((rc = ix->cand_key.reserve((size_t)rows_main * S * L * sizeof(float)))) return rc;
-                if ((rc = ix->cand_mi.reserve((size_t)rows_main * merge_L * sizeof(uint32_t)))) return rc;
-                if ((rc = ix->cand_mt.reserve((size_t)rows_main * sizeof(float)))) return rc;
-                key_main = ix->cand_key.as<float>();
-            }
-            if (merge_tail) {
-                if ((rc = ix->cand_key2.reserve((size_t)rows_tail * S2 * L * sizeof(float)))) return rc;
-                if ((rc = ix->cand_mi2.reserve((size_t)rows_tail * (merge_seeded ? 128 : merge_L) * sizeof(uint32_t)))) return rc;
-                if ((rc = ix->cand_mt2.reserve((size_t)rows_tail * sizeof(float)))) return rc;
-                key_tail = ix->cand_key2.as<float>();
-            }
-            if (use_1 && !coarse_on_q && P.pieces) {
-                // A launch cut into pieces (cut_pieces): the tables go to the device, unused list slots read as empty lists
-                // with threshold +inf, every piece's tournament looks at its own first tiles.
-                std::vector<int> pcs_h, first_h, count_h;
-                int n_wg = 0;
-                int64_t plen = 0;
-                const int sp = cut_pieces(gx_main, ix->ref_tiles, (int64_t)ix->n_cu * P.wg_per_cu, PIECE_MIN_TILES, 1024 / L, &pcs_h, &first_h, &count_h, &n_wg, &plen);
-                if (sp != S) return fail(NABO_E_INVALID, "internal: piece plan changed between planning and launch");
-                std::vector<int> ranges_h((size_t)gx_main * S * 4, 0);
-                const int pre_pct = ix->opt.prepass;
-                bool any_pre = false;
-                for (size_t i = 0; i + 3 < pcs_h.size(); i += 4) {
-                    int pt = 0, gt = 2;
-                    if (pre_pct > 0) nabo::l2c_pre_plan(kcq, lkeep, pcs_h[i + 3] - pcs_h[i + 2], pre_pct, &pt, &gt);
-                    int *r = &ranges_h[((size_t)pcs_h[i] * S + pcs_h[i + 1]) * 4];
-                    r[0] = pcs_h[i + 2]; r[1] = pcs_h[i + 3]; r[2] = pt; r[3] = gt;
-                    any_pre = any_pre || pt > 0;
-                }
-                // one workgroup per piece, longest first (the slots that finish a short piece pick up the next one)
-                std::vector<int> order(pcs_h.size() / 4);
-                for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-                std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-                    return pcs_h[4 * a + 3] - pcs_h[4 * a + 2] > pcs_h[4 * b + 3] - pcs_h[4 * b + 2];
-                });
-                std::vector<int> &img = ix->piece_host;        // (alive until the query's last synchronisation)
-                img.clear();
-                for (int i : order) img.insert(img.end(), pcs_h.begin() + 4 * i, pcs_h.begin() + 4 * i + 4);
-                const size_t off_ranges = img.size();
-                img.insert(img.end(), ranges_h.begin(), ranges_h.end());
-                if ((rc = ix->piecebuf.reserve(img.size() * sizeof(int)))) return rc;
-                HIP_TRY(hipMemcpyAsync(ix->piecebuf.p, img.data(), img.size() * sizeof(int), hipMemcpyHostToDevice, st));
-                L2cPieces pcs;
-                pcs.pieces = ix->piecebuf.as<int>();
-                pcs.n_pieces = (int)order.size();
-                pieces_wgs = pcs.n_pieces;
-                pcs.ranges = ix->piecebuf.as<int>() + off_ranges;
-                pcs.rows_per_col = rows_per_wg;
-                HIP_TRY(hipMemsetAsync(ix->cand_idx.p, 0xFF, (size_t)rows_main * S * L * sizeof(uint32_t), st));
-                HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ix->cand_tau.p), 0x7F800000, (size_t)rows_main * S, st));
-                const float *seeds_main = nullptr;
-                int stride_main = 0;
-                if (ix->pass_level == 0 && !ix->wide_retry) ix->pre_tiles_last = 0;
-                if (any_pre) {
-                    if ((rc = ix->taupre.reserve((size_t)rows_main * S * sizeof(float)))) return rc;
-                    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ix->taupre.p), 0x7F800000, (size_t)rows_main * S, st));
-                    HIP_TRY(nabo::l2c_pre_launch(kcq, lkeep, ix->xpk.as<unsigned char>(), ytiles, (int)tps, S, rows_main, 0, 0, 2,
-                                                 ix->ref_tiles_alloc - 1, st, m, ix->taupre.as<float>(), pcs.ranges, rows_per_wg));
-                    seeds_main = ix->taupre.as<float>();
-                    stride_main = S;
-                    if (ix->pass_level == 0 && !ix->wide_retry) ix->pre_tiles_last = ranges_h[2];
-                }
-                HIP_TRY(nabo::l2c_topk_launch(kcq, geo, ix->xpk.as<unsigned char>(), ytiles, (int)tps, S, (int)gx_main, 0, lkeep,
-                                              ix->cand_idx.as<uint32_t>(), key_main, ix->cand_tau.as<float>(),
-                                              ix->ref_tiles_alloc - 1, st, m, seeds_main, stride_main, 0, &pcs));
-            } else if (use_1 && !coarse_on_q) {
-                // Tournament seeds (l2c_topk.hip: l2c_pre_kernel): every (row, split) list starts from an upper bound of its
-                // lkeep-th smallest score among the split's first references instead of +inf -- not for a pass that has its
-                // seeds already.  NABO_PREPASS: 0 off, otherwise percent of the planned length (A/B runs; same bits always).
-                const int pre_pct = seeds ? 0 : ix->opt.prepass;
-                const float *seeds_main = seeds, *seeds_tail = seeds;
-                int stride_main = 0, stride_tail = 0;
-                if (ix->pass_level == 0 && !ix->wide_retry) ix->pre_tiles_last = 0;
-                if (pre_pct > 0) {
-                    int pt = 0, gt = 2;
-                    nabo::l2c_pre_plan(kcq, lkeep, (int)tps, pre_pct, &pt, &gt);
-                    if (pt > 0 && gx_main > 0) {
-                        if ((rc = ix->taupre.reserve((size_t)rows_main * S * sizeof(float)))) return rc;
-                        HIP_TRY(nabo::l2c_pre_launch(kcq, lkeep, ix->xpk.as<unsigned char>(), ytiles, (int)tps, S, rows_main, 0, pt, gt,
-                                                     ix->ref_tiles_alloc - 1, st, m, ix->taupre.as<float>()));
-                        seeds_main = ix->taupre.as<float>();
-                        stride_main = S;
-                        if (ix->pass_level == 0 && !ix->wide_retry) ix->pre_tiles_last = pt;
-                    }
-                    nabo::l2c_pre_plan(kcq, lkeep, (int)tps2, pre_pct, &pt, &gt);
-                    if (pt > 0 && gx_tail > 0) {
-                        if ((rc = ix->taupre2.reserve((size_t)rows_tail * S2 * sizeof(float)))) return rc;
-                        HIP_TRY(nabo::l2c_pre_launch(kcq, lkeep, ix->xpk.as<unsigned char>(), ytiles, (int)tps2, S2, rows_tail,
-                                                     rows_main / 32, pt, gt, ix->ref_tiles_alloc - 1, st, m, ix->taupre2.as<float>()));
-                        seeds_tail = ix->taupre2.as<float>();
-                        stride_tail = S2;
-                    }
-                }
-                if (gx_main > 0)
-                    HIP_TRY(nabo::l2c_topk_launch(kcq, geo, ix->xpk.as<unsigned char>(), ytiles, (int)tps, S, (int)gx_main, 0, lkeep,
-                                                  ix->cand_idx.as<uint32_t>(), key_main, ix->cand_tau.as<float>(),
-                                                  ix->ref_tiles_alloc - 1, st, m, seeds_main, stride_main, 0));
-                // the tail launch (a fraction of a round, reference splits) leaves most CUs idle: the refine of the main
-                // launch's rows (an HBM gather) runs beside it on the second stream
-                if (gx_main > 0 && gx_tail > 0 && !cand_mode && ix->opt.refine_overlap != 0) {
-                    HIP_TRY(hipEventRecord(ix->ev_main, st));
-                    refine_beside_tail = true;
-                }
-                if (gx_tail > 0)
-                    HIP_TRY(nabo::l2c_topk_launch(kcq, geo, ix->xpk.as<unsigned char>(), ytiles, (int)tps2, S2, (int)gx_tail,
-                                                  rows_main / 32, lkeep, ix->cand_idx2.as<uint32_t>(), key_tail,
-                                                  ix->cand_tau2.as<float>(), ix->ref_tiles_alloc - 1, st, m, seeds_tail, stride_tail,
-                                                  rows_main));
-            } else {
-            if (gx_main > 0)
-                HIP_TRY(nabo::l2q_topk_launch(kcq, ix->xpk.as<unsigned char>(), ytiles,
-                                              (int)tps, S, (int)gx_main, 0, lkeep, ix->cand_idx.as<uint32_t>(), nullptr,
-                                              ix->cand_tau.as<float>(), ix->ref_tiles_alloc - 1, st, wstart));
-            if (gx_tail > 0)
-                HIP_TRY(nabo::l2q_topk_launch(kcq, ix->xpk.as<unsigned char>(), ytiles,
-                                              (int)tps2, S2, (int)gx_tail, rows_main / 32, lkeep,
-                                              ix->cand_idx2.as<uint32_t>(), nullptr, ix->cand_tau2.as<float>(),
-                                              ix->ref_tiles_alloc - 1, st, wstart));
-            }
-#ifdef NABO_EXPERIMENTS
-        } else if (use_h) {
-            const unsigned char *ytiles = use_1 ? ix->ycpk1.as<unsigned char>() : ix->ycpk.as<unsigned char>();
-            if (gx_main > 0)
-                HIP_TRY(nabo::l2h_topk_launch(kcq, ix->xpk.as<unsigned char>(), ytiles,
-                                              (int)tps, S, (int)gx_main, 0, lkeep, ix->cand_idx.as<uint32_t>(), nullptr,
-                                              ix->cand_tau.as<float>(), ix->ref_tiles_alloc - 1, st));
-            if (gx_tail > 0)
-                HIP_TRY(nabo::l2h_topk_launch(kcq, ix->xpk.as<unsigned char>(), ytiles,
-                                              (int)tps2, S2, (int)gx_tail, rows_main / 32, lkeep,
-                                              ix->cand_idx2.as<uint32_t>(), nullptr, ix->cand_tau2.as<float>(),
-                                              ix->ref_tiles_alloc - 1, st));
-#endif
-        } else {
-            if (gx_main > 0)
-                HIP_TRY(nabo::l2_topk_launch(ix->ksteps, epl_launch, ix->xpk.as<float>(), ix->ypk.as<float>(), (int)tps, S,
-                                             (int)gx_main, 0, lkeep, ix->cand_idx.as<uint32_t>(), nullptr,
-                                             ix->cand_tau.as<float>(), st));
-            if (gx_tail > 0)
-                HIP_TRY(nabo::l2_topk_launch(ix->ksteps, epl_launch, ix->xpk.as<float>(), ix->ypk.as<float>(), (int)tps2, S2,
-                                             (int)gx_tail, rows_main / 32, lkeep, ix->cand_idx2.as<uint32_t>(), nullptr,
-                                             ix->cand_tau2.as<float>(), st));
-        }
-        HIP_TRY(hipEventRecord(ix->ev[2], st));
-        if (nabo::debug_ablate() != 0) {     // -DNABO_EXPERIMENTS builds only: kernel-timing runs, results are garbage
-            HIP_TRY(hipEventRecord(ix->ev[3], st));
-            HIP_TRY(hipEventRecord(ix->ev[4], st));
-            HIP_TRY(hipEventRecord(ix->ev[5], st));
-            HIP_TRY(hipStreamSynchronize(st));
-            float tt = 0;
-            HIP_TRY(hipEventElapsedTime(&tt, ix->ev[1], ix->ev[2]));
-            ix->ms[1] = tt;
-            return NABO_OK;
-        }
-        // rounding-error coefficient of the filter score, relative to (||x|| + max||y||)^2
-        // (f16x3: one fp32 accumulation per product term, 16 per step, plus the dropped lo*lo term and the
-        // representation error of the hi + lo split)
-        // (one-product pass: the hi x lo, lo x hi and lo x lo terms are INSIDE its score -- the error slot of
-        // pack_ctiles_kernel<.,.,1> -- so the same accumulation / representation coefficient applies to its kc1 steps)
-        const double err_coef = use_h ? 1.05 * ((16.0 * kcq + 8.0) * std::ldexp(1.0, -24) + std::ldexp(1.0, -20) + std::ldexp(1.0, -21))
-                                      : 1.05 * (2.0 * ix->ksteps + 4.0) * std::ldexp(1.0, -24);
-        const double tau_scale = use_h ? 1.0 / (ix->hscale * ix->hscale) : 1.0 / (ix->fscale * ix->fscale);
-        const double ymax_sqrt = use_h ? ix->ymax_sqrt_c : ix->ymax_sqrt;
-        const int64_t m_main = rows_main < m ? rows_main : m;
-        // what the float64 re-evaluation reads: the filter's lists, or ONE merged list per row (merge_lists_kernel)
-        const uint32_t *ci_main = ix->cand_idx.as<uint32_t>(), *ci_tail = ix->cand_idx2.as<uint32_t>();
-        const float *ct_main = ix->cand_tau.as<float>(), *ct_tail = ix->cand_tau2.as<float>();
-        int S_main = S, S_tail = S2, L_main = L, L_tail = L;
-        auto merge_lists = [&](bool tail, hipStream_t sm) -> hipError_t {
-            if (tail) {
-                const int keep_t = merge_seeded ? (S2 * L < 128 ? S2 * L : 128) : merge_keep, lout_t = merge_seeded ? keep_t : merge_L;
-                hipError_t e = nabo::merge_lists_launch(ix->cand_idx2.as<uint32_t>(), key_tail, ix->cand_tau2.as<float>(), m - rows_main, S2, L,
-                                                        keep_t, lout_t, ix->cand_mi2.as<uint32_t>(), ix->cand_mt2.as<float>(), sm);
-                ci_tail = ix->cand_mi2.as<uint32_t>(); ct_tail = ix->cand_mt2.as<float>(); S_tail = 1; L_tail = lout_t; keep_tail = keep_t;
-                return e;
-            }
-            hipError_t e = nabo::merge_lists_launch(ix->cand_idx.as<uint32_t>(), key_main, ix->cand_tau.as<float>(), m_main, S, L, merge_keep,
-                                                    merge_L, ix->cand_mi.as<uint32_t>(), ix->cand_mt.as<float>(), sm);
-            ci_main = ix->cand_mi.as<uint32_t>(); ct_main = ix->cand_mt.as<float>(); S_main = 1; L_main = merge_L;
-            return e;
-        };
-        if (cand_mode) {
-            if (merge_main) HIP_TRY(merge_lists(false, st));
-            if (merge_tail) HIP_TRY(merge_lists(true, st));
-            HIP_TRY(nabo::refine_cand_launch(dX, 0, m_main, ix->dY, g, ci_main, ct_main,
-                                             S_main, L_main, ix->xnorm.as<double>(), err_coef, ymax_sqrt, tau_scale, k, ix->base,
-                                             n_valid, d_oidx, d_odist, out_bound, st, cosine ? 2 : 0, lkeep, rperm, tperm));
-            if (gx_tail > 0)
-                HIP_TRY(nabo::refine_cand_launch(dX, rows_main, m, ix->dY, g, ci_tail,
-                                                 ct_tail, S_tail, L_tail, ix->xnorm.as<double>(), err_coef,
-                                                 ymax_sqrt, tau_scale, k, ix->base, n_valid, d_oidx, d_odist, out_bound, st,
-                                                 cosine ? 2 : 0, lkeep, rperm, tperm));
-            HIP_TRY(hipEventRecord(ix->ev[3], st));
-            HIP_TRY(hipEventRecord(ix->ev[4], st));
-            HIP_TRY(hipEventRecord(ix->ev[5], st));
-            HIP_TRY(hipStreamSynchronize(st));
-            float tt = 0;
-            for (int i = 0; i < 4; ++i) {
-                HIP_TRY(hipEventElapsedTime(&tt, ix->ev[i], ix->ev[i + 1]));
-                ix->ms[i] = tt;
-            }
-            HIP_TRY(hipEventElapsedTime(&tt, ix->ev[0], ix->ev[5]));
-            ix->ms[4] = tt;
-            ix->counters[0] = 0;
-            ix->counters[1] = S;
-            ix->counters[2] = L;
-            ix->counters[3] = gx_main * S + gx_tail * S2;
-            return NABO_OK;
-        }
-        float *fail_seed = nullptr;          // seeds for a seeded pass of the rows that fail (pass 0 on the l2c kernel)
-        if (seedable && ix->pass_level == 0) {
-            if ((rc = ix->failseed.reserve((size_t)m * sizeof(float)))) return rc;
-            fail_seed = ix->failseed.as<float>();
-        }
-        hipStream_t st_main = st;
-        if (refine_beside_tail) {
-            st_main = ix->stream2;
-            HIP_TRY(hipStreamWaitEvent(st_main, ix->ev_main, 0));
-        }
-        if (merge_main) HIP_TRY(merge_lists(false, st_main));
-        HIP_TRY(nabo::refine_launch(dX, 0, m_main, ix->dY, g, ci_main, ct_main, S_main, L_main,
-                                    ix->xnorm.as<double>(), err_coef, ymax_sqrt, tau_scale, k, drop, ix->base, n_valid,
-                                    ix->mlistbuf.as<uint32_t>(), tail_len(ix), d_oidx, d_odist,
-                                    ix->fails.as<uint32_t>(), ix->failcnt.as<unsigned int>(), st_main, cosine ? 2 : 0, 0.0, 0.0f,
-                                    merge_main ? merge_keep : lkeep, rperm, tperm, fail_seed));
-        if (refine_beside_tail) HIP_TRY(hipEventRecord(ix->ev_ref, st_main));
-        if (merge_tail) HIP_TRY(merge_lists(true, st));
-        if (gx_tail > 0)
-            HIP_TRY(nabo::refine_launch(dX, rows_main, m, ix->dY, g, ci_tail,
-                                        ct_tail, S_tail, L_tail, ix->xnorm.as<double>(), err_coef,
-                                        ymax_sqrt, tau_scale, k, drop, ix->base, n_valid, ix->mlistbuf.as<uint32_t>(),
-                                        tail_len(ix), d_oidx, d_odist, ix->fails.as<uint32_t>(),
-                                        ix->failcnt.as<unsigned int>(), st, cosine ? 2 : 0, 0.0, 0.0f, merge_tail ? keep_tail : lkeep, rperm, tperm,
-                                        fail_seed));
-        if (refine_beside_tail) HIP_TRY(hipStreamWaitEvent(st, ix->ev_ref, 0));
-        HIP_TRY(hipEventRecord(ix->ev[3], st));
-        HIP_TRY(hipMemcpyAsync(&n_fail, ix->failcnt.p, sizeof(n_fail), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        float ms_first[3] = {0, 0, 0};
-        bool retried = false;
-        if (use_1 && n_fail > 0) {
-            // Rows this one-product pass could not certify go on as a dense batch through this very function at the next
-            // level: from level 0 on the l2c kernel to the SEEDED one-product pass (level 1: every row starts from the
-            // threshold refine.hip derived from its failed certificate), otherwise to the f16x3 pass (level 2), which
-            // sends what IT cannot certify on to the 64-entry lists / the exact kernels.
-            for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms_first[i], ix->ev[i], ix->ev[i + 1]));
-            const int64_t nf = n_fail;
-            const int here = ix->pass_level;
-            const int next = (here == 0 && fail_seed) ? 1 : 2;
-            const int b = here;                              // buffer set of this frame (levels 0 and 1 recurse from here)
-            if ((rc = ix->failsp[b].reserve((size_t)nf * sizeof(uint32_t)))) return rc;
-            if ((rc = ix->xfailp[b].reserve((size_t)nf * g * sizeof(double)))) return rc;
-            if ((rc = ix->tmpip[b].reserve((size_t)nf * k * sizeof(int64_t)))) return rc;
-            if ((rc = ix->tmpdp[b].reserve((size_t)nf * k * sizeof(double)))) return rc;
-            HIP_TRY(hipMemcpyAsync(ix->failsp[b].p, ix->fails.p, (size_t)nf * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-            if (next == 1) {
-                if ((rc = ix->seedp[b].reserve((size_t)nf * sizeof(float)))) return rc;
-                HIP_TRY(hipMemcpyAsync(ix->seedp[b].p, fail_seed, (size_t)nf * sizeof(float), hipMemcpyDeviceToDevice, st));
-            }
-            HIP_TRY(nabo::gather_rows_launch(dX, ix->failsp[b].as<uint32_t>(), nf, g, ix->xfailp[b].as<double>(), st));
-            if ((rc = note_row_pass(ix, ix->failsp[b].as<uint32_t>(), nf, (uint8_t)(next == 1 ? NABO_PASS_SEEDED : NABO_PASS_SECOND), pass_map)))
-                return rc;                                   // (synchronises the stream)
-            const float *seed_saved = ix->seed_tau;
-            const std::vector<uint32_t> *map_saved = ix->row_map;
-            ix->pass_level = next;
-            ix->seed_tau = next == 1 ? ix->seedp[b].as<float>() : nullptr;
-            ix->row_map = &pass_map;
-            rc = query_impl(ix, ix->xfailp[b].as<double>(), 1, nf, k, drop_first, ix->tmpip[b].as<int64_t>(),
-                            ix->tmpdp[b].as<double>(), 1, false, nullptr);
-            ix->pass_level = here;
-            ix->seed_tau = seed_saved;
-            ix->row_map = map_saved;
-            if (rc) return rc;
-            ix->pass_rows[next - 1] = nf;
-            if (here == 0 && m >= 1024 && ix->pass_rows[1] > m / 4) ix->coarse_weak = true;
-            n_fail = (unsigned int)ix->counters[0];          // rows that still needed the exact kernels
-            HIP_TRY(nabo::scatter_rows_launch(ix->tmpip[b].as<int64_t>(), ix->tmpdp[b].as<double>(), ix->failsp[b].as<uint32_t>(),
-                                              nf, k, d_oidx, d_odist, st));
-            HIP_TRY(hipEventRecord(ix->ev[3], st));          // (ev[0..5] were reused by the inner call)
-            retried = true;
-        } else if (n_fail >= 16 && epl == 1 && !ix->wide_retry && ix->opt.wide_retry != 0) {
-            // Second chance: rows the 32-entry lists could not certify (ties / near-ties reaching past the kept
-            // entries) go through the same filter once more with 64-entry lists before anything is brute-forced.
-            // The flagged rows are gathered into a dense batch; this very function solves it (wide_retry) and
-            // sends what is STILL uncertified to the exact kernels; the answers are scattered back.
-            for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms_first[i], ix->ev[i], ix->ev[i + 1]));
-            const int64_t nf = n_fail;
-            if ((rc = ix->fails2.reserve((size_t)nf * sizeof(uint32_t)))) return rc;
-            if ((rc = ix->xfail.reserve((size_t)nf * g * sizeof(double)))) return rc;
-            if ((rc = ix->tmpi.reserve((size_t)nf * k * sizeof(int64_t)))) return rc;
-            if ((rc = ix->tmpd.reserve((size_t)nf * k * sizeof(double)))) return rc;
-            HIP_TRY(hipMemcpyAsync(ix->fails2.p, ix->fails.p, (size_t)nf * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-            HIP_TRY(nabo::gather_rows_launch(dX, ix->fails2.as<uint32_t>(), nf, g, ix->xfail.as<double>(), st));
-            if ((rc = note_row_pass(ix, ix->fails2.as<uint32_t>(), nf, (uint8_t)NABO_PASS_WIDE, pass_map))) return rc;      // (synchronises)
-            const std::vector<uint32_t> *map_saved = ix->row_map;
-            ix->wide_retry = true;
-            ix->row_map = &pass_map;
-            rc = query_impl(ix, ix->xfail.as<double>(), 1, nf, k, drop_first, ix->tmpi.as<int64_t>(), ix->tmpd.as<double>(), 1,
-                            false, nullptr);
-            ix->wide_retry = false;
-            ix->row_map = map_saved;
-            if (rc) return rc;
-            ix->pass_rows[2] = nf;
-            n_fail = (unsigned int)ix->counters[0];          // rows that still needed the exact kernels
-            HIP_TRY(nabo::scatter_rows_launch(ix->tmpi.as<int64_t>(), ix->tmpd.as<double>(), ix->fails2.as<uint32_t>(), nf, k,
-                                              d_oidx, d_odist, st));
-            HIP_TRY(hipEventRecord(ix->ev[3], st));          // (ev[0..5] were reused by the inner call)
-            retried = true;
-        } else if (n_fail > 0) {
-            // workspace for the exact distances of the flagged rows: up to ~1 GiB, at least one row
-            uint64_t d_rows = (1ull << 30) / ((uint64_t)ix->n * sizeof(double));
-            if (d_rows < 1) d_rows = 1;
-            if (d_rows > n_fail) d_rows = n_fail;
-            if (d_rows > 65535) d_rows = 65535;
-            if ((rc = ix->exact_d.reserve((size_t)d_rows * ix->n * sizeof(double)))) return rc;
-            if ((rc = note_row_pass(ix, ix->fails.as<uint32_t>(), n_fail, (uint8_t)NABO_PASS_EXACT, pass_map))) return rc;
-            HIP_TRY(nabo::exact_rows_launch(dX, ix->dY, ix->n, g, ix->metric, ix->f, ix->dmask, ix->fails.as<uint32_t>(),
-                                            n_fail, k, drop, ix->base, ix->mlistbuf.as<uint32_t>(), tail_len(ix),
-                                            d_oidx, d_odist, ix->exact_d.as<double>(), (unsigned int)d_rows, st));
-        }
-        HIP_TRY(hipEventRecord(ix->ev[4], st));
-        n_wg = pieces_wgs ? pieces_wgs : gx_main * S + gx_tail * S2;
-        if (retried) { ix->ms_keep[0] = ms_first[0]; ix->ms_keep[1] = ms_first[1]; ix->ms_keep[2] = ms_first[2]; ix->ms_keep_valid = true; }
-    } else {
-        const int64_t n_chunks = (ix->n + 63) / 64;
-        const int64_t gx = (m + 63) / 64;
-        S = ix->opt.splits;
-        if (S <= 0) {
-            S = 1;
-            if (gx < 512) {
-                S = (int)((1024 + gx - 1) / gx);
-                if (S > n_chunks) S = (int)n_chunks;
-                if (S > 16) S = 16;
-            }
-        }
-        if (S > 16) S = 16;
-        if (S < 1) S = 1;
-        bool done = false;
-        const int S_exact = S;
-        snprintf(ix->kernel, sizeof(ix->kernel), "canberra_topk_kernel (float64)");
-        if (top) ix->row_pass.assign((size_t)m, (uint8_t)NABO_PASS_EXACT);
-        if (ix->cb_f32 && n_valid >= kk) {
-            // fp32 lower-bound filter -> float64 refine + certification -> exact re-solve of uncertified rows
-            float slack, plateau;
-            nabo::cbf_constants(g, &slack, &plateau);
-            // which counting pass: bitmaps (canberra_bits.hip) where built and instantiated (32-entry lists), else SWAR
-            const bool bits = ix->cb_bits && epl == 1;
-            if (bits) snprintf(ix->kernel, sizeof(ix->kernel), "cbb_filter_kernel<%d> (bit-sliced count on %d-bucket bitmaps + fp32 lower bound)", ix->cb_gp, nabo::cbb_buckets());
-            else snprintf(ix->kernel, sizeof(ix->kernel), "cbf_filter_kernel<%d> (7-bit integer count + fp32 lower bound)", ix->cb_gp);
-            // filter geometry: T rows per workgroup, 2 workgroups per CU resident; every (row, split) ends
-            // with `lists` candidate lists (one per wave).  Splits fill the chip when there are few rows and
-            // trim the last, partially filled round of workgroups when there are many.
-            const int lists = nabo::cbf_lists_per_split();
-            const int rpw = bits ? nabo::cbb_rows_per_wg() : nabo::cbf_rows_per_wg(epl);
-            const int64_t gxf = (m + rpw - 1) / rpw;
-            // resident workgroups: SWAR pass -- one-wave workgroups, 2 per SIMD; bitmap pass -- ONE 8-wave workgroup per CU
-            // (its LDS copy of the table rows + eight waves' lists fill the CU's LDS)
-            const int64_t slots = bits ? (int64_t)ix->n_cu : (int64_t)ix->n_cu * 8;
-            int Sf = ix->opt.splits;
-            int s_max = 1024 / (lists * L);                   // refine handles <= 1024 candidates per row
-            if (bits) {                                       // splits are ranges of 2048-reference blocks, >= 2 each
-                const int64_t nb2 = ((ix->n + 2047) / 2048) / 2;
-                if (s_max > nb2) s_max = (int)nb2;
-            } else if (s_max > n_chunks / (8 * lists)) s_max = (int)(n_chunks / (8 * lists));
-            if (s_max < 1) s_max = 1;
-            if (Sf <= 0) {
-                Sf = 1;
-                double best = 1e30;
-                for (int s2 = 1; s2 <= s_max; ++s2) {
-                    // full-length rounds of workgroups, and ~8 % more bound evaluations per extra split
-                    // (every list warms up on its own): measured on 100k x 100k, d = 50
-                    const double cost = (double)((gxf * s2 + slots - 1) / slots) / s2 * (1.0 + 0.08 * (s2 - 1));
-                    if (cost < best - 1e-9) { best = cost; Sf = s2; }
-                }
-            }
-            if (Sf > s_max) Sf = s_max;
-            // "tail round": with many rows the last, partially filled round of workgroups gets its own (larger)
-            // split factor so that it takes a fraction of a round -- same idea as in the Euclidean launch above
-            int64_t gx_main = gxf, gx_tail = 0;
-            int S2 = 1;
-            if (ix->opt.splits <= 0 && ix->opt.tail_split != 0 && gxf > slots && gxf % slots != 0 &&
-                s_max >= 2) {
-                const int64_t tail = gxf % slots;
-                double best_t = 1e30;
-                int best_s = 1;
-                for (int s2 = 1; s2 <= s_max; ++s2) {
-                    const double c = (double)((tail * s2 + slots - 1) / slots) / s2 * (1.0 + 0.08 * (s2 - 1));
-                    if (c < best_t - 1e-9) { best_t = c; best_s = s2; }
-                }
-                const double cost_uniform = (double)((gxf * Sf + slots - 1) / slots) / Sf * (1.0 + 0.08 * (Sf - 1));
-                const double cost_tail = (double)(gxf / slots) + best_t;
-                if (best_s > 1 && cost_tail < cost_uniform - 1e-9) {
-                    gx_tail = tail; gx_main = gxf - tail; S2 = best_s; Sf = 1;
-                }
-            }
-            S = Sf;
-            const int SL = Sf * lists, SL2 = S2 * lists;
-            const int64_t rows_main = gx_tail > 0 ? gx_main * rpw : m;          // rows of the main launch
-            const int64_t rows_tail = m - rows_main;
-            if ((rc = ix->xpk.reserve((size_t)m * ix->cb_gp * 2 * sizeof(float)))) return rc;
-            if ((rc = ix->xh.reserve((size_t)m * ix->cb_gp * 2))) return rc;
-            if ((rc = ix->cand_idx.reserve((size_t)rows_main * SL * L * sizeof(uint32_t)))) return rc;
-            if ((rc = ix->cand_tau.reserve((size_t)rows_main * SL * sizeof(float) + 16))) return rc;
-            if (rows_tail > 0) {
-                if ((rc = ix->cand_idx2.reserve((size_t)rows_tail * SL2 * L * sizeof(uint32_t)))) return rc;
-                if ((rc = ix->cand_tau2.reserve((size_t)rows_tail * SL2 * sizeof(float) + 16))) return rc;
-            }
-            if ((rc = ix->fails.reserve((size_t)m * sizeof(uint32_t)))) return rc;
-            const bool dbg_counts = (nabo::debug_ablate() & 4) != 0;
-            if (dbg_counts) HIP_TRY(hipMemsetAsync(ix->cand_tau.as<float>() + (size_t)rows_main * SL, 0, 8, st));
-            HIP_TRY(hipMemsetAsync(ix->cbflag.p, 0, 4 * sizeof(unsigned int), st));
-            unsigned int *d_failcnt = ix->cbflag.as<unsigned int>() + 1, *d_flag = ix->cbflag.as<unsigned int>();
-            HIP_TRY(nabo::cbf_pack_targets_launch(dX, m, g, ix->cb_gp, ix->f, ix->xpk.as<float>(), d_flag, st));
-            if (bits) {
-                if ((rc = ix->cbrow.reserve((size_t)m * ix->cb_gp * sizeof(uint16_t)))) return rc;
-                HIP_TRY(nabo::cbb_pack_targets_launch(dX, m, g, ix->cb_gp, ix->f, ix->cbedges.as<double>(), ix->cbrow.as<uint16_t>(), st));
-                HIP_TRY(hipEventRecord(ix->ev[1], st));
-                HIP_TRY(nabo::cbb_filter_launch(ix->cb_gp, ix->xpk.as<float>(), ix->cbrow.as<uint16_t>(), rows_main,
-                                                ix->yrow.as<float>(), ix->cbtab.as<uint32_t>(), ix->cbvalid.as<uint32_t>(), ix->n, g,
-                                                Sf, ix->cand_idx.as<uint32_t>(), ix->cand_tau.as<float>(), st));
-                if (rows_tail > 0)
-                    HIP_TRY(nabo::cbb_filter_launch(ix->cb_gp, ix->xpk.as<float>() + (size_t)rows_main * ix->cb_gp * 2,
-                                                    ix->cbrow.as<uint16_t>() + (size_t)rows_main * ix->cb_gp, rows_tail,
-                                                    ix->yrow.as<float>(), ix->cbtab.as<uint32_t>(), ix->cbvalid.as<uint32_t>(),
-                                                    ix->n, g, S2, ix->cand_idx2.as<uint32_t>(), ix->cand_tau2.as<float>(), st));
-            } else {
-                HIP_TRY(nabo::cbf_pack_targets8_launch(dX, m, g, ix->cb_gp, ix->f, ix->cbscale.as<double>(), ix->xh.p, st));
-                HIP_TRY(hipEventRecord(ix->ev[1], st));
-                HIP_TRY(nabo::cbf_filter_launch(ix->cb_gp, epl, ix->xpk.as<float>(), ix->xh.p, rows_main, ix->yrow.as<float>(),
-                                                ix->ych.p, ix->n, g, ix->dmask, Sf, ix->cand_idx.as<uint32_t>(),
-                                                ix->cand_tau.as<float>(), st));
-                if (rows_tail > 0)
-                    HIP_TRY(nabo::cbf_filter_launch(ix->cb_gp, epl, ix->xpk.as<float>() + (size_t)rows_main * ix->cb_gp * 2,
-                                                    ix->xh.as<unsigned char>() + (size_t)rows_main * ix->cb_gp * 2, rows_tail,
-                                                    ix->yrow.as<float>(), ix->ych.p, ix->n, g, ix->dmask, S2,
-                                                    ix->cand_idx2.as<uint32_t>(), ix->cand_tau2.as<float>(), st));
-            }
-            HIP_TRY(hipEventRecord(ix->ev[2], st));
-            if (dbg_counts) {
-                unsigned int c2[2] = {0, 0};
-                HIP_TRY(hipMemcpyAsync(c2, ix->cand_tau.as<float>() + (size_t)rows_main * SL, 8, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                fprintf(stderr, "[nabo debug] canberra filter (main launch): splits=%d survivors=%u (%.1f per row) batches=%u\n",
-                        Sf, c2[0], (double)c2[0] / (double)rows_main, c2[1]);
-            }
-            HIP_TRY(nabo::refine_launch(dX, 0, rows_main, ix->dY, g, ix->cand_idx.as<uint32_t>(), ix->cand_tau.as<float>(), SL,
-                                        L, nullptr, 0.0, 0.0, 1.0, k, drop, ix->base, n_valid, ix->mlistbuf.as<uint32_t>(),
-                                        tail_len(ix), d_oidx, d_odist, ix->fails.as<uint32_t>(), d_failcnt, st, 1,
-                                        ix->f, plateau));
-            if (rows_tail > 0)
-                HIP_TRY(nabo::refine_launch(dX, rows_main, m, ix->dY, g, ix->cand_idx2.as<uint32_t>(),
-                                            ix->cand_tau2.as<float>(), SL2, L, nullptr, 0.0, 0.0, 1.0, k, drop, ix->base,
-                                            n_valid, ix->mlistbuf.as<uint32_t>(), tail_len(ix), d_oidx, d_odist,
-                                            ix->fails.as<uint32_t>(), d_failcnt, st, 1, ix->f, plateau));
-            HIP_TRY(hipEventRecord(ix->ev[3], st));
-            unsigned int hf[2] = {0, 0};
-            HIP_TRY(hipMemcpyAsync(hf, ix->cbflag.p, sizeof(hf), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (hf[0] == 0) {                    // targets fit fp32: results stand, re-solve uncertified rows
-                n_fail = hf[1];
-                if (top) {
-                    ix->row_pass.assign((size_t)m, (uint8_t)NABO_PASS_CANBERRA);
-                    if ((rc = note_row_pass(ix, ix->fails.as<uint32_t>(), n_fail, (uint8_t)NABO_PASS_EXACT, pass_map))) return rc;
-                }
-                if (n_fail > 0) {
-                    const int64_t nf = n_fail;
-                    int S3 = 1;
-                    const int64_t gx3 = (nf + 63) / 64;
-                    if (gx3 < 512) {
-                        S3 = (int)((1024 + gx3 - 1) / gx3);
-                        if (S3 > n_chunks) S3 = (int)n_chunks;
-                        if (S3 > 16) S3 = 16;
-                    }
-                    if ((rc = ix->xfail.reserve((size_t)nf * g * sizeof(double)))) return rc;
-                    if ((rc = ix->cand_d.reserve((size_t)nf * S3 * L * sizeof(double)))) return rc;
-                    if ((rc = ix->cand_idx2.reserve((size_t)nf * S3 * L * sizeof(uint32_t)))) return rc;
-                    if ((rc = ix->tmpi.reserve((size_t)nf * k * sizeof(int64_t)))) return rc;
-                    if ((rc = ix->tmpd.reserve((size_t)nf * k * sizeof(double)))) return rc;
-                    HIP_TRY(nabo::gather_rows_launch(dX, ix->fails.as<uint32_t>(), nf, g, ix->xfail.as<double>(), st));
-                    HIP_TRY(nabo::canberra_topk_launch(epl, ix->xfail.as<double>(), nf, ix->yt.as<double>(), ix->n, g, ix->f,
-                                                       ix->dmask, S3, ix->cand_d.as<double>(), ix->cand_idx2.as<uint32_t>(), st));
-                    HIP_TRY(nabo::merge_local_launch(ix->cand_d.as<double>(), ix->cand_idx2.as<uint32_t>(), nf, S3 * L, k, drop,
-                                                     ix->base, ix->tmpi.as<int64_t>(), ix->tmpd.as<double>(), nullptr, st));
-                    HIP_TRY(nabo::scatter_rows_launch(ix->tmpi.as<int64_t>(), ix->tmpd.as<double>(), ix->fails.as<uint32_t>(), nf,
-                                                      k, d_oidx, d_odist, st));
-                }
-                HIP_TRY(hipEventRecord(ix->ev[4], st));
-                done = true;
-            }
-        }
-        if (!done) {
-            S = S_exact;
-            if ((rc = ix->cand_d.reserve((size_t)m * S * L * sizeof(double)))) return rc;
-            if ((rc = ix->cand_idx.reserve((size_t)m * S * L * sizeof(uint32_t)))) return rc;
-            HIP_TRY(hipEventRecord(ix->ev[1], st));
-            HIP_TRY(nabo::canberra_topk_launch(epl, dX, m, ix->yt.as<double>(), ix->n, g, ix->f, ix->dmask, S,
-                                               ix->cand_d.as<double>(), ix->cand_idx.as<uint32_t>(), st));
-            HIP_TRY(hipEventRecord(ix->ev[2], st));
-            HIP_TRY(nabo::merge_local_launch(ix->cand_d.as<double>(), ix->cand_idx.as<uint32_t>(), m, S * L, k, drop,
-                                             ix->base, d_oidx, d_odist, nullptr, st));
-            HIP_TRY(hipEventRecord(ix->ev[3], st));
-            if (n_valid < kk)
-                HIP_TRY(nabo::masked_tail_launch(dX, m, ix->dY, g, ix->metric, ix->f, ix->mlistbuf.as<uint32_t>(),
-                                                 tail_len(ix), (int)n_valid, k, drop, ix->base, d_oidx, d_odist, st));
-            HIP_TRY(hipEventRecord(ix->ev[4], st));
-        }
-        n_wg = gx * S;
-    }
-    if (!out_on_device) {
-        HIP_TRY(hipMemcpyAsync(out_idx, d_oidx, ob, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_dist, d_odist, ob, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipEventRecord(ix->ev[5], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float t = 0;
-    for (int i = 0; i < 4; ++i) {
-        HIP_TRY(hipEventElapsedTime(&t, ix->ev[i], ix->ev[i + 1]));
-        ix->ms[i] = t;
-    }
-    HIP_TRY(hipEventElapsedTime(&t, ix->ev[0], ix->ev[5]));
-    ix->ms[4] = t;
-    if (ix->ms_keep_valid) {            // a second-chance pass reused the events: phases 0-2 were saved before it ran
-        ix->ms_keep_valid = false;
-        HIP_TRY(hipEventElapsedTime(&t, ix->ev[3], ix->ev[5]));
-        const double inner_total = ix->ms[4];      // (events 0..2 now belong to the inner call)
-        (void)inner_total;
-        ix->ms[0] = ix->ms_keep[0];
-        ix->ms[1] = ix->ms_keep[1];
-        ix->ms[2] = ix->ms_keep[2];
-        ix->ms[3] = ix->ms_inner + t;              // inner pass (its own total) + scatter / copy-out
-        ix->ms[4] = ix->ms[0] + ix->ms[1] + ix->ms[2] + ix->ms[3];
-    }
-    ix->ms_inner = ix->ms[4];
-    ix->counters[0] = n_fail;
-    ix->counters[1] = S;
-    ix->counters[2] = L;
-    ix->counters[3] = n_wg;
-    return NABO_OK;
+    rc = exact_route ? query_exact(ix, q) : ix->metric != NABO_METRIC_MOD_CANBERRA ? query_l2(ix, q) : query_canberra(ix, q);
+    if (rc || q.timing_only) return rc;
+    return finish_query(ix, q, out_idx, out_dist, out_on_device);
 }
 
 // (every entry point that touches an index first waits for the asynchronous query it may have in flight and hands its
@@ -2005,7 +1752,7 @@ int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t
     int rc = plan_l2(&ix, m, kq, cand ? 0 : drop, cand, &P);
     if (rc) return rc;
     int pt = 0, gt = 0;
-    if (P.on_l2c && ix.opt.prepass > 0) nabo::l2c_pre_plan(P.kcq, P.lkeep, (int)(P.pieces ? P.piece_len : P.tps), ix.opt.prepass, &pt, &gt);
+    if (P.on_l2c && ix.opt.prepass > 0) nabo::l2c_pre_plan(P.kcq, P.lkeep, (int)P.tps, ix.opt.prepass, &pt, &gt);
     out[0] = P.use_1 ? NABO_PASS_ONE_PRODUCT : NABO_PASS_SECOND;
     out[1] = P.geo;
     out[2] = P.rows_per_wg;
@@ -2019,11 +1766,9 @@ int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t
     out[10] = pt;
     out[11] = gt;
     out[12] = (int64_t)n_cu * P.wg_per_cu;
-    out[13] = P.pieces ? P.piece_wgs : P.gx_main * P.S + P.gx_tail * P.S2;
+    out[13] = P.gx_main * P.S + P.gx_tail * P.S2;
     out[14] = P.rows_pad;
-    out[15] = P.kcq;
-    out[16] = P.pieces ? 1 : 0;
-    out[17] = P.piece_len;
+    out[15] = P.kcq;                                 // (out[16], out[17]: the launch cut into pieces, removed -- always 0)
     if (kernel && kernel_len) snprintf(kernel, kernel_len, "%s", P.kernel);
     return NABO_OK;
 }

@@ -8,7 +8,7 @@
 // split, all ones = "no reference"; api.hip raises the split count of larger sets
 #define NABO_LIST_SPLIT_REFS (((int64_t)1 << 25) - 1)
 
-// A filter launch cut into PIECES (l2c_topk.hip; api.hip: cut_pieces): device arrays.
+// A filter launch cut into PIECES (l2c_topk.hip, experiments builds; the host side was removed from api.hip): device arrays.
 //   pieces   [n_pieces] int4 (column-workgroup, list slot of that column, first reference tile, end tile), one workgroup each,
 //            longest first
 //   ranges   [columns x S] int4 (first tile, end tile, tournament tiles, tiles per tournament group) per (column, slot);
@@ -23,8 +23,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int WAVE = 64;
 
 // NABO_DEBUG_ABLATE (kernel-timing experiments whose RESULTS ARE GARBAGE: no-hit runs, L2-resident streams, counters)
-// exists only in builds made with -DNABO_EXPERIMENTS (tools/ab, tools/r*_call*.sh build such variants next to the
-// product through `python -m nabo_amd._build --out ...`); the shipped library never reads the variable.
+// exists only in builds made with -DNABO_EXPERIMENTS (tools/ab builds such variants next to the product through
+// `python -m nabo_amd._build --out ...`; besides it they only read the options from NABO_OPT_<NAME>); the shipped
+// library never reads the variable.
 static inline int debug_ablate()
 {
 #ifdef NABO_EXPERIMENTS

@@ -1,6 +1,6 @@
 // l2c_topk.hip -- the ONE-PRODUCT Euclidean filter: the first pass of the default Euclidean / cosine query (gfx950).
 //
-// Operands: pack_ctiles_kernel<., true, 1> (l2s_topk.hip) -- a cell is ONE vector of g + 3 f16 slots,
+// Operands: pack_ctiles_kernel<., true, 1> (pack.hip) -- a cell is ONE vector of g + 3 f16 slots,
 //   references [hi (g) | nh | nl | ey],  targets [-2 hi (g) | 2^15 | 2^15 | -tx],
 // so the contraction  ||rep_y||^2 - 2 hi_x.hi_y - tx ey  needs KS = ceil((g + 3) / 32) steps of v_mfma_f32_16x16x32_f16
 // (2 at g = 50) where the f16x3 split of l2q_topk.hip needs 5.  tx ey >= the split's dropped terms (hi x lo, lo x hi,
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                                                           int tau_stride, int64_t tau_row0,
                                                           const int4 *__restrict__ pieces, int piece_S)
 {
-    // PIECES (api.hip: cut_pieces): with fewer column-workgroups than the chip has slots a launch of (columns x splits)
+    // PIECES (host side removed: see git history): with fewer column-workgroups than the chip has slots a launch of (columns x splits)
     // workgroups either leaves slots empty or spills a few workgroups into a second round that costs as much as the first.
     // Instead the linear space (column, reference tile) is cut into ~`slots` equal chunks, a chunk that crosses a column
     // boundary into two pieces, and the launch is ONE WORKGROUP PER PIECE = (column, list slot of the column, first tile, end
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             xb[rb][s] = p[((rb & 1) * KS + s) * 64 + lane];
-            // pinned in AGPRs (l2h_topk.hip) at one wave per SIMD.  NOT at two: with 256 registers per wave hipcc then
+            // pinned in AGPRs (the asm below) at one wave per SIMD.  NOT at two: with 256 registers per wave hipcc then
             // parks ACCUMULATORS in the spare AGPRs and copies them (v_accvgpr_write) right behind the inline-assembly
             // MFMA that is still writing them -- a hazard it cannot see (wrong neighbours in 3 of 9 test shapes).
             if (WPS == 1) asm volatile("" : "+a"(xb[rb][s]));

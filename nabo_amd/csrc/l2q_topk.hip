@@ -1,12 +1,18 @@
-// l2q_topk.hip -- the f16x3 Euclidean filter of l2h_topk.hip on the 16x16x32 MFMA shape (gfx950).
+// l2q_topk.hip -- Euclidean score + top-L filter with the contraction on the f16 matrix pipe ("f16x3" split), gfx950.
 //
-// Same arithmetic, same K-concatenated f16 operands (hi/lo split, norm slot; l2h_topk.hip's header), same staged
-// candidate lists -- but the contraction runs on v_mfma_f32_16x16x32_f16 instead of v_mfma_f32_32x32x16_f16.  Both
-// shapes deliver 1024 flop per cycle and SIMD; what differs is the CLOCK the chip holds under them.  The f16 kernels
-// are power-limited: with the matrix pipe 93 % busy the part runs the 32x32x16 stream at 1.75 GHz, and every stall
-// removed from the loop comes back as a lower clock (GRBM_GUI_ACTIVE per ablation).  tools/
-// mfma_clock_lab.hip (random operands, registers only, one wave per SIMD): 32x32x16 holds 1.66 GHz = 1657 TFLOP/s,
-// 16x16x32 holds 2.05 GHz = 2008 TFLOP/s at the same cycles per flop (MI355X_MICROARCH.md, "DVFS give-back" item 7).
+// Every centred, scaled component v is split v = hi + lo (two f16 values, 22 significant bits together); the -2 x.y
+// term is accumulated in fp32 from the three products  hi_y*hi_x + lo_y*hi_x + hi_y*lo_x  (lo*lo <= 2^-22 |x||y| is
+// dropped).  Operands are K-CONCATENATED (pack.hip: pack_ctiles_kernel): a reference cell is ONE vector [hi | lo | hi] of
+// 3 (g+1) slots, a target [hi | hi | lo] (x -2), slot g of every segment carrying the norm term, so a tile is KC steps of
+// 16 slots starting from C = 0.  The score only FILTERS candidates: refine.hip recomputes them in float64 and certifies
+// the row with an error bound that accounts for the split (api.hip), so results are the same bits as the fp32 path.
+// Candidate lists are staged as in topk_lists.h.
+// The contraction runs on v_mfma_f32_16x16x32_f16 -- the first form of this filter ran on v_mfma_f32_32x32x16_f16
+// (l2h_topk.hip, measured slower and removed: see git history).  Both shapes deliver 1024 flop per cycle and SIMD;
+// what differs is the CLOCK the chip holds under them.  The f16 kernels are power-limited: with the matrix pipe 93 %
+// busy the part runs the 32x32x16 stream at 1.75 GHz, and every stall removed from the loop comes back as a lower clock
+// (GRBM_GUI_ACTIVE per ablation).  tools/mfma_clock_lab.hip (random operands, registers only, one wave
+// per SIMD): 32x32x16 holds 1.66 GHz = 1657 TFLOP/s, 16x16x32 holds 2.05 GHz = 2008 TFLOP/s at the same cycles per flop (MI355X_MICROARCH.md, "DVFS give-back" item 7).
 //
 // Layout: a wave owns 128 target rows as EIGHT row-blocks of 16; a reference tile is 32 cells = two halves of 16.
 //   v_mfma_f32_16x16x32_f16: A = 16 references x 32 slots, B = 32 slots x 16 targets, lane l supplies cell l & 15,
@@ -116,7 +122,7 @@ __device__ __forceinline__ void qfilter(const qacc &acc, int rb0, uint32_t jb, u
 }
 
 // Grid: x = target super-blocks (4 waves x 128 rows), y = reference splits.
-// HOMEP: the locality-ordered form (order.hip; off by default) -- compiled separately so that the default kernel carries
+// HOMEP: the locality-ordered form (its host side, order.hip, was removed: see git history) -- compiled separately so that the default kernel carries
 // none of its per-tile index arithmetic.
 template <int KC, int EPL, int ROWN, bool HOMEP = false>
 __global__ __launch_bounds__(256, 1) void l2q_topk_kernel(const unsigned char *__restrict__ Xpk,
@@ -150,7 +156,7 @@ __global__ __launch_bounds__(256, 1) void l2q_topk_kernel(const unsigned char *_
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             xb[rb][s] = p[((rb & 1) * KS + s) * 64 + lane];
-            asm volatile("" : "+a"(xb[rb][s]));        // pinned in AGPRs (see l2h_topk.hip)
+            asm volatile("" : "+a"(xb[rb][s]));        // pinned in AGPRs (see l2c_topk.hip)
         }
     }
     unsigned char *wl = smem_raw + (size_t)wave * C::BYTES;          // this wave's lists (topk_lists.h)
@@ -163,7 +169,7 @@ __global__ __launch_bounds__(256, 1) void l2q_topk_kernel(const unsigned char *_
 
     const int t_begin = split * tiles_per_split;
     const int t_end = t_begin + tiles_per_split;
-    // Locality order (order.hip): before the common stream a wave visits L2Q_HOME tiles around the tile that holds its
+    // Locality order (host side removed, see HOMEP): before the common stream a wave visits L2Q_HOME tiles around the tile that holds its
     // rows' neighbourhood (wave_start, per 128 target rows): its thresholds are near their final values when the stream
     // proper begins, and that stream still runs from the split's first tile in step with every other wave of the XCD
     // (one copy of the stream in L2 -- a cyclic start per wave gave 4x fewer episodes and a 14 % SLOWER kernel: every wave
@@ -240,7 +246,7 @@ __global__ __launch_bounds__(256, 1) void l2q_topk_kernel(const unsigned char *_
         }
     };
     // Peeled first pair of steps + padding tile: the wait hipcc places at the loop head must be vmcnt(19..10) (one set's
-    // refills done, the other's in flight), see l2h_topk.hip.
+    // refills done, the other's in flight), as in the removed 32x32x16 kernel (l2h_topk.hip, git history).
     tile_step(a0, t_begin);
     tile_step(a1, t_begin + 1);
     for (int t = t_begin + 2; t < t_end; t += 2) {

@@ -166,7 +166,7 @@ hipError_t maxabs_launch(const double *V, int64_t n, int g, const double *centre
 // subnormals round with an absolute error).  The error term is a product of two slots: it costs no instruction, and it
 // is per PAIR -- a per-row constant would have to assume max ||y||.
 // Register layouts (16 bytes per lane and register, a tile is kc KiB either way):
-//   L16 = false (v_mfma_f32_32x32x16_f16; l2h / l2s kernels): register s < kc, lane l: cell l & 31,
+//   L16 = false (v_mfma_f32_32x32x16_f16; the removed l2h / l2s kernels): register s < kc, lane l: cell l & 31,
 //                slots 16 s + 8 (l >> 5) + j;
 //   L16 = true  (v_mfma_f32_16x16x32_f16; l2q kernel): register h (kc/2) + s, h < 2, s < kc/2, lane l: cell 16 h + (l & 15),
 //                slots 32 s + 8 (l >> 4) + j.
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(64) void pack_ctiles_kernel(const double *__restric
         const int c = L16 ? 16 * hc + (lane & 15) : lane & 31;
         const int64_t cell = tile * 32 + c;
         const bool live = cell < ncell;
-        // locality order (order.hip): packed position `cell` holds caller row perm[cell]; norm64 is indexed by POSITION
+        // locality order (order.hip, removed: see git history): packed position `cell` holds caller row perm[cell]; norm64 is indexed by POSITION
         const int64_t src = (live && perm) ? (int64_t)perm[cell] : cell;
         // whole-row pass: range check and ||rep||^2 (every lane of a cell computes the same)
         bool bad = false;

@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void refine_kernel(const double *__restrict__ 
                                                      const uint32_t *__restrict__ tperm, float *__restrict__ fail_seed)
 {
     // rows [row0, m) of the filter's row order; candidate arrays are indexed by the row LOCAL to this launch.
-    // Locality order (order.hip): the filter worked on permuted rows -- position prow holds target row tperm[prow]
+    // Locality order (order.hip, removed: see git history): the filter worked on permuted rows -- position prow holds target row tperm[prow]
     // (xnorm is indexed by position), candidate value c is reference row rperm[c]; both are mapped back HERE, before
     // the sort by (distance, index), so order rows and indices are the caller's.
     const int lane = lane_id();

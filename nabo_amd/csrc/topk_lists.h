@@ -1,5 +1,5 @@
-// topk_lists.h -- wave-private candidate lists in LDS shared by the Euclidean top-L kernels (l2_topk.hip,
-// l2h_topk.hip, l2s_topk.hip): STAGED hits, BATCHED list updates.
+// topk_lists.h -- wave-private candidate lists in LDS shared by the Euclidean top-L kernels (l2_topk.hip;
+// l2q_topk.hip and l2c_topk.hip stage theirs the same way): STAGED hits, BATCHED list updates.
 //
 // Accumulator convention (v_mfma_f32_32x32x*): lane l holds, for target row (l & 31) of a row-block, 16 scores a[i];
 // register i of lane half h = l >> 5 belongs to reference jb + cd_row(i, 0) where jb = first reference of the tile + 4 h.
@@ -389,8 +389,9 @@ __device__ __forceinline__ void filter_and_stage(const f32x16 &acc, int rb, uint
     }
 }
 
-// The same filter in two parts (l2h_topk.hip): the minimum / compare, free of control flow so that hipcc can schedule it
-// between the MFMAs of the chain issued next, and the branch on its verdict.
+// The same filter in two parts (written for the removed l2h_topk.hip; l2q_topk.hip's qfilter_eval follows it): the
+// minimum / compare, free of control flow so that hipcc can schedule it between the MFMAs of the chain issued next, and
+// the branch on its verdict.
 struct FilterVerdict { float m; uint64_t any; };
 
 template <int NB>
