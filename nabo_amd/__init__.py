@@ -7,6 +7,8 @@ from ._knn import knn, knn_devices, pairwise, KnnIndex, snn_counts  # noqa: F401
 from ._mapping import Mapping, write_dense_pca, expand_graph  # noqa: F401
 from ._score import (get_mapping_score, mapping_score_from_edges, mapping_score_null,  # noqa: F401
                      get_mapping_score_null)
+from ._paths import (RefGraph, group_hops, get_mapping_specificity, get_ref_specificity,  # noqa: F401
+                     calc_contiguous_spl)
 
-__all__ = ["Mapping", "write_dense_pca", "expand_graph", "get_mapping_score", "mapping_score_from_edges", "mapping_score_null", "get_mapping_score_null", "knn", "knn_devices", "pairwise", "KnnIndex", "snn_counts", "device_count", "EUCLIDEAN", "MOD_CANBERRA", "COSINE",
+__all__ = ["Mapping", "write_dense_pca", "expand_graph", "get_mapping_score", "mapping_score_from_edges", "mapping_score_null", "get_mapping_score_null", "RefGraph", "group_hops", "get_mapping_specificity", "get_ref_specificity", "calc_contiguous_spl", "knn", "knn_devices", "pairwise", "KnnIndex", "snn_counts", "device_count", "EUCLIDEAN", "MOD_CANBERRA", "COSINE",
            "NaboError"]

@@ -29,6 +29,11 @@ SYMBOLS = [
     "nabo_sharded_query", "nabo_sharded_last_stats", "nabo_knn_devices",
 ]
 
+# every symbol include/nabo_graph.h declares (hop distances on the reference graph; kept apart from SYMBOLS, which
+# pins include/nabo_knn.h)
+GRAPH_SYMBOLS = ["nabo_refgraph_create", "nabo_refgraph_destroy", "nabo_refgraph_set_option", "nabo_refgraph_group_hops",
+                 "nabo_refgraph_last_stats", "nabo_refgraph_last_local_nodes"]
+
 
 class NaboError(RuntimeError):
     pass
@@ -88,7 +93,13 @@ def lib():
     L.nabo_sharded_query.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, i32]
     L.nabo_sharded_last_stats.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
     L.nabo_knn_devices.argtypes = [vp, i64, vp, i64, i32, i32, i32, dbl, vp, i32, C.POINTER(i32), i32, i32, vp, vp]
-    for name in SYMBOLS:
+    L.nabo_refgraph_create.argtypes = [C.POINTER(vp), i32, i64, vp, vp]
+    L.nabo_refgraph_destroy.argtypes = [vp]
+    L.nabo_refgraph_set_option.argtypes = [vp, C.c_char_p, i64]
+    L.nabo_refgraph_group_hops.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    L.nabo_refgraph_last_stats.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
+    L.nabo_refgraph_last_local_nodes.argtypes = [vp, i64, vp]
+    for name in SYMBOLS + GRAPH_SYMBOLS:
         if name not in ("nabo_version", "nabo_last_error"):
             getattr(L, name).restype = C.c_int
     _lib = L

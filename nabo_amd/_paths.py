@@ -1,0 +1,302 @@
+"""Hop distances on the reference graph: mapping specificity and contiguous path lengths on the GPU.
+
+Array / HDF5 restatement of three methods of the reference's `Graph` (nabo/_graph.py) that call networkx's
+`shortest_path_length` once per node pair on `refG`, the reference's SNN graph as an undirected simple graph:
+
+  * `get_mapping_specificity` (:794-824)  per target node, the mean hop distance over all pairs of the reference
+    nodes it is connected to;
+  * `get_ref_specificity`     (:826-857)  per reference node, the mean specificity of the target nodes mapped to it;
+  * `calc_contiguous_spl`     (:904-916)  the mean hop distance between consecutive nodes of a list.
+
+The distances come from `nabo_refgraph_group_hops` (include/nabo_graph.h, nabo_amd/csrc/paths.hip): every pair
+of a group of reference nodes, answered by a workgroup-local search or by whole-graph multi-source BFS sweeps.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+
+def _i64(a, name):
+    a = np.ascontiguousarray(a, dtype=np.int64)
+    if a.ndim != 1:
+        raise ValueError("ERROR: %s must be 1-D" % name)
+    return a
+
+
+class _DeviceGraph:
+    """A graph resident on one device (nabo_refgraph_create); node ids are 0 .. n-1."""
+
+    def __init__(self, ptr, nbr, device=0, options=None):
+        ptr, nbr = _i64(ptr, "ptr"), _i64(nbr, "nbr")
+        if ptr.shape[0] < 1:
+            raise ValueError("ERROR: ptr needs n_nodes + 1 entries")
+        if int(ptr[-1]) != nbr.shape[0]:
+            raise ValueError("ERROR: ptr[-1] = %d but nbr has %d entries" % (int(ptr[-1]), nbr.shape[0]))
+        self.n = ptr.shape[0] - 1
+        self._h = None
+        L = _lib.lib()
+        h = C.c_void_p()
+        _lib.check(L.nabo_refgraph_create(C.byref(h), int(device), int(self.n), ptr.ctypes.data, nbr.ctypes.data))
+        self._h = h
+        for k, v in (options or {}).items():
+            self.set_option(k, v)
+
+    def set_option(self, name, value):
+        _lib.check(_lib.lib().nabo_refgraph_set_option(self._h, name.encode(), int(value)))
+
+    def group_hops(self, grp_ptr, members, pair_hops=False):
+        grp_ptr, members = _i64(grp_ptr, "grp_ptr"), _i64(members, "members")
+        if grp_ptr.shape[0] < 1 or int(grp_ptr[-1]) != members.shape[0]:
+            raise ValueError("ERROR: grp_ptr must have n_groups + 1 entries ending at len(members)")
+        G = grp_ptr.shape[0] - 1
+        m = np.diff(grp_ptr)
+        if (m < 0).any():
+            raise ValueError("ERROR: grp_ptr is not monotone")
+        s = np.zeros(G, dtype=np.int64)
+        u = np.zeros(G, dtype=np.int64)
+        ph = np.empty(int((m * (m - 1) // 2).sum()), dtype=np.int32) if pair_hops else None
+        _lib.check(_lib.lib().nabo_refgraph_group_hops(self._h, int(G), grp_ptr.ctypes.data, members.ctypes.data,
+                                                       s.ctypes.data, u.ctypes.data, None if ph is None else ph.ctypes.data))
+        return (s, u, ph) if pair_hops else (s, u)
+
+    def last_stats(self):
+        """{"ms": (build, local, global, total), "local_groups", "global_groups", "sweeps", "max_level"}"""
+        ms = (C.c_double * 4)()
+        cnt = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().nabo_refgraph_last_stats(self._h, ms, cnt))
+        return {"ms": tuple(ms), "local_groups": cnt[0], "global_groups": cnt[1], "sweeps": cnt[2], "max_level": cnt[3]}
+
+    def last_local_nodes(self, n_groups):
+        out = np.empty(int(n_groups), dtype=np.int32)
+        _lib.check(_lib.lib().nabo_refgraph_last_local_nodes(self._h, int(n_groups), out.ctypes.data))
+        return out
+
+    def close(self):
+        if self._h is not None:
+            _lib.lib().nabo_refgraph_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def group_hops(ptr, nbr, grp_ptr, members, pair_hops=False, device=0, options=None):
+    """Hop distances of every member pair of every group, on the undirected simple graph a CSR (ptr, nbr) describes
+    (rows in either arc direction; duplicate arcs and self-loops allowed).
+
+    Group g is members[grp_ptr[g]:grp_ptr[g+1]] (node ids; repeats allowed, a repeated pair is at distance 0).
+    Returns (sum, unreached): int64 [n_groups] sums of the reachable pairs' distances and counts of unreachable
+    pairs; with pair_hops=True also int32 distances of every pair (-1 = no path), each group's m(m-1)/2 pairs in
+    (i, j) lexicographic order, groups one after the other.  `options`: {"local_capacity": .., "local_max_members":
+    ..} (include/nabo_graph.h) -- they decide which tier answers a group, never the result."""
+    g = _DeviceGraph(ptr, nbr, device, options)
+    try:
+        return g.group_hops(grp_ptr, members, pair_hops)
+    finally:
+        g.close()
+
+
+# ---- the mapping file ---------------------------------------------------------------------------------------------
+def _open_ref(h5, ref_name):
+    if h5["name_stash/ref_name"][0].decode("UTF-8") != ref_name:
+        raise KeyError("ERROR: The reference is named %s in the mapping file and not %s. Please verify that you are "
+                       "trying to load right reference." % (h5["name_stash/ref_name"][0].decode("UTF-8"), ref_name))
+    cells = [x.decode("UTF-8") for x in h5["ref_cells/ref_cells"][:]]
+    names = [c + "_" + ref_name for c in cells]
+    return names, {n: i for i, n in enumerate(names)}, h5["name_stash/ref_name"][1].decode("UTF-8")
+
+
+def _target_rows(h5, target, pos):
+    """(target node names in load order, ptr, reference positions) of one mapped sample; KeyError if absent"""
+    from ._mapping import read_graph_csr
+    uid = None
+    if "target_names" in h5["name_stash"]:
+        for i in h5["name_stash/target_names"][:]:
+            if i[0].decode("UTF-8") == target:
+                uid = i[1].decode("UTF-8")
+    if uid is None:
+        raise KeyError(target)
+    nodes, ptr, nbr, _ = read_graph_csr(h5[uid + "_graph"], pos)
+    return nodes, ptr, nbr
+
+
+def _mapped_sets(ptr, nbr):
+    """per target node, its reference neighbours once each in first-seen order (networkx adjacency order)"""
+    gp, mem = [0], []
+    for i in range(len(ptr) - 1):
+        seen = dict.fromkeys(nbr[ptr[i]:ptr[i + 1]].tolist())
+        mem.extend(seen)
+        gp.append(len(mem))
+    return np.array(gp, dtype=np.int64), np.array(mem, dtype=np.int64)
+
+
+def _ref_specificity(h5, ref_name, target, target_values, incl_unmapped):
+    names, pos, ref_uid = _open_ref(h5, ref_name)
+    grp = h5[ref_uid + "_graph"]
+    from ._mapping import _G_NODES, _G_PTR
+    if _G_PTR in grp:
+        ref_nodes = sorted(x.decode("UTF-8") for x in grp[_G_NODES][:])
+    else:
+        ref_nodes = [n for n in grp]
+    t_nodes, ptr, nbr = _target_rows(h5, target, pos)
+    return _ref_specificity_rows(ref_nodes, pos, len(names), t_nodes, ptr, nbr, target_values, incl_unmapped)
+
+
+def _ref_specificity_rows(ref_nodes, pos, n_ref, t_nodes, ptr, nbr, target_values, incl_unmapped):
+    """ref_nodes: reference node names in the reference's node order; pos: name -> id; rows hold ids"""
+    gp, mem = _mapped_sets(ptr, nbr)
+    back = [[] for _ in range(n_ref)]
+    for i, t in enumerate(t_nodes):
+        for r in mem[gp[i]:gp[i + 1]].tolist():
+            back[r].append(target_values[t])
+    out = {}
+    for n in ref_nodes:
+        v = back[pos[n]]
+        if len(v) > 1:
+            out[n] = np.mean(v)
+        elif len(v) == 1:
+            out[n] = v[0]
+        elif incl_unmapped:
+            out[n] = 0
+    return out
+
+
+def _raise_unreachable(dg, names, grp_ptr, members, g):
+    a0, a1 = int(grp_ptr[g]), int(grp_ptr[g + 1])
+    mem = members[a0:a1]
+    _, _, ph = dg.group_hops(np.array([0, a1 - a0], dtype=np.int64), mem, pair_hops=True)
+    p = int(np.nonzero(ph < 0)[0][0])
+    m, i = a1 - a0, 0
+    while p >= m - i - 1:
+        p -= m - i - 1
+        i += 1
+    raise ValueError("ERROR: no path between %s and %s in the reference graph" % (names[mem[i]], names[mem[i + 1 + p]]))
+
+
+def _specificity(dg, names, t_nodes, ptr, nbr, fill_na):
+    """mapping specificity of target nodes t_nodes whose rows (ptr, nbr) hold reference node ids of dg"""
+    gp, mem = _mapped_sets(ptr, nbr)
+    s, u = dg.group_hops(gp, mem)
+    bad = np.nonzero(u)[0]
+    if bad.size:
+        _raise_unreachable(dg, names, gp, mem, int(bad[0]))
+    m = np.diff(gp)
+    pairs = m * (m - 1) // 2
+    vals = [float(s[i]) / float(pairs[i]) if m[i] > 1 else float("nan") for i in range(len(t_nodes))]
+    out = dict(zip(t_nodes, vals))
+    if fill_na:
+        top = max(out.values())
+        if top == top:
+            out = {k: (top if v != v else v) for k, v in out.items()}
+    return out
+
+
+def _contiguous(dg, names, idx):
+    idx = np.asarray(idx, dtype=np.int64)
+    if idx.shape[0] < 2:
+        return float("nan")
+    G = idx.shape[0] - 1
+    gp = np.arange(0, 2 * G + 1, 2, dtype=np.int64)
+    mem = np.stack([idx[:-1], idx[1:]], axis=1).reshape(-1)
+    s, u = dg.group_hops(gp, mem)
+    bad = np.nonzero(u)[0]
+    if bad.size:
+        _raise_unreachable(dg, names, gp, mem, int(bad[0]))
+    return float(s.sum()) / float(G)
+
+
+class RefGraph:
+    """The reference graph of a mapping file, resident on the GPU, with the path methods of the reference's Graph.
+
+    Reads the reference's `<uid>_graph` in either layout (per-node or columnar, `read_graph_csr`) and keeps the
+    undirected simple graph networkx's `refG` would be on the device.  Node ids are positions in
+    `ref_cells/ref_cells`; nodes are named `<cell>_<ref_name>` as in the reference.  Use as a context manager or
+    call close()."""
+
+    def __init__(self, mapping_h5_fn, ref_name, device=0, options=None):
+        import h5py
+        from ._mapping import read_graph_csr
+        self.fn, self.ref_name = mapping_h5_fn, ref_name
+        with h5py.File(mapping_h5_fn, "r") as h5:
+            self.names, self.pos, ref_uid = _open_ref(h5, ref_name)
+            rows, ptr, nbr, _ = read_graph_csr(h5[ref_uid + "_graph"], self.pos)
+        # rows in the group's order -> a CSR by reference position (arc direction does not matter to the device)
+        src = np.repeat(np.array([self.pos[r] for r in rows], dtype=np.int64), np.diff(ptr))
+        order = np.argsort(src, kind="stable")
+        cptr = np.zeros(len(self.names) + 1, dtype=np.int64)
+        np.cumsum(np.bincount(src, minlength=len(self.names)), out=cptr[1:])
+        self._g = _DeviceGraph(cptr, nbr[order], device, options)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if getattr(self, "_g", None) is not None:
+            self._g.close()
+            self._g = None
+
+    def last_stats(self):
+        return self._g.last_stats()
+
+    def mapping_specificity(self, target_name, fill_na=True):
+        """Graph.get_mapping_specificity (nabo/_graph.py:794-824): {target node: mean hop distance over all pairs of
+        the reference nodes it is connected to}.  Matches the reference bit for bit, quirks included:
+
+          * the value is float64(sum of pair distances) / float64(number of pairs) -- equal to the reference's
+            float(np.mean(spls)), whose sum of integers is exact;
+          * a target node with fewer than 2 mapped reference nodes gets NaN;
+          * keys follow the target's node order in the file (HDF5 name order, `load_from_h5` :93-107);
+          * fill_na replaces NaN by Python's max(values): if the FIRST value is NaN that maximum is NaN and nothing is
+            filled; a target with no nodes raises ValueError as max() of nothing does;
+          * an unreachable pair raises ValueError naming both nodes (the reference raises networkx.NetworkXNoPath);
+          * an unknown target raises KeyError."""
+        import h5py
+        with h5py.File(self.fn, "r") as h5:
+            t_nodes, ptr, nbr = _target_rows(h5, target_name, self.pos)
+        return _specificity(self._g, self.names, t_nodes, ptr, nbr, fill_na)
+
+    def ref_specificity(self, target, target_values, incl_unmapped=False):
+        """Graph.get_ref_specificity (nabo/_graph.py:826-857): {reference node: mean of target_values over the nodes
+        of `target` mapped to it}.  Keys in the reference's node order (the file's); each node's values in the order
+        networkx lists its neighbours (the target's node order), so the mean is np.mean of the same list, bit for bit;
+        a node with one mapped target node gets that value as is, one with none is left out (or 0 with
+        incl_unmapped).  A target node missing from target_values raises KeyError.  The reference selects neighbours
+        whose NAME ends with `target`, so a reference neighbour or another sample's node named that way would also
+        be picked up; here only the nodes of sample `target` count.  Host code: no GPU is used."""
+        import h5py
+        with h5py.File(self.fn, "r") as h5:
+            return _ref_specificity(h5, self.ref_name, target, target_values, incl_unmapped)
+
+    def contiguous_spl(self, nodes):
+        """Graph.calc_contiguous_spl (nabo/_graph.py:904-916): mean hop distance between consecutive nodes of the list
+        (node names).  Fewer than 2 nodes give NaN (np.mean of nothing); an unknown node raises KeyError; an
+        unreachable pair raises ValueError (the reference: networkx.NodeNotFound / NetworkXNoPath)."""
+        return _contiguous(self._g, self.names, [self.pos[n] for n in nodes])
+
+
+def get_mapping_specificity(mapping_h5_fn, ref_name, target_name, fill_na=True, device=0):
+    """Graph.get_mapping_specificity from the mapping file (`mapping_h5_fn, ref_name` stand for the Graph object);
+    see RefGraph.mapping_specificity."""
+    with RefGraph(mapping_h5_fn, ref_name, device) as g:
+        return g.mapping_specificity(target_name, fill_na)
+
+
+def get_ref_specificity(mapping_h5_fn, ref_name, target, target_values, incl_unmapped=False):
+    """Graph.get_ref_specificity from the mapping file; see RefGraph.ref_specificity (host code, no GPU)."""
+    import h5py
+    with h5py.File(mapping_h5_fn, "r") as h5:
+        return _ref_specificity(h5, ref_name, target, target_values, incl_unmapped)
+
+
+def calc_contiguous_spl(mapping_h5_fn, ref_name, nodes, device=0):
+    """Graph.calc_contiguous_spl from the mapping file; see RefGraph.contiguous_spl."""
+    with RefGraph(mapping_h5_fn, ref_name, device) as g:
+        return g.contiguous_spl(nodes)
