@@ -26,7 +26,8 @@ FILE_FLAGS = {"l2_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-na
               # needs no NaN canonicalisation (two v_max per row-block otherwise)
               "l2c_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
               "canberra_f32.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]}
-HEADERS = [os.path.join(CSRC, "knn_common.h"), os.path.join(CSRC, "topk_lists.h"), os.path.join(HERE, "..", "include", "nabo_knn.h"), os.path.join(HERE, "..", "include", "nabo_graph.h")]
+HEADERS = [os.path.join(CSRC, "knn_common.h"), os.path.join(CSRC, "topk_lists.h"), os.path.join(CSRC, "launch.h"),
+           os.path.join(CSRC, "host_common.h"), os.path.join(HERE, "..", "include", "nabo_knn.h"), os.path.join(HERE, "..", "include", "nabo_graph.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "--offload-arch=" + ARCH, "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-Wno-inline-asm"]

@@ -12,188 +12,14 @@
 #include <vector>
 
 #include "../../include/nabo_knn.h"
+#include "host_common.h"
 #include "knn_common.h"
 
-namespace nabo {
-// kernels (pack.hip, l2_topk.hip, refine.hip, canberra.hip)
-hipError_t centre_launch(const double *Y, int64_t n, int g, double *centre, hipStream_t st);
-hipError_t pack_ref_launch(const double *Y, int64_t n, int g, const double *centre, double scale, int ksteps, int64_t ntiles_total,
-                           const uint8_t *mask, float *out, unsigned int *norm_max_bits, hipStream_t st);
-hipError_t pack_query_launch(const double *X, int64_t m, int g, const double *centre, double scale, int ksteps,
-                             int64_t ntiles_total, float *out, double *xnorm, hipStream_t st);
-hipError_t l2_topk_launch(int ksteps, int epl, const float *Xpk, const float *Ypk, int tiles_per_split, int S, int gx,
-                          int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
-                          hipStream_t st);
-void l2_topk_geometry(int ksteps, int epl, int *rows_per_wg, int *wg_per_cu, int *lkeep_max);
-// f16 operands of the matrix-pipe filters (pack.hip): K-concatenated tiles, nseg = 3 the f16x3 split, 1 the one-product form
-hipError_t maxabs_launch(const double *V, int64_t n, int g, const double *centre, unsigned long long *out_bits, hipStream_t st);
-hipError_t pack_cref_launch(const double *Y, int64_t n, int g, const double *centre, double scale, int kc,
-                            int64_t ntiles_total, const uint8_t *mask, unsigned char *out, unsigned int *norm_max_bits,
-                            bool layout16, hipStream_t st, const uint32_t *perm = nullptr, int nseg = 3);
-hipError_t pack_cquery_launch(const double *X, int64_t m, int g, const double *centre, double scale, int kc,
-                              int64_t ntiles_total, unsigned char *out, double *xnorm, bool layout16, hipStream_t st,
-                              const uint32_t *perm = nullptr, int nseg = 3);
-int l2q_pick_kc(int g);
-// the one-product first pass (l2c_topk.hip; operands packed with layout16, nseg = 1)
-hipError_t l2c_topk_launch(int kc, int geo, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
-                           int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
-                           int64_t pad_tile, hipStream_t st, int64_t rows_valid, const float *tau_init, int tau_stride = 0,
-                           int64_t tau_row0 = 0, const L2cPieces *pieces = nullptr);
-// tournament seeds for the one-product pass (l2c_topk.hip: l2c_pre_kernel)
-void l2c_pre_plan(int kc, int lkeep, int tiles_per_split, int scale_pct, int *pre_tiles, int *gt);
-hipError_t l2c_pre_launch(int kc, int lkeep, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
-                          int64_t rows, int64_t tile_off, int pre_tiles, int gt, int64_t pad_tile, hipStream_t st,
-                          int64_t rows_valid, float *tau_out, const int *ranges = nullptr, int rows_per_col = 0);
-hipError_t merge_lists_launch(const uint32_t *cand_idx, const float *cand_key, const float *cand_tau, int64_t rows, int S, int L,
-                              int lkeep, int Lout, uint32_t *out_idx, float *out_tau, hipStream_t st);
-int l2c_pick_kc(int g);
-int l2c_geometry(int kc, int lkeep_want, int pin);
-void l2c_topk_geometry(int kc, int lkeep_want, int pin, int *rows_per_wg, int *wg_per_cu, int *lkeep_max);
-// the same filter on v_mfma_f32_16x16x32_f16 (l2q_topk.hip; operands packed with layout16)
-hipError_t l2q_topk_launch(int kc, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
-                           int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
-                           int64_t pad_tile, hipStream_t st, const int32_t *wave_start = nullptr);
-void l2q_topk_geometry(int kc, int *rows_per_wg, int *wg_per_cu, int *lkeep_max);
-hipError_t pairwise_launch(const double *X, int64_t m, const double *Y, int64_t n, int g, int metric, double f,
-                           double *D, hipStream_t st);
-hipError_t refine_launch(const double *X, int64_t row0, int64_t m, const double *Y, int g, const uint32_t *cand_idx,
-                         const float *cand_tau, int S, int L, const double *xnorm, double err_coef, double ymax_sqrt,
-                         double tau_scale, int k, int drop, int64_t base, int64_t n_valid_total, const uint32_t *masked_list,
-                         int n_masked_list, int64_t *out_idx, double *out_dist, uint32_t *fail_rows,
-                         unsigned int *fail_count, hipStream_t st, int metric = 0, double cb_f = 0.0,
-                         float cb_plateau = 0.0f, int lvalid = 0, const uint32_t *rperm = nullptr,
-                         const uint32_t *tperm = nullptr, float *fail_seed = nullptr);
-hipError_t refine_cand_launch(const double *X, int64_t row0, int64_t m, const double *Y, int g, const uint32_t *cand_idx,
-                              const float *cand_tau, int S, int L, const double *xnorm, double err_coef,
-                              double ymax_sqrt, double tau_scale, int kout, int64_t base, int64_t n_valid_total,
-                              int64_t *out_idx, double *out_dist, double *out_bound, hipStream_t st, int metric = 0,
-                              int lvalid = 0, const uint32_t *rperm = nullptr, const uint32_t *tperm = nullptr);
-hipError_t normalise_rows_launch(const double *X, int64_t m, int g, double *out, hipStream_t st);
-hipError_t exact_rows_launch(const double *X, const double *Y, int64_t n, int g, int metric, double f,
-                             const uint8_t *mask, const uint32_t *rows, unsigned int nrows, int k, int drop,
-                             int64_t base, const uint32_t *masked_list, int n_masked_list, int64_t *out_idx,
-                             double *out_dist, double *D, unsigned int d_rows, hipStream_t st);
-hipError_t masked_tail_launch(const double *X, int64_t m, const double *Y, int g, int metric, double f,
-                              const uint32_t *masked_list, int n_masked_list, int n_valid, int k, int drop,
-                              int64_t base, int64_t *out_idx, double *out_dist, hipStream_t st);
-hipError_t transpose_ref_launch(const double *Y, int64_t n, int g, double *Yt, hipStream_t st);
-hipError_t canberra_topk_launch(int epl, const double *X, int64_t m, const double *Yt, int64_t n, int g, double f,
-                                const uint8_t *mask, int S, double *cand_d, uint32_t *cand_i, hipStream_t st);
-hipError_t merge_local_launch(const double *cand_d, const uint32_t *cand_i, int64_t m, int P, int k, int drop,
-                              int64_t base, int64_t *out_idx, double *out_dist, int *n_found, hipStream_t st);
-hipError_t merge_parts_launch(const double *parts_d, const int64_t *parts_i, int n_parts, int64_t m, int kp, int k,
-                              int drop, int64_t *out_idx, double *out_dist, hipStream_t st);
-// fp32 lower-bound Canberra filter (canberra_f32.hip) + helpers (refine.hip)
-hipError_t cbf_pack_targets_launch(const double *X, int64_t m, int g, int gp, double f, float *xq, unsigned int *flag,
-                                   hipStream_t st);
-hipError_t cbf_pack_refs_launch(const double *Y, int64_t n, int g, int gp, float *ycf, unsigned int *flag,
-                                hipStream_t st);
-int cbf_pick_gp(int g);
-void cbf_constants(int g, float *slack, float *plateau);
-int cbf_lists_per_split();
-int cbf_rows_per_wg(int epl);
-hipError_t cbf_filter_launch(int gp, int epl, const float *xq, const void *xh, int64_t m, const float *ycf,
-                             const void *ych, int64_t n, int g, const uint8_t *mask, int S, uint32_t *cand_idx,
-                             float *cand_tau, hipStream_t st);
-hipError_t cbf_pack_refs_rows_launch(const double *Y, int64_t n, int g, int gp, float *yrow, hipStream_t st);
-hipError_t cbf_colminmax_launch(const double *Y, int64_t n, int g, unsigned int *colmm, hipStream_t st);
-hipError_t cbf_pack_refs8_launch(const double *Y, int64_t n, int g, int gp, const double *quant, void *ych, hipStream_t st);
-hipError_t cbf_pack_targets8_launch(const double *X, int64_t m, int g, int gp, double f, const double *quant, void *xh,
-                                    hipStream_t st);
-// the counting pass on per-bucket bitmaps (canberra_bits.hip)
-int cbb_buckets();
-int cbb_rows_per_wg();
-bool cbb_available(int g, int gp, int epl);
-size_t cbb_table_bytes(int64_t n, int g);
-size_t cbb_valid_bytes(int64_t n);
-hipError_t cbb_pack_table_launch(const double *Y, int64_t n, int g, const double *edges, uint32_t *tab, hipStream_t st);
-hipError_t cbb_valid_launch(const uint8_t *mask, int64_t n, uint32_t *vbits, hipStream_t st);
-hipError_t cbb_pack_targets_launch(const double *X, int64_t m, int g, int gp, double f, const double *edges, uint16_t *rowoff,
-                                   hipStream_t st);
-hipError_t cbb_filter_launch(int gp, const float *xq, const uint16_t *rowoff, int64_t m, const float *yrow, const uint32_t *tab,
-                             const uint32_t *vbits, int64_t n, int g, int S, uint32_t *cand_idx, float *cand_tau, hipStream_t st);
-hipError_t gather_rows_launch(const double *X, const uint32_t *rows, int64_t nrows, int g, double *out, hipStream_t st);
-hipError_t iota_launch(uint32_t *out, int64_t n, hipStream_t st);
-hipError_t scatter_rows_launch(const int64_t *si, const double *sd, const uint32_t *rows, int64_t nrows, int k,
-                               int64_t *out_idx, double *out_dist, hipStream_t st);
-hipError_t null_hist_launch(int64_t n_t, int P, uint64_t seed, int key_bits, const uint64_t *prefix, int done_bits,
-                            unsigned int *hist, hipStream_t st);
-hipError_t null_label_launch(int64_t n_t, int P, int W, uint64_t seed, int key_bits, const uint64_t *thr,
-                             const uint8_t *group, uint32_t *bits, hipStream_t st);
-hipError_t null_score_launch(int64_t n_ref, const int64_t *row_ptr, const int64_t *edge_t, const double *edge_w, int P,
-                             int W, const uint32_t *bits, const int64_t *n_lab, int64_t n_a, double mult,
-                             double *out_obs, int64_t *out_nge, double *out_mean, double *out_sd, hipStream_t st);
-hipError_t snn_counts_launch(const int64_t *t_idx, int64_t m, const int64_t *r_idx, int64_t n, int k, int32_t *out,
-                             hipStream_t st);
-hipError_t csr_sort_temp_bytes(int64_t E, int64_t n_ref, size_t *bytes);
-hipError_t csr_build_launch(const int64_t *edge_r, const int64_t *edge_t, const double *edge_w, int64_t E, int64_t n_ref,
-                            int64_t n_t, uint32_t *keys_a, uint32_t *pos_a, uint32_t *keys_b, uint32_t *pos_b, void *temp,
-                            size_t temp_bytes, int64_t *row_ptr, int64_t *out_t, double *out_w, unsigned int *flag,
-                            hipStream_t st);
-}  // namespace nabo
+using nabo::api_fail;
+using nabo::DevBuf;
+using nabo::use_device;
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e__ = (expr);                                                               \
-        if (e__ != hipSuccess) {                                                               \
-            (void)hipGetLastError(); /* (the thread's sticky copy: a later launch check must not report THIS failure) */ \
-            return fail(e__ == hipErrorOutOfMemory ? NABO_E_NOMEM : NABO_E_HIP, "%s failed: %s", \
-                        #expr, hipGetErrorString(e__));                                        \
-        }                                                                                      \
-    } while (0)
-
-int use_device(int device)
-{
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0)
-        return fail(NABO_E_NODEVICE, "no HIP device is available (libnabo_knn has no CPU fallback)");
-    if (device < 0 || device >= cnt) return fail(NABO_E_NODEVICE, "device %d out of range (have %d)", device, cnt);
-    HIP_TRY(hipSetDevice(device));
-    return NABO_OK;
-}
-
-// grow-only device buffer; owns its allocation (freed by release() or with the object: `delete ix` cannot miss a member)
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    int reserve(size_t bytes)
-    {
-        if (bytes <= cap) return NABO_OK;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return fail(NABO_E_NOMEM, "hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
-        }
-        cap = want;
-        return NABO_OK;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
 
 int pick_ksteps(int g)
 {
@@ -363,15 +189,6 @@ struct nabo_index {
 };
 
 namespace nabo {
-// for sharded.hip (same library, other translation unit)
-int api_fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 int index_device(const nabo_index *ix) { return ix->device; }
 int index_g(const nabo_index *ix) { return ix->g; }
 int64_t index_n(const nabo_index *ix) { return ix->n; }
@@ -518,6 +335,17 @@ static int apply_mask(nabo_index *ix, const uint8_t *ref_mask)
     return NABO_OK;
 }
 
+static thread_local char g_err[512] = "";      // nabo_last_error(): this thread's last message
+
+int nabo::api_fail(int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
 extern "C" {
 
 const char *nabo_version(void) { return "nabo_knn 0.1 (gfx950)"; }
@@ -533,22 +361,22 @@ int nabo_device_count(void)
 int nabo_index_create(nabo_index **out, int32_t device, int64_t n_ref, int32_t g, int32_t metric,
                       double dist_factor, int64_t ref_index_base)
 {
-    if (!out) return fail(NABO_E_INVALID, "out is NULL");
+    if (!out) return api_fail(NABO_E_INVALID, "out is NULL");
     *out = nullptr;
-    if (n_ref < 1 || n_ref >= 0xFFFFFFF0ll) return fail(NABO_E_INVALID, "n_ref=%lld out of range", (long long)n_ref);
-    if (g < 1) return fail(NABO_E_INVALID, "g=%d must be >= 1", g);
+    if (n_ref < 1 || n_ref >= 0xFFFFFFF0ll) return api_fail(NABO_E_INVALID, "n_ref=%lld out of range", (long long)n_ref);
+    if (g < 1) return api_fail(NABO_E_INVALID, "g=%d must be >= 1", g);
     if (metric != NABO_METRIC_EUCLIDEAN && metric != NABO_METRIC_MOD_CANBERRA && metric != NABO_METRIC_COSINE)
-        return fail(NABO_E_INVALID, "unknown metric %d", metric);
+        return api_fail(NABO_E_INVALID, "unknown metric %d", metric);
     if (metric == NABO_METRIC_MOD_CANBERRA && !(dist_factor > 0))
-        return fail(NABO_E_INVALID, "dist_factor must be > 0");          // nabo/_mapping.py:516-521
-    if (ref_index_base < 0) return fail(NABO_E_INVALID, "ref_index_base must be >= 0");
+        return api_fail(NABO_E_INVALID, "dist_factor must be > 0");          // nabo/_mapping.py:516-521
+    if (ref_index_base < 0) return api_fail(NABO_E_INVALID, "ref_index_base must be >= 0");
     // the shard merge carries global indices as 32-bit payloads (0xFFFFFFFF = absent)
     if (ref_index_base + n_ref > 0xFFFFFFFEll)
-        return fail(NABO_E_UNSUPPORTED, "ref_index_base + n_ref = %lld exceeds 2^32 - 2", (long long)(ref_index_base + n_ref));
+        return api_fail(NABO_E_UNSUPPORTED, "ref_index_base + n_ref = %lld exceeds 2^32 - 2", (long long)(ref_index_base + n_ref));
     int rc = use_device(device);
     if (rc) return rc;
     nabo_index *ix = new (std::nothrow) nabo_index();
-    if (!ix) return fail(NABO_E_NOMEM, "host allocation failed");
+    if (!ix) return api_fail(NABO_E_NOMEM, "host allocation failed");
     ix->device = device;
     ix->n = n_ref;
     ix->g = g;
@@ -573,7 +401,7 @@ int nabo_index_create(nabo_index **out, int32_t device, int64_t n_ref, int32_t g
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ix->ev_ref, hipEventDisableTiming);
     if (e != hipSuccess) {
         nabo_index_destroy(ix);
-        return fail(NABO_E_HIP, "stream/event creation failed: %s", hipGetErrorString(e));
+        return api_fail(NABO_E_HIP, "stream/event creation failed: %s", hipGetErrorString(e));
     }
     *out = ix;
     return NABO_OK;
@@ -581,12 +409,12 @@ int nabo_index_create(nabo_index **out, int32_t device, int64_t n_ref, int32_t g
 
 int nabo_index_set_option(nabo_index *ix, const char *name, int64_t value)
 {
-    if (!ix || !name) return fail(NABO_E_INVALID, "NULL argument");
-    if (ix->async_busy) return fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
-    if (!option_set(ix->opt, name, value)) return fail(NABO_E_INVALID, "unknown option '%s'", name);
+    if (!ix || !name) return api_fail(NABO_E_INVALID, "NULL argument");
+    if (ix->async_busy) return api_fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
+    if (!option_set(ix->opt, name, value)) return api_fail(NABO_E_INVALID, "unknown option '%s'", name);
     if (strcmp(name, "order_flags") == 0) {      // (locality-ordered streaming was measured slower and removed)
         ix->opt.order_flags = 0;
-        return fail(NABO_E_UNSUPPORTED, "option '%s' (locality-ordered streaming, once in experiments builds only) was removed", name);
+        return api_fail(NABO_E_UNSUPPORTED, "option '%s' (locality-ordered streaming, once in experiments builds only) was removed", name);
     }
     return NABO_OK;
 }
@@ -609,8 +437,8 @@ int nabo_index_destroy(nabo_index *ix)
 
 int nabo_index_set_ref(nabo_index *ix, const double *Y, int32_t y_on_device, const uint8_t *ref_mask)
 {
-    if (!ix || !Y) return fail(NABO_E_INVALID, "NULL argument");
-    if (ix->async_busy) return fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
+    if (!ix || !Y) return api_fail(NABO_E_INVALID, "NULL argument");
+    if (ix->async_busy) return api_fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
     int rc = use_device(ix->device);
     if (rc) return rc;
     hipStream_t st = ix->stream;
@@ -769,9 +597,9 @@ int nabo_index_set_ref(nabo_index *ix, const double *Y, int32_t y_on_device, con
 
 int nabo_index_set_mask(nabo_index *ix, const uint8_t *ref_mask)
 {
-    if (!ix) return fail(NABO_E_INVALID, "NULL index");
-    if (ix->async_busy) return fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
-    if (!ix->have_ref) return fail(NABO_E_INVALID, "nabo_index_set_ref has not been called");
+    if (!ix) return api_fail(NABO_E_INVALID, "NULL index");
+    if (ix->async_busy) return api_fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
+    if (!ix->have_ref) return api_fail(NABO_E_INVALID, "nabo_index_set_ref has not been called");
     int rc = use_device(ix->device);
     if (rc) return rc;
     if ((rc = apply_mask(ix, ref_mask))) return rc;
@@ -973,14 +801,14 @@ static int plan_l2(const nabo_index *ix, int64_t m, int k, int drop, bool cand_m
         if (split_refs < 64 || split_refs > NABO_LIST_SPLIT_REFS) split_refs = NABO_LIST_SPLIT_REFS;
         const int64_t split_tiles = (split_refs - 1) / 32;
         const int64_t s_min = (ix->ref_tiles + split_tiles - 1) / split_tiles;
-        if (s_min > 1024 / L) return fail(NABO_E_INVALID, "more than 2^25 x (1024 / list length) reference cells in one index");
+        if (s_min > 1024 / L) return api_fail(NABO_E_INVALID, "more than 2^25 x (1024 / list length) reference cells in one index");
         if (S < s_min) S = (int)s_min;
         if (gx_tail > 0 && S2 < s_min) S2 = (int)s_min;
     }
     const int64_t tps = (ix->ref_tiles + S - 1) / S;
     const int64_t tps2 = (ix->ref_tiles + S2 - 1) / S2;
     if (tps * S > ix->ref_tiles_alloc || tps2 * S2 > ix->ref_tiles_alloc)
-        return fail(NABO_E_INVALID, "internal: split padding exceeds allocation");
+        return api_fail(NABO_E_INVALID, "internal: split padding exceeds allocation");
 
     P->epl = epl; P->L = L;
     P->use_h = use_h; P->use_1 = use_1; P->on_l2c = on_l2c; P->r1 = r1;
@@ -1006,7 +834,7 @@ static int query_body(nabo_index *ix, const double *X, int32_t x_on_device, int6
 static int query_impl(nabo_index *ix, const double *X, int32_t x_on_device, int64_t m, int32_t k, int32_t drop_first,
                       int64_t *out_idx, double *out_dist, int32_t out_on_device, bool cand_mode, double *out_bound)
 {
-    if (!ix) return fail(NABO_E_INVALID, "NULL argument");
+    if (!ix) return api_fail(NABO_E_INVALID, "NULL argument");
     if (ix->depth == 0) {                            // a top-level query: the per-row record starts over
         ix->row_pass.clear();
         ix->row_map = nullptr;
@@ -1053,7 +881,7 @@ static int query_exact(nabo_index *ix, Query &q)
     int rc;
     unsigned int d_rows = 0;
     if (q.top) ix->row_pass.assign((size_t)q.m, (uint8_t)NABO_PASS_EXACT);
-    if (q.m > 0xFFFFFFF0ll) return fail(NABO_E_UNSUPPORTED, "m=%lld: fewer than 2^32-16 rows per call", (long long)q.m);
+    if (q.m > 0xFFFFFFF0ll) return api_fail(NABO_E_UNSUPPORTED, "m=%lld: fewer than 2^32-16 rows per call", (long long)q.m);
     if ((rc = ix->fails.reserve((size_t)q.m * sizeof(uint32_t)))) return rc;
     if ((rc = reserve_exact_ws(ix, (uint64_t)q.m, 65528, &d_rows))) return rc;
     HIP_TRY(nabo::iota_launch(ix->fails.as<uint32_t>(), q.m, st));
@@ -1596,22 +1424,22 @@ static int finish_query(nabo_index *ix, const Query &q, int64_t *out_idx, double
 static int query_body(nabo_index *ix, const double *X, int32_t x_on_device, int64_t m, int32_t k, int32_t drop_first,
                       int64_t *out_idx, double *out_dist, int32_t out_on_device, bool cand_mode, double *out_bound)
 {
-    if (!ix || !X || !out_idx || !out_dist) return fail(NABO_E_INVALID, "NULL argument");
-    if (!ix->have_ref) return fail(NABO_E_INVALID, "nabo_index_set_ref has not been called");
-    if (m < 0) return fail(NABO_E_INVALID, "m=%lld must be >= 0", (long long)m);
+    if (!ix || !X || !out_idx || !out_dist) return api_fail(NABO_E_INVALID, "NULL argument");
+    if (!ix->have_ref) return api_fail(NABO_E_INVALID, "nabo_index_set_ref has not been called");
+    if (m < 0) return api_fail(NABO_E_INVALID, "m=%lld must be >= 0", (long long)m);
     if (m == 0) return NABO_OK;                      // no target cells: nothing to do (reference loops are empty)
     const int drop = drop_first ? 1 : 0;
     const int kk = k + drop;
-    if (k < 1) return fail(NABO_E_INVALID, "k=%d must be >= 1", k);
+    if (k < 1) return api_fail(NABO_E_INVALID, "k=%d must be >= 1", k);
     if (kk > ix->n && !cand_mode)
-        return fail(NABO_E_INVALID, "k + drop_first = %d exceeds the %lld references", kk, (long long)ix->n);
+        return api_fail(NABO_E_INVALID, "k + drop_first = %d exceeds the %lld references", kk, (long long)ix->n);
     if (cand_mode && (ix->metric == NABO_METRIC_MOD_CANBERRA || !out_bound || !out_on_device || k > 32))
-        return fail(NABO_E_INVALID, "candidate mode: Euclidean or cosine metric, device outputs, <= 32 candidates");
+        return api_fail(NABO_E_INVALID, "candidate mode: Euclidean or cosine metric, device outputs, <= 32 candidates");
     // Shapes outside the instantiated filter kernels (k' > NABO_MAX_K, g > NABO_MAX_COMPS) are answered by the exact
     // float64 kernels for every row: the reference accepts any k / use_comps (nabo/_mapping.py:495-524).
     const bool exact_route = kk > NABO_MAX_K || (ix->metric != NABO_METRIC_MOD_CANBERRA && ix->ksteps < 0);
     if (exact_route && cand_mode)
-        return fail(NABO_E_UNSUPPORTED, "candidate mode needs g <= %d (got %d)", NABO_MAX_COMPS, ix->g);
+        return api_fail(NABO_E_UNSUPPORTED, "candidate mode needs g <= %d (got %d)", NABO_MAX_COMPS, ix->g);
     int rc = use_device(ix->device);
     if (rc) return rc;
     hipStream_t st = ix->stream;
@@ -1653,15 +1481,15 @@ static void async_join(nabo_index *ix)
 int nabo_index_query(nabo_index *ix, const double *X, int32_t x_on_device, int64_t m, int32_t k,
                      int32_t drop_first, int64_t *out_idx, double *out_dist, int32_t out_on_device)
 {
-    if (ix && ix->async_busy) return fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
+    if (ix && ix->async_busy) return api_fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
     return query_impl(ix, X, x_on_device, m, k, drop_first, out_idx, out_dist, out_on_device, false, nullptr);
 }
 
 int nabo_index_query_async(nabo_index *ix, const double *X, int32_t x_on_device, int64_t m, int32_t k,
                            int32_t drop_first, int64_t *out_idx, double *out_dist, int32_t out_on_device)
 {
-    if (!ix) return fail(NABO_E_INVALID, "NULL argument");
-    if (ix->async_busy) return fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
+    if (!ix) return api_fail(NABO_E_INVALID, "NULL argument");
+    if (ix->async_busy) return api_fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
     async_join(ix);
     ix->async_busy = true;
     ix->async_rc = NABO_OK;
@@ -1674,30 +1502,30 @@ int nabo_index_query_async(nabo_index *ix, const double *X, int32_t x_on_device,
         });
     } catch (...) {
         ix->async_busy = false;
-        return fail(NABO_E_NOMEM, "could not start the query's host thread");
+        return api_fail(NABO_E_NOMEM, "could not start the query's host thread");
     }
     return NABO_OK;
 }
 
 int nabo_index_query_wait(nabo_index *ix)
 {
-    if (!ix) return fail(NABO_E_INVALID, "NULL argument");
+    if (!ix) return api_fail(NABO_E_INVALID, "NULL argument");
     if (!ix->async_busy) return NABO_OK;
     async_join(ix);
     ix->async_busy = false;
-    return ix->async_rc ? fail(ix->async_rc, "%s", ix->async_msg) : NABO_OK;
+    return ix->async_rc ? api_fail(ix->async_rc, "%s", ix->async_msg) : NABO_OK;
 }
 
 int nabo_index_query_candidates(nabo_index *ix, const double *X, int32_t x_on_device, int64_t m, int32_t n_cand,
                                 int64_t *out_idx, double *out_dist, double *out_bound)
 {
-    if (ix && ix->async_busy) return fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
+    if (ix && ix->async_busy) return api_fail(NABO_E_INVALID, "an asynchronous query is in flight on this index: nabo_index_query_wait first");
     return query_impl(ix, X, x_on_device, m, n_cand, 0, out_idx, out_dist, 1, true, out_bound);
 }
 
 int nabo_index_last_stats(const nabo_index *ix, double ms[5], int64_t counters[4])
 {
-    if (!ix) return fail(NABO_E_INVALID, "NULL index");
+    if (!ix) return api_fail(NABO_E_INVALID, "NULL index");
     if (ms) memcpy(ms, ix->ms, sizeof(ix->ms));
     if (counters) memcpy(counters, ix->counters, sizeof(ix->counters));
     return NABO_OK;
@@ -1705,7 +1533,7 @@ int nabo_index_last_stats(const nabo_index *ix, double ms[5], int64_t counters[4
 
 int nabo_index_last_passes(const nabo_index *ix, int64_t rows[3])
 {
-    if (!ix || !rows) return fail(NABO_E_INVALID, "NULL argument");
+    if (!ix || !rows) return api_fail(NABO_E_INVALID, "NULL argument");
     rows[0] = ix->pass_rows[0];
     rows[1] = ix->pass_rows[1];
     rows[2] = ix->pass_rows[2];
@@ -1716,10 +1544,10 @@ int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t
                     int32_t n_cu, const char *l2_mode, const char *options, int64_t out[NABO_PLAN_FIELDS], char *kernel,
                     size_t kernel_len)
 {
-    if (!out) return fail(NABO_E_INVALID, "NULL argument");
-    if (n_ref < 1 || g < 1 || m < 1 || k < 1 || n_cu < 1) return fail(NABO_E_INVALID, "bad shape");
+    if (!out) return api_fail(NABO_E_INVALID, "NULL argument");
+    if (n_ref < 1 || g < 1 || m < 1 || k < 1 || n_cu < 1) return api_fail(NABO_E_INVALID, "bad shape");
     if (metric != NABO_METRIC_EUCLIDEAN && metric != NABO_METRIC_COSINE)
-        return fail(NABO_E_UNSUPPORTED, "nabo_query_plan describes the Euclidean / cosine filter launches");
+        return api_fail(NABO_E_UNSUPPORTED, "nabo_query_plan describes the Euclidean / cosine filter launches");
     nabo_index ix;                                   // a shape, never a device object: nothing here touches HIP
     ix.n = n_ref;
     ix.g = g;
@@ -1730,9 +1558,9 @@ int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t
         snprintf(buf, sizeof(buf), "%s", options);
         for (char *tok = strtok(buf, ","); tok; tok = strtok(nullptr, ",")) {
             char *eq = strchr(tok, '=');
-            if (!eq) return fail(NABO_E_INVALID, "option '%s': expected name=value", tok);
+            if (!eq) return api_fail(NABO_E_INVALID, "option '%s': expected name=value", tok);
             *eq = 0;
-            if (!option_set(ix.opt, tok, atoll(eq + 1))) return fail(NABO_E_INVALID, "unknown option '%s'", tok);
+            if (!option_set(ix.opt, tok, atoll(eq + 1))) return api_fail(NABO_E_INVALID, "unknown option '%s'", tok);
         }
     }
     index_init_filters(&ix, (l2_mode && *l2_mode) ? l2_mode : nullptr);
@@ -1775,17 +1603,17 @@ int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t
 
 int nabo_index_last_row_pass(const nabo_index *ix, uint8_t *out, int64_t m)
 {
-    if (!ix || !out) return fail(NABO_E_INVALID, "NULL argument");
+    if (!ix || !out) return api_fail(NABO_E_INVALID, "NULL argument");
     if ((int64_t)ix->row_pass.size() != m)
-        return fail(NABO_E_INVALID, "the last nabo_index_query on this index had %lld rows, not %lld (candidate queries keep no record)",
-                    (long long)ix->row_pass.size(), (long long)m);
+        return api_fail(NABO_E_INVALID, "the last nabo_index_query on this index had %lld rows, not %lld (candidate queries keep no record)",
+                        (long long)ix->row_pass.size(), (long long)m);
     if (m > 0) memcpy(out, ix->row_pass.data(), (size_t)m);
     return NABO_OK;
 }
 
 int nabo_index_last_kernel(const nabo_index *ix, char *buf, size_t n)
 {
-    if (!ix || !buf || n == 0) return fail(NABO_E_INVALID, "NULL argument");
+    if (!ix || !buf || n == 0) return api_fail(NABO_E_INVALID, "NULL argument");
     snprintf(buf, n, "%s", ix->kernel);
     return NABO_OK;
 }
@@ -1794,7 +1622,7 @@ int nabo_knn(const double *X, int64_t m, const double *Y, int64_t n, int32_t g, 
              double dist_factor, const uint8_t *ref_mask, int32_t drop_first, int64_t *out_idx, double *out_dist,
              int32_t device)
 {
-    if (!X || !Y || !out_idx || !out_dist) return fail(NABO_E_INVALID, "NULL argument");
+    if (!X || !Y || !out_idx || !out_dist) return api_fail(NABO_E_INVALID, "NULL argument");
     nabo_index *ix = nullptr;
     int rc = nabo_index_create(&ix, device, n, g, metric, dist_factor, 0);
     if (rc) return rc;
@@ -1807,11 +1635,11 @@ int nabo_knn(const double *X, int64_t m, const double *Y, int64_t n, int32_t g, 
 int nabo_pairwise(const double *X, int64_t m, const double *Y, int64_t n, int32_t g, int32_t metric,
                   double dist_factor, double *D, int32_t device)
 {
-    if (!X || !Y || !D) return fail(NABO_E_INVALID, "NULL argument");
-    if (m < 1 || n < 1 || g < 1) return fail(NABO_E_INVALID, "empty operand");
+    if (!X || !Y || !D) return api_fail(NABO_E_INVALID, "NULL argument");
+    if (m < 1 || n < 1 || g < 1) return api_fail(NABO_E_INVALID, "empty operand");
     if (metric != NABO_METRIC_EUCLIDEAN && metric != NABO_METRIC_MOD_CANBERRA && metric != NABO_METRIC_COSINE)
-        return fail(NABO_E_INVALID, "unknown metric %d", metric);
-    if (m > 65535) return fail(NABO_E_UNSUPPORTED, "nabo_pairwise is the tile-sized seam: m <= 65535");
+        return api_fail(NABO_E_INVALID, "unknown metric %d", metric);
+    if (m > 65535) return api_fail(NABO_E_UNSUPPORTED, "nabo_pairwise is the tile-sized seam: m <= 65535");
     int rc = use_device(device);
     if (rc) return rc;
     DevBuf dx, dy, dd;
@@ -1826,18 +1654,18 @@ int nabo_pairwise(const double *X, int64_t m, const double *Y, int64_t n, int32_
                                                    dd.as<double>(), nullptr);
     if (e == hipSuccess) e = hipMemcpy(D, dd.p, db, hipMemcpyDeviceToHost);
     dx.release(); dy.release(); dd.release();
-    if (e != hipSuccess) return fail(NABO_E_HIP, "nabo_pairwise: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return api_fail(NABO_E_HIP, "nabo_pairwise: %s", hipGetErrorString(e));
     return NABO_OK;
 }
 
 int nabo_merge_topk(int32_t device, const int64_t *parts_idx, const double *parts_dist, int32_t n_parts, int64_t m,
                     int32_t kp, int32_t k, int32_t drop_first, int64_t *out_idx, double *out_dist)
 {
-    if (!parts_idx || !parts_dist || !out_idx || !out_dist) return fail(NABO_E_INVALID, "NULL argument");
+    if (!parts_idx || !parts_dist || !out_idx || !out_dist) return api_fail(NABO_E_INVALID, "NULL argument");
     const int drop = drop_first ? 1 : 0;
-    if (n_parts < 1 || m < 1 || kp < 1 || k < 1) return fail(NABO_E_INVALID, "bad shape");
-    if (k + drop > n_parts * kp) return fail(NABO_E_INVALID, "k + drop_first exceeds n_parts * kp");
-    if ((int64_t)n_parts * kp > 1024) return fail(NABO_E_UNSUPPORTED, "n_parts * kp > 1024");
+    if (n_parts < 1 || m < 1 || kp < 1 || k < 1) return api_fail(NABO_E_INVALID, "bad shape");
+    if (k + drop > n_parts * kp) return api_fail(NABO_E_INVALID, "k + drop_first exceeds n_parts * kp");
+    if ((int64_t)n_parts * kp > 1024) return api_fail(NABO_E_UNSUPPORTED, "n_parts * kp > 1024");
     int rc = use_device(device);
     if (rc) return rc;
     HIP_TRY(nabo::merge_parts_launch(parts_dist, parts_idx, n_parts, m, kp, k, drop, out_idx, out_dist, nullptr));
@@ -1848,8 +1676,8 @@ int nabo_merge_topk(int32_t device, const int64_t *parts_idx, const double *part
 int nabo_snn_counts(int32_t device, const int64_t *t_idx, int64_t m, const int64_t *r_idx, int64_t n, int32_t k,
                     int32_t *out_snn)
 {
-    if (!t_idx || !r_idx || !out_snn) return fail(NABO_E_INVALID, "NULL argument");
-    if (m < 1 || n < 1 || k < 1) return fail(NABO_E_INVALID, "bad shape");
+    if (!t_idx || !r_idx || !out_snn) return api_fail(NABO_E_INVALID, "NULL argument");
+    if (m < 1 || n < 1 || k < 1) return api_fail(NABO_E_INVALID, "bad shape");
     int rc = use_device(device);
     if (rc) return rc;
     HIP_TRY(nabo::snn_counts_launch(t_idx, m, r_idx, n, k, out_snn, nullptr));
@@ -1857,179 +1685,9 @@ int nabo_snn_counts(int32_t device, const int64_t *t_idx, int64_t m, const int64
     return NABO_OK;
 }
 
-// row_ptr != NULL: edges in CSR by reference node (edge_r unused); row_ptr == NULL: COO, E = n_edges, the CSR is built
-// on the device by a stable sort (csr_build.hip).
-static int score_null_impl(int32_t device, int64_t n_ref, const int64_t *row_ptr, int64_t n_edges, const int64_t *edge_r,
-                           const int64_t *edge_t, const double *edge_w, int64_t n_t, const uint8_t *group, int32_t n_perm,
-                           uint64_t seed, int32_t key_bits, double multiplier, double *out_obs, int64_t *out_nge,
-                           double *out_mean, double *out_sd, int64_t *out_sizes)
-{
-    const bool coo = row_ptr == nullptr;
-    if (!group || !out_obs || !out_nge || !out_mean || !out_sd) return fail(NABO_E_INVALID, "NULL argument");
-    if (n_ref < 1 || n_t < 1) return fail(NABO_E_INVALID, "empty operand");
-    if (n_perm < 1 || n_perm > 4096) return fail(NABO_E_UNSUPPORTED, "n_perm=%d: 1..4096 supported", n_perm);
-    if (key_bits < 8 || key_bits > 64 || key_bits % 8) return fail(NABO_E_INVALID, "key_bits must be 8, 16, .., 64");
-    if (n_ref >= 0x7FFFFFFFll) return fail(NABO_E_UNSUPPORTED, "n_ref too large for one launch");
-    const int64_t E = coo ? n_edges : row_ptr[n_ref];
-    if (coo) {
-        if (E < 0) return fail(NABO_E_INVALID, "n_edges < 0");
-        if (E >= 0xFFFFFFFFll) return fail(NABO_E_UNSUPPORTED, "n_edges=%lld: fewer than 2^32-1 supported", (long long)E);
-        if (E > 0 && !edge_r) return fail(NABO_E_INVALID, "NULL edge arrays");
-    } else {
-        if (row_ptr[0] != 0 || E < 0) return fail(NABO_E_INVALID, "row_ptr must start at 0");
-        for (int64_t r = 0; r < n_ref; ++r)
-            if (row_ptr[r + 1] < row_ptr[r]) return fail(NABO_E_INVALID, "row_ptr must be non-decreasing");
-        if (E > 0 && (!edge_t || !edge_w)) return fail(NABO_E_INVALID, "NULL edge arrays");
-        for (int64_t e = 0; e < E; ++e)
-            if (edge_t[e] < 0 || edge_t[e] >= n_t) return fail(NABO_E_INVALID, "edge_t[%lld] out of range", (long long)e);
-    }
-    if (E > 0 && (!edge_t || !edge_w)) return fail(NABO_E_INVALID, "NULL edge arrays");
-    int64_t n_a = 0;
-    for (int64_t t = 0; t < n_t; ++t) n_a += group[t] ? 1 : 0;
-    if (n_a < 1) return fail(NABO_E_INVALID, "the group of interest is empty");
-    int rc = use_device(device);
-    if (rc) return rc;
-    const int P = n_perm, W = (P + 1 + 31) / 32;
-    hipStream_t st = nullptr;
-    DevBuf d_rp, d_et, d_ew, d_grp, d_pre, d_hist, d_bits, d_nl, d_obs, d_nge, d_mean, d_sd;
-    DevBuf c_r, c_t, c_w, c_ka, c_kb, c_pa, c_pb, c_tmp, c_flag;          // COO staging + sort scratch
-    auto release = [&]() {
-        DevBuf *all[] = {&d_rp, &d_et, &d_ew, &d_grp, &d_pre, &d_hist, &d_bits, &d_nl, &d_obs, &d_nge, &d_mean, &d_sd,
-                         &c_r,  &c_t,  &c_w,  &c_ka,  &c_kb,  &c_pa,   &c_pb,   &c_tmp, &c_flag};
-        for (DevBuf *b : all) b->release();
-    };
-#define NS_TRY(expr)                                                                     \
-    do {                                                                                 \
-        hipError_t e__ = (expr);                                                         \
-        if (e__ != hipSuccess) {                                                         \
-            release();                                                                   \
-            return fail(e__ == hipErrorOutOfMemory ? NABO_E_NOMEM : NABO_E_HIP, "%s failed: %s", #expr, \
-                        hipGetErrorString(e__));                                         \
-        }                                                                                \
-    } while (0)
-#define NS_RES(buf, bytes)                         \
-    do {                                           \
-        if ((rc = (buf).reserve(bytes))) {         \
-            release();                             \
-            return rc;                             \
-        }                                          \
-    } while (0)
-    NS_RES(d_rp, (size_t)(n_ref + 1) * 8);
-    NS_RES(d_et, (size_t)(E ? E : 1) * 8);
-    NS_RES(d_ew, (size_t)(E ? E : 1) * 8);
-    NS_RES(d_grp, (size_t)n_t);
-    NS_RES(d_pre, (size_t)P * 8);
-    NS_RES(d_hist, (size_t)P * 256 * 4);
-    NS_RES(d_bits, (size_t)n_t * W * 4);
-    NS_RES(d_nl, (size_t)P * 8);
-    NS_RES(d_obs, (size_t)n_ref * 8);
-    NS_RES(d_nge, (size_t)n_ref * 8);
-    NS_RES(d_mean, (size_t)n_ref * 8);
-    NS_RES(d_sd, (size_t)n_ref * 8);
-    if (!coo) {
-        NS_TRY(hipMemcpyAsync(d_rp.p, row_ptr, (size_t)(n_ref + 1) * 8, hipMemcpyHostToDevice, st));
-        if (E) {
-            NS_TRY(hipMemcpyAsync(d_et.p, edge_t, (size_t)E * 8, hipMemcpyHostToDevice, st));
-            NS_TRY(hipMemcpyAsync(d_ew.p, edge_w, (size_t)E * 8, hipMemcpyHostToDevice, st));
-        }
-    } else {
-        size_t tb = 0;
-        NS_TRY(nabo::csr_sort_temp_bytes(E, n_ref, &tb));
-        const size_t e1 = (size_t)(E ? E : 1);
-        NS_RES(c_r, e1 * 8);
-        NS_RES(c_t, e1 * 8);
-        NS_RES(c_w, e1 * 8);
-        NS_RES(c_ka, e1 * 4);
-        NS_RES(c_kb, e1 * 4);
-        NS_RES(c_pa, e1 * 4);
-        NS_RES(c_pb, e1 * 4);
-        NS_RES(c_tmp, tb ? tb : 1);
-        NS_RES(c_flag, sizeof(unsigned int));
-        if (E) {
-            NS_TRY(hipMemcpyAsync(c_r.p, edge_r, (size_t)E * 8, hipMemcpyHostToDevice, st));
-            NS_TRY(hipMemcpyAsync(c_t.p, edge_t, (size_t)E * 8, hipMemcpyHostToDevice, st));
-            NS_TRY(hipMemcpyAsync(c_w.p, edge_w, (size_t)E * 8, hipMemcpyHostToDevice, st));
-        }
-        NS_TRY(nabo::csr_build_launch(c_r.as<int64_t>(), c_t.as<int64_t>(), c_w.as<double>(), E, n_ref, n_t,
-                                      c_ka.as<uint32_t>(), c_pa.as<uint32_t>(), c_kb.as<uint32_t>(), c_pb.as<uint32_t>(),
-                                      c_tmp.p, tb, d_rp.as<int64_t>(), d_et.as<int64_t>(), d_ew.as<double>(),
-                                      c_flag.as<unsigned int>(), st));
-        unsigned int bad = 0;
-        NS_TRY(hipMemcpyAsync(&bad, c_flag.p, sizeof(bad), hipMemcpyDeviceToHost, st));
-        NS_TRY(hipStreamSynchronize(st));
-        if (bad) {
-            release();
-            return fail(NABO_E_INVALID, "%s out of range", (bad & 1u) ? "edge_ref" : "edge_t");
-        }
-        DevBuf *stage[] = {&c_r, &c_t, &c_w, &c_ka, &c_kb, &c_pa, &c_pb, &c_tmp};
-        for (DevBuf *b : stage) b->release();
-    }
-    NS_TRY(hipMemcpyAsync(d_grp.p, group, (size_t)n_t, hipMemcpyHostToDevice, st));
-    // radix select of the n_A-th smallest key of every permutation, 8 bits per pass
-    std::vector<uint64_t> prefix((size_t)P, 0), below((size_t)P, 0), rank((size_t)P, (uint64_t)n_a);
-    std::vector<int64_t> sizes((size_t)P, 0);
-    std::vector<unsigned int> hist((size_t)P * 256);
-    for (int done = 0; done < key_bits; done += 8) {
-        NS_TRY(hipMemcpyAsync(d_pre.p, prefix.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));
-        NS_TRY(hipMemsetAsync(d_hist.p, 0, (size_t)P * 256 * 4, st));
-        NS_TRY(nabo::null_hist_launch(n_t, P, seed, key_bits, d_pre.as<uint64_t>(), done, d_hist.as<unsigned int>(), st));
-        NS_TRY(hipMemcpyAsync(hist.data(), d_hist.p, (size_t)P * 256 * 4, hipMemcpyDeviceToHost, st));
-        NS_TRY(hipStreamSynchronize(st));
-        for (int p = 0; p < P; ++p) {
-            const unsigned int *h = &hist[(size_t)p * 256];
-            uint64_t cum = 0;
-            int b = 0;
-            for (; b < 256; ++b) {
-                if (cum + h[b] >= rank[p]) break;
-                cum += h[b];
-            }
-            if (b == 256) { release(); return fail(NABO_E_HIP, "internal: radix select lost rank (permutation %d)", p); }
-            prefix[p] = (prefix[p] << 8) | (uint64_t)b;
-            below[p] += cum;
-            rank[p] -= cum;
-            if (done + 8 >= key_bits) sizes[p] = (int64_t)(below[p] + h[b]);      // keys <= T_p (ties at T_p included)
-        }
-    }
-    NS_TRY(hipMemcpyAsync(d_pre.p, prefix.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));        // thresholds T_p
-    NS_TRY(hipMemcpyAsync(d_nl.p, sizes.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));
-    NS_TRY(nabo::null_label_launch(n_t, P, W, seed, key_bits, d_pre.as<uint64_t>(), d_grp.as<uint8_t>(), d_bits.as<uint32_t>(), st));
-    NS_TRY(nabo::null_score_launch(n_ref, d_rp.as<int64_t>(), d_et.as<int64_t>(), d_ew.as<double>(), P, W,
-                                   d_bits.as<uint32_t>(), d_nl.as<int64_t>(), n_a, multiplier, d_obs.as<double>(),
-                                   d_nge.as<int64_t>(), d_mean.as<double>(), d_sd.as<double>(), st));
-    NS_TRY(hipMemcpyAsync(out_obs, d_obs.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
-    NS_TRY(hipMemcpyAsync(out_nge, d_nge.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
-    NS_TRY(hipMemcpyAsync(out_mean, d_mean.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
-    NS_TRY(hipMemcpyAsync(out_sd, d_sd.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
-    NS_TRY(hipStreamSynchronize(st));
-    if (out_sizes) memcpy(out_sizes, sizes.data(), (size_t)P * 8);
-    release();
-#undef NS_TRY
-#undef NS_RES
-    return NABO_OK;
-}
-
-int nabo_score_null(int32_t device, int64_t n_ref, const int64_t *row_ptr, const int64_t *edge_t,
-                    const double *edge_w, int64_t n_t, const uint8_t *group, int32_t n_perm, uint64_t seed,
-                    int32_t key_bits, double multiplier, double *out_obs, int64_t *out_nge, double *out_mean,
-                    double *out_sd, int64_t *out_sizes)
-{
-    if (!row_ptr) return fail(NABO_E_INVALID, "NULL argument");
-    return score_null_impl(device, n_ref, row_ptr, 0, nullptr, edge_t, edge_w, n_t, group, n_perm, seed, key_bits,
-                           multiplier, out_obs, out_nge, out_mean, out_sd, out_sizes);
-}
-
-int nabo_score_null_edges(int32_t device, int64_t n_ref, int64_t n_edges, const int64_t *edge_ref, const int64_t *edge_t,
-                          const double *edge_w, int64_t n_t, const uint8_t *group, int32_t n_perm, uint64_t seed,
-                          int32_t key_bits, double multiplier, double *out_obs, int64_t *out_nge, double *out_mean,
-                          double *out_sd, int64_t *out_sizes)
-{
-    return score_null_impl(device, n_ref, nullptr, n_edges, edge_ref, edge_t, edge_w, n_t, group, n_perm, seed, key_bits,
-                           multiplier, out_obs, out_nge, out_mean, out_sd, out_sizes);
-}
-
 int nabo_dev_malloc(int32_t device, void **ptr, size_t bytes)
 {
-    if (!ptr) return fail(NABO_E_INVALID, "NULL argument");
+    if (!ptr) return api_fail(NABO_E_INVALID, "NULL argument");
     int rc = use_device(device);
     if (rc) return rc;
     HIP_TRY(hipMalloc(ptr, bytes ? bytes : 1));
@@ -2062,7 +1720,7 @@ int nabo_memcpy_d2h(int32_t device, void *dst, const void *src, size_t bytes)
 
 int nabo_dev_mem_info(int32_t device, size_t *free_bytes, size_t *total_bytes)
 {
-    if (!free_bytes || !total_bytes) return fail(NABO_E_INVALID, "NULL argument");
+    if (!free_bytes || !total_bytes) return api_fail(NABO_E_INVALID, "NULL argument");
     int rc = use_device(device);
     if (rc) return rc;
     HIP_TRY(hipMemGetInfo(free_bytes, total_bytes));

@@ -13,6 +13,7 @@
 // Layout: lane = reference (64 per chunk, coalesced from the transposed pack Yt[chunk][k][64]),
 // target row = wave-uniform; each wave owns T targets and their candidate lists in LDS.
 #include "knn_common.h"
+#include "launch.h"
 
 namespace nabo {
 

@@ -37,6 +37,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "knn_common.h"
+#include "launch.h"
 
 namespace nabo {
 
@@ -656,8 +657,6 @@ hipError_t cbb_pack_targets_launch(const double *X, int64_t m, int g, int gp, do
                        rowoff);
     return hipGetLastError();
 }
-
-void cbf_constants(int g, float *slack, float *plateau);
 
 template <int GP, int EPL>
 static hipError_t cbb_launch_one(const float *xq, const uint16_t *rowoff, int64_t m, const float *yrow, const uint32_t *tab,

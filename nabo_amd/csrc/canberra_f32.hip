@@ -30,6 +30,7 @@
 // (fp32 key + u32 index) in LDS.  See cbf_filter_kernel for the count / compact / bound structure.
 #include <cstdlib>
 #include "knn_common.h"
+#include "launch.h"
 
 namespace nabo {
 

@@ -12,6 +12,8 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <stdint.h>
 
+#include "launch.h"
+
 namespace nabo {
 
 __global__ __launch_bounds__(256) void csr_keys_kernel(const int64_t *__restrict__ edge_r, int64_t E, int64_t n_ref,

@@ -19,10 +19,9 @@
 #include <vector>
 
 #include "../../include/nabo_knn.h"
+#include "launch.h"
 
 namespace nabo {
-int api_fail(int code, const char *fmt, ...);
-
 namespace {
 
 // Rows [0, n) in chunks on the caller's cores.  Nothing escapes a worker thread: an exception thrown inside one (bad_alloc

@@ -31,6 +31,7 @@
 #include <cstdlib>
 
 #include "knn_common.h"
+#include "launch.h"
 #include "topk_lists.h"
 
 namespace nabo {

@@ -37,6 +37,7 @@
 #define NABO_DRAIN_CALL 1
 #endif
 #include "knn_common.h"
+#include "launch.h"
 #include "topk_lists.h"
 
 namespace nabo {

@@ -28,6 +28,7 @@
 #include <hip/hip_fp16.h>
 
 #include "knn_common.h"
+#include "launch.h"
 #include "topk_lists.h"
 
 namespace nabo {

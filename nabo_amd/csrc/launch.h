@@ -1,0 +1,148 @@
+// launch.h -- every function of libnabo_knn.so that one translation unit defines and another calls: the kernel launchers,
+// their geometry and plan helpers, the index accessors sharded.hip uses, and the error recorder.  The defining file and
+// every caller include it, so each definition is checked against the one declaration here; default arguments live here
+// and nowhere else.  Host types only: tests/host_shim compiles sharded.hip and its fakes of some of these with g++.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#ifdef NABO_SHARDED_HOST
+#include "hip_shim.h"
+#else
+#include <hip/hip_runtime.h>
+#endif
+
+struct L2cPieces;      // knn_common.h
+struct nabo_index;     // api.hip
+
+namespace nabo {
+
+// api.hip: records the message nabo_last_error() returns and passes the code through
+int api_fail(int code, const char *fmt, ...);
+// api.hip: what sharded.hip reads and sets on an index
+int index_device(const nabo_index *ix);
+int index_g(const nabo_index *ix);
+int64_t index_n(const nabo_index *ix);
+int index_metric(const nabo_index *ix);
+bool index_can_emit_candidates(const nabo_index *ix);
+void index_set_shard_mode(nabo_index *ix, bool on);
+void index_set_cand_slack(nabo_index *ix, int s);
+
+// pack.hip: fp32 tiles of the fp32-MFMA filter
+hipError_t centre_launch(const double *Y, int64_t n, int g, double *centre, hipStream_t st);
+hipError_t pack_ref_launch(const double *Y, int64_t n, int g, const double *centre, double scale, int ksteps, int64_t ntiles_total,
+                           const uint8_t *mask, float *out, unsigned int *norm_max_bits, hipStream_t st);
+hipError_t pack_query_launch(const double *X, int64_t m, int g, const double *centre, double scale, int ksteps,
+                             int64_t ntiles_total, float *out, double *xnorm, hipStream_t st);
+// f16 operands of the matrix-pipe filters (pack.hip): K-concatenated tiles, nseg = 3 the f16x3 split, 1 the one-product form
+hipError_t maxabs_launch(const double *V, int64_t n, int g, const double *centre, unsigned long long *out_bits, hipStream_t st);
+hipError_t pack_cref_launch(const double *Y, int64_t n, int g, const double *centre, double scale, int kc,
+                            int64_t ntiles_total, const uint8_t *mask, unsigned char *out, unsigned int *norm_max_bits,
+                            bool layout16, hipStream_t st, const uint32_t *perm = nullptr, int nseg = 3);
+hipError_t pack_cquery_launch(const double *X, int64_t m, int g, const double *centre, double scale, int kc,
+                              int64_t ntiles_total, unsigned char *out, double *xnorm, bool layout16, hipStream_t st,
+                              const uint32_t *perm = nullptr, int nseg = 3);
+
+// the fp32-MFMA filter (l2_topk.hip)
+hipError_t l2_topk_launch(int ksteps, int epl, const float *Xpk, const float *Ypk, int tiles_per_split, int S, int gx,
+                          int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
+                          hipStream_t st);
+void l2_topk_geometry(int ksteps, int epl, int *rows_per_wg, int *wg_per_cu, int *lkeep_max);
+// the same filter on v_mfma_f32_16x16x32_f16 (l2q_topk.hip; operands packed with layout16)
+int l2q_pick_kc(int g);
+hipError_t l2q_topk_launch(int kc, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
+                           int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
+                           int64_t pad_tile, hipStream_t st, const int32_t *wave_start = nullptr);
+void l2q_topk_geometry(int kc, int *rows_per_wg, int *wg_per_cu, int *lkeep_max);
+// the one-product first pass (l2c_topk.hip; operands packed with layout16, nseg = 1)
+int l2c_pick_kc(int g);
+int l2c_geometry(int kc, int lkeep_want, int pin);
+void l2c_topk_geometry(int kc, int lkeep_want, int pin, int *rows_per_wg, int *wg_per_cu, int *lkeep_max);
+hipError_t l2c_topk_launch(int kc, int geo, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
+                           int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
+                           int64_t pad_tile, hipStream_t st, int64_t rows_valid, const float *tau_init, int tau_stride = 0,
+                           int64_t tau_row0 = 0, const L2cPieces *pieces = nullptr);
+// tournament seeds for the one-product pass (l2c_topk.hip: l2c_pre_kernel)
+void l2c_pre_plan(int kc, int lkeep, int tiles_per_split, int scale_pct, int *pre_tiles, int *gt);
+hipError_t l2c_pre_launch(int kc, int lkeep, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
+                          int64_t rows, int64_t tile_off, int pre_tiles, int gt, int64_t pad_tile, hipStream_t st,
+                          int64_t rows_valid, float *tau_out, const int *ranges = nullptr, int rows_per_col = 0);
+
+// list merges, float64 re-evaluation, exact kernels and row helpers (refine.hip)
+hipError_t merge_lists_launch(const uint32_t *cand_idx, const float *cand_key, const float *cand_tau, int64_t rows, int S, int L,
+                              int lkeep, int Lout, uint32_t *out_idx, float *out_tau, hipStream_t st);
+hipError_t pairwise_launch(const double *X, int64_t m, const double *Y, int64_t n, int g, int metric, double f,
+                           double *D, hipStream_t st);
+hipError_t refine_launch(const double *X, int64_t row0, int64_t m, const double *Y, int g, const uint32_t *cand_idx,
+                         const float *cand_tau, int S, int L, const double *xnorm, double err_coef, double ymax_sqrt,
+                         double tau_scale, int k, int drop, int64_t base, int64_t n_valid_total, const uint32_t *masked_list,
+                         int n_masked_list, int64_t *out_idx, double *out_dist, uint32_t *fail_rows,
+                         unsigned int *fail_count, hipStream_t st, int metric = 0, double cb_f = 0.0,
+                         float cb_plateau = 0.0f, int lvalid = 0, const uint32_t *rperm = nullptr,
+                         const uint32_t *tperm = nullptr, float *fail_seed = nullptr);
+hipError_t refine_cand_launch(const double *X, int64_t row0, int64_t m, const double *Y, int g, const uint32_t *cand_idx,
+                              const float *cand_tau, int S, int L, const double *xnorm, double err_coef,
+                              double ymax_sqrt, double tau_scale, int kout, int64_t base, int64_t n_valid_total,
+                              int64_t *out_idx, double *out_dist, double *out_bound, hipStream_t st, int metric = 0,
+                              int lvalid = 0, const uint32_t *rperm = nullptr, const uint32_t *tperm = nullptr);
+hipError_t normalise_rows_launch(const double *X, int64_t m, int g, double *out, hipStream_t st);
+hipError_t exact_rows_launch(const double *X, const double *Y, int64_t n, int g, int metric, double f,
+                             const uint8_t *mask, const uint32_t *rows, unsigned int nrows, int k, int drop,
+                             int64_t base, const uint32_t *masked_list, int n_masked_list, int64_t *out_idx,
+                             double *out_dist, double *D, unsigned int d_rows, hipStream_t st);
+hipError_t masked_tail_launch(const double *X, int64_t m, const double *Y, int g, int metric, double f,
+                              const uint32_t *masked_list, int n_masked_list, int n_valid, int k, int drop,
+                              int64_t base, int64_t *out_idx, double *out_dist, hipStream_t st);
+hipError_t gather_rows_launch(const double *X, const uint32_t *rows, int64_t nrows, int g, double *out, hipStream_t st);
+hipError_t iota_launch(uint32_t *out, int64_t n, hipStream_t st);
+hipError_t scatter_rows_launch(const int64_t *si, const double *sd, const uint32_t *rows, int64_t nrows, int k,
+                               int64_t *out_idx, double *out_dist, hipStream_t st);
+
+// exact Canberra kernel, the top-k merges and SNN counts (canberra.hip)
+hipError_t transpose_ref_launch(const double *Y, int64_t n, int g, double *Yt, hipStream_t st);
+hipError_t canberra_topk_launch(int epl, const double *X, int64_t m, const double *Yt, int64_t n, int g, double f,
+                                const uint8_t *mask, int S, double *cand_d, uint32_t *cand_i, hipStream_t st);
+hipError_t merge_local_launch(const double *cand_d, const uint32_t *cand_i, int64_t m, int P, int k, int drop,
+                              int64_t base, int64_t *out_idx, double *out_dist, int *n_found, hipStream_t st);
+hipError_t merge_parts_launch(const double *parts_d, const int64_t *parts_i, int n_parts, int64_t m, int kp, int k,
+                              int drop, int64_t *out_idx, double *out_dist, hipStream_t st);
+hipError_t snn_counts_launch(const int64_t *t_idx, int64_t m, const int64_t *r_idx, int64_t n, int k, int32_t *out,
+                             hipStream_t st);
+
+// fp32 lower-bound Canberra filter (canberra_f32.hip)
+hipError_t cbf_pack_targets_launch(const double *X, int64_t m, int g, int gp, double f, float *xq, unsigned int *flag,
+                                   hipStream_t st);
+hipError_t cbf_pack_refs_launch(const double *Y, int64_t n, int g, int gp, float *ycf, unsigned int *flag,
+                                hipStream_t st);
+int cbf_pick_gp(int g);
+void cbf_constants(int g, float *slack, float *plateau);
+int cbf_lists_per_split();
+int cbf_rows_per_wg(int epl);
+hipError_t cbf_filter_launch(int gp, int epl, const float *xq, const void *xh, int64_t m, const float *ycf,
+                             const void *ych, int64_t n, int g, const uint8_t *mask, int S, uint32_t *cand_idx,
+                             float *cand_tau, hipStream_t st);
+hipError_t cbf_pack_refs_rows_launch(const double *Y, int64_t n, int g, int gp, float *yrow, hipStream_t st);
+hipError_t cbf_colminmax_launch(const double *Y, int64_t n, int g, unsigned int *colmm, hipStream_t st);
+hipError_t cbf_pack_refs8_launch(const double *Y, int64_t n, int g, int gp, const double *quant, void *ych, hipStream_t st);
+hipError_t cbf_pack_targets8_launch(const double *X, int64_t m, int g, int gp, double f, const double *quant, void *xh,
+                                    hipStream_t st);
+// the counting pass on per-bucket bitmaps (canberra_bits.hip)
+int cbb_buckets();
+int cbb_rows_per_wg();
+bool cbb_available(int g, int gp, int epl);
+size_t cbb_table_bytes(int64_t n, int g);
+size_t cbb_valid_bytes(int64_t n);
+hipError_t cbb_pack_table_launch(const double *Y, int64_t n, int g, const double *edges, uint32_t *tab, hipStream_t st);
+hipError_t cbb_valid_launch(const uint8_t *mask, int64_t n, uint32_t *vbits, hipStream_t st);
+hipError_t cbb_pack_targets_launch(const double *X, int64_t m, int g, int gp, double f, const double *edges, uint16_t *rowoff,
+                                   hipStream_t st);
+hipError_t cbb_filter_launch(int gp, const float *xq, const uint16_t *rowoff, int64_t m, const float *yrow, const uint32_t *tab,
+                             const uint32_t *vbits, int64_t n, int g, int S, uint32_t *cand_idx, float *cand_tau, hipStream_t st);
+
+// COO edges -> CSR by reference node, a stable device sort (csr_build.hip; for score_null.hip)
+hipError_t csr_sort_temp_bytes(int64_t E, int64_t n_ref, size_t *bytes);
+hipError_t csr_build_launch(const int64_t *edge_r, const int64_t *edge_t, const double *edge_w, int64_t E, int64_t n_ref,
+                            int64_t n_t, uint32_t *keys_a, uint32_t *pos_a, uint32_t *keys_b, uint32_t *pos_b, void *temp,
+                            size_t temp_bytes, int64_t *row_ptr, int64_t *out_t, double *out_w, unsigned int *flag,
+                            hipStream_t st);
+
+}  // namespace nabo

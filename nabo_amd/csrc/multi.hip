@@ -15,10 +15,7 @@
 #include <vector>
 
 #include "../../include/nabo_knn.h"
-
-namespace nabo {
-int api_fail(int code, const char *fmt, ...);
-}
+#include "launch.h"
 
 namespace {
 

@@ -8,6 +8,7 @@
 #include <hip/hip_fp16.h>
 
 #include "knn_common.h"
+#include "launch.h"
 
 namespace nabo {
 

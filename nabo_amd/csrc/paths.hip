@@ -436,54 +436,18 @@ hipError_t paths_reduce_launch(const int64_t *pair_off, int64_t n_groups, const 
 
 #include "../../include/nabo_graph.h"
 #include "../../include/nabo_knn.h"
-
-namespace nabo {
-int api_fail(int code, const char *fmt, ...);      // api.hip: sets nabo_last_error()
-}  // namespace nabo
+#include "host_common.h"
 
 namespace {
 
+using nabo::DevBuf;
 using nabo::PathsPair;
+using nabo::use_device;
 
 constexpr int64_t LOCAL_CAPACITY_MAX = 896;     // 1024 slots x 32 B of LDS
 // measured balls (DESIGN.md "Hop distances"): the nodes within ceil(Dmax/2) of a group's members are <= 115 for 90 %
 // of c1_3k's targets and <= 380 for 99 % of mapping_small's; 768 holds both with the table <= 3/4 full
 constexpr int64_t LOCAL_CAPACITY_DEFAULT = 768;
-
-#define PATHS_TRY(expr)                                                                                             \
-    do {                                                                                                           \
-        hipError_t e__ = (expr);                                                                                   \
-        if (e__ != hipSuccess) {                                                                                   \
-            (void)hipGetLastError();                                                                               \
-            return nabo::api_fail(e__ == hipErrorOutOfMemory ? NABO_E_NOMEM : NABO_E_HIP, "%s failed: %s", #expr,      \
-                                  hipGetErrorString(e__));                                                                  \
-        }                                                                                                          \
-    } while (0)
-
-struct DevMem {
-    void *p = nullptr;
-    DevMem() = default;
-    DevMem(const DevMem &) = delete;
-    DevMem &operator=(const DevMem &) = delete;
-    ~DevMem() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes)
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        return hipMalloc(&p, bytes ? bytes : 8);
-    }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-int use_device(int device)
-{
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0)
-        return nabo::api_fail(NABO_E_NODEVICE, "no HIP device is available (libnabo_knn has no CPU fallback)");
-    if (device < 0 || device >= cnt) return nabo::api_fail(NABO_E_NODEVICE, "device %d out of range (have %d)", device, cnt);
-    PATHS_TRY(hipSetDevice(device));
-    return NABO_OK;
-}
 
 double now_ms()
 {
@@ -496,9 +460,9 @@ struct nabo_refgraph {
     int device = 0;
     int64_t n = 0, n_arcs = 0;
     hipStream_t st = nullptr;
-    DevMem rowptr, col;
+    DevBuf rowptr, col;
     // global-tier state, allocated on first use: visited / frontier / next masks, node lists, counters
-    DevMem visited, front, nxt, cur, next_list, touched, counters;
+    DevBuf visited, front, nxt, cur, next_list, touched, counters;
     int64_t *host_counters = nullptr;     // pinned
     int64_t local_capacity = LOCAL_CAPACITY_DEFAULT, local_max_members = 64;
     double build_ms = 0;
@@ -518,25 +482,25 @@ int refgraph_build(nabo_refgraph *g, const int64_t *ptr, const int64_t *nbr)
 {
     const int64_t n = g->n, E = ptr[n];
     size_t sort_bytes = 0, uniq_bytes = 0;
-    PATHS_TRY(nabo::paths_build_temp_bytes(2 * E, n, &sort_bytes, &uniq_bytes));
-    DevMem d_ptr, d_nbr, keys_a, keys_b, sort_temp, uniq_temp, n_keys;
-    PATHS_TRY(d_ptr.alloc((size_t)(n + 1) * 8));
-    PATHS_TRY(d_nbr.alloc((size_t)E * 8));
-    PATHS_TRY(keys_a.alloc((size_t)2 * E * 8));
-    PATHS_TRY(keys_b.alloc((size_t)2 * E * 8));
-    PATHS_TRY(sort_temp.alloc(sort_bytes));
-    PATHS_TRY(uniq_temp.alloc(uniq_bytes));
-    PATHS_TRY(n_keys.alloc(8));
-    PATHS_TRY(hipMemcpyAsync(d_ptr.p, ptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, g->st));
-    if (E) PATHS_TRY(hipMemcpyAsync(d_nbr.p, nbr, (size_t)E * 8, hipMemcpyHostToDevice, g->st));
-    PATHS_TRY(g->rowptr.alloc((size_t)(n + 1) * 4));
-    PATHS_TRY(g->col.alloc((size_t)2 * E * 4));
-    PATHS_TRY(nabo::paths_build_launch(d_ptr.as<int64_t>(), d_nbr.as<int64_t>(), n, E, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(),
-                                       sort_temp.p, sort_bytes, uniq_temp.p, uniq_bytes, n_keys.as<int64_t>(),
-                                       g->rowptr.as<int32_t>(), g->col.as<int32_t>(), g->st));
+    HIP_TRY(nabo::paths_build_temp_bytes(2 * E, n, &sort_bytes, &uniq_bytes));
+    DevBuf d_ptr, d_nbr, keys_a, keys_b, sort_temp, uniq_temp, n_keys;
+    HIP_TRY(d_ptr.alloc((size_t)(n + 1) * 8));
+    HIP_TRY(d_nbr.alloc((size_t)E * 8));
+    HIP_TRY(keys_a.alloc((size_t)2 * E * 8));
+    HIP_TRY(keys_b.alloc((size_t)2 * E * 8));
+    HIP_TRY(sort_temp.alloc(sort_bytes));
+    HIP_TRY(uniq_temp.alloc(uniq_bytes));
+    HIP_TRY(n_keys.alloc(8));
+    HIP_TRY(hipMemcpyAsync(d_ptr.p, ptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, g->st));
+    if (E) HIP_TRY(hipMemcpyAsync(d_nbr.p, nbr, (size_t)E * 8, hipMemcpyHostToDevice, g->st));
+    HIP_TRY(g->rowptr.alloc((size_t)(n + 1) * 4));
+    HIP_TRY(g->col.alloc((size_t)2 * E * 4));
+    HIP_TRY(nabo::paths_build_launch(d_ptr.as<int64_t>(), d_nbr.as<int64_t>(), n, E, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(),
+                                     sort_temp.p, sort_bytes, uniq_temp.p, uniq_bytes, n_keys.as<int64_t>(),
+                                     g->rowptr.as<int32_t>(), g->col.as<int32_t>(), g->st));
     int64_t arcs = 0;
-    PATHS_TRY(hipMemcpyAsync(&arcs, n_keys.p, 8, hipMemcpyDeviceToHost, g->st));
-    PATHS_TRY(hipStreamSynchronize(g->st));
+    HIP_TRY(hipMemcpyAsync(&arcs, n_keys.p, 8, hipMemcpyDeviceToHost, g->st));
+    HIP_TRY(hipStreamSynchronize(g->st));
     g->n_arcs = arcs;
     return NABO_OK;
 }
@@ -545,17 +509,17 @@ int ensure_global_state(nabo_refgraph *g)
 {
     if (g->visited.p) return NABO_OK;
     const size_t n = (size_t)g->n;
-    PATHS_TRY(g->visited.alloc(n * 8));
-    PATHS_TRY(g->front.alloc(n * 8));
-    PATHS_TRY(g->nxt.alloc(n * 8));
-    PATHS_TRY(g->cur.alloc(n * 4));
-    PATHS_TRY(g->next_list.alloc(n * 4));
-    PATHS_TRY(g->touched.alloc(n * 4));
-    PATHS_TRY(g->counters.alloc(4 * 8));
-    PATHS_TRY(hipHostMalloc((void **)&g->host_counters, 4 * 8, hipHostMallocDefault));
-    PATHS_TRY(hipMemsetAsync(g->visited.p, 0, n * 8, g->st));
-    PATHS_TRY(hipMemsetAsync(g->front.p, 0, n * 8, g->st));
-    PATHS_TRY(hipMemsetAsync(g->nxt.p, 0, n * 8, g->st));
+    HIP_TRY(g->visited.alloc(n * 8));
+    HIP_TRY(g->front.alloc(n * 8));
+    HIP_TRY(g->nxt.alloc(n * 8));
+    HIP_TRY(g->cur.alloc(n * 4));
+    HIP_TRY(g->next_list.alloc(n * 4));
+    HIP_TRY(g->touched.alloc(n * 4));
+    HIP_TRY(g->counters.alloc(4 * 8));
+    HIP_TRY(hipHostMalloc((void **)&g->host_counters, 4 * 8, hipHostMallocDefault));
+    HIP_TRY(hipMemsetAsync(g->visited.p, 0, n * 8, g->st));
+    HIP_TRY(hipMemsetAsync(g->front.p, 0, n * 8, g->st));
+    HIP_TRY(hipMemsetAsync(g->nxt.p, 0, n * 8, g->st));
     return NABO_OK;
 }
 
@@ -565,37 +529,37 @@ int run_global(nabo_refgraph *g, const std::vector<int32_t> &sources, const std:
 {
     int rc = ensure_global_state(g);
     if (rc) return rc;
-    DevMem d_src;
-    PATHS_TRY(d_src.alloc(sources.size() * 4));
+    DevBuf d_src;
+    HIP_TRY(d_src.alloc(sources.size() * 4));
     if (!sources.empty())
-        PATHS_TRY(hipMemcpyAsync(d_src.p, sources.data(), sources.size() * 4, hipMemcpyHostToDevice, g->st));
+        HIP_TRY(hipMemcpyAsync(d_src.p, sources.data(), sources.size() * 4, hipMemcpyHostToDevice, g->st));
     int32_t *cur = g->cur.as<int32_t>(), *nxt_list = g->next_list.as<int32_t>();
     int64_t *cnt = g->counters.as<int64_t>();
     const int64_t n_sweeps = (int64_t)sweep_ptr.size() - 1;
     for (int64_t w = 0; w < n_sweeps; ++w) {
         const int n_src = (int)std::min<int64_t>(64, (int64_t)sources.size() - 64 * w);
         const int64_t p0 = sweep_ptr[w], np = sweep_ptr[w + 1] - p0;
-        PATHS_TRY(nabo::paths_sweep_init_launch(d_src.as<int32_t>() + 64 * w, n_src, g->visited.as<uint64_t>(), g->front.as<uint64_t>(),
-                                                cur, g->touched.as<int32_t>(), cnt, g->st));
+        HIP_TRY(nabo::paths_sweep_init_launch(d_src.as<int32_t>() + 64 * w, n_src, g->visited.as<uint64_t>(), g->front.as<uint64_t>(),
+                                              cur, g->touched.as<int32_t>(), cnt, g->st));
         int64_t open = np, n_cur = n_src;
         int32_t level = 0;
         while (open > 0 && n_cur > 0) {
             ++level;
-            PATHS_TRY(nabo::paths_level_launch(g->rowptr.as<int32_t>(), g->col.as<int32_t>(), cur, nxt_list, g->visited.as<uint64_t>(),
-                                               g->front.as<uint64_t>(), g->nxt.as<uint64_t>(), g->touched.as<int32_t>(), d_pairs + p0,
-                                               np, level, d_pair_dist, cnt, n_cur, g->st));
-            PATHS_TRY(hipMemcpyAsync(g->host_counters, cnt, 2 * 8, hipMemcpyDeviceToHost, g->st));
-            PATHS_TRY(nabo::paths_advance_launch(cnt, g->st));
-            PATHS_TRY(hipStreamSynchronize(g->st));
+            HIP_TRY(nabo::paths_level_launch(g->rowptr.as<int32_t>(), g->col.as<int32_t>(), cur, nxt_list, g->visited.as<uint64_t>(),
+                                             g->front.as<uint64_t>(), g->nxt.as<uint64_t>(), g->touched.as<int32_t>(), d_pairs + p0,
+                                             np, level, d_pair_dist, cnt, n_cur, g->st));
+            HIP_TRY(hipMemcpyAsync(g->host_counters, cnt, 2 * 8, hipMemcpyDeviceToHost, g->st));
+            HIP_TRY(nabo::paths_advance_launch(cnt, g->st));
+            HIP_TRY(hipStreamSynchronize(g->st));
             n_cur = g->host_counters[0];
             open -= g->host_counters[1];
             std::swap(cur, nxt_list);
         }
         g->stats[3] = std::max<int64_t>(g->stats[3], level);
-        PATHS_TRY(nabo::paths_clear_launch(g->touched.as<int32_t>(), cnt, g->visited.as<uint64_t>(), g->front.as<uint64_t>(), g->st));
+        HIP_TRY(nabo::paths_clear_launch(g->touched.as<int32_t>(), cnt, g->visited.as<uint64_t>(), g->front.as<uint64_t>(), g->st));
     }
     // the lists may have been swapped an odd number of times: keep the object's pointers as they are (both are scratch)
-    PATHS_TRY(hipStreamSynchronize(g->st));
+    HIP_TRY(hipStreamSynchronize(g->st));
     g->stats[2] += n_sweeps;
     return NABO_OK;
 }
@@ -705,28 +669,28 @@ int nabo_refgraph_group_hops(nabo_refgraph *g, int64_t n_groups, const int64_t *
         const int64_t m = grp_ptr[i + 1] - grp_ptr[i];
         if (use_local && m >= 2 && m <= g->local_max_members) local.push_back((int32_t)i);
     }
-    DevMem d_grp, d_mem, d_off, d_local, d_dist, d_nodes, d_sum, d_unr;
-    PATHS_TRY(d_grp.alloc((size_t)(n_groups + 1) * 8));
-    PATHS_TRY(d_mem.alloc((size_t)M * 4));
-    PATHS_TRY(d_off.alloc((size_t)(n_groups + 1) * 8));
-    PATHS_TRY(d_local.alloc(local.size() * 4));
-    PATHS_TRY(d_dist.alloc((size_t)P * 4));
-    PATHS_TRY(d_nodes.alloc(local.size() * 4));
-    PATHS_TRY(d_sum.alloc((size_t)n_groups * 8));
-    PATHS_TRY(d_unr.alloc((size_t)n_groups * 8));
-    PATHS_TRY(hipMemcpyAsync(d_grp.p, grp_ptr, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, g->st));
-    if (M) PATHS_TRY(hipMemcpyAsync(d_mem.p, mem.data(), (size_t)M * 4, hipMemcpyHostToDevice, g->st));
-    PATHS_TRY(hipMemcpyAsync(d_off.p, pair_off.data(), (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, g->st));
+    DevBuf d_grp, d_mem, d_off, d_local, d_dist, d_nodes, d_sum, d_unr;
+    HIP_TRY(d_grp.alloc((size_t)(n_groups + 1) * 8));
+    HIP_TRY(d_mem.alloc((size_t)M * 4));
+    HIP_TRY(d_off.alloc((size_t)(n_groups + 1) * 8));
+    HIP_TRY(d_local.alloc(local.size() * 4));
+    HIP_TRY(d_dist.alloc((size_t)P * 4));
+    HIP_TRY(d_nodes.alloc(local.size() * 4));
+    HIP_TRY(d_sum.alloc((size_t)n_groups * 8));
+    HIP_TRY(d_unr.alloc((size_t)n_groups * 8));
+    HIP_TRY(hipMemcpyAsync(d_grp.p, grp_ptr, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, g->st));
+    if (M) HIP_TRY(hipMemcpyAsync(d_mem.p, mem.data(), (size_t)M * 4, hipMemcpyHostToDevice, g->st));
+    HIP_TRY(hipMemcpyAsync(d_off.p, pair_off.data(), (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, g->st));
     std::vector<int32_t> nodes(local.size(), -1);
     if (!local.empty()) {
-        PATHS_TRY(hipMemcpyAsync(d_local.p, local.data(), local.size() * 4, hipMemcpyHostToDevice, g->st));
+        HIP_TRY(hipMemcpyAsync(d_local.p, local.data(), local.size() * 4, hipMemcpyHostToDevice, g->st));
         int32_t slots = 2;
         while (slots < g->local_capacity + g->local_capacity / 8) slots *= 2;
-        PATHS_TRY(nabo::paths_local_launch(g->rowptr.as<int32_t>(), g->col.as<int32_t>(), d_grp.as<int64_t>(), d_mem.as<int32_t>(),
-                                           d_off.as<int64_t>(), d_local.as<int32_t>(), (int64_t)local.size(), slots,
-                                           (int32_t)g->local_capacity, d_dist.as<int32_t>(), d_nodes.as<int32_t>(), g->st));
-        PATHS_TRY(hipMemcpyAsync(nodes.data(), d_nodes.p, local.size() * 4, hipMemcpyDeviceToHost, g->st));
-        PATHS_TRY(hipStreamSynchronize(g->st));
+        HIP_TRY(nabo::paths_local_launch(g->rowptr.as<int32_t>(), g->col.as<int32_t>(), d_grp.as<int64_t>(), d_mem.as<int32_t>(),
+                                         d_off.as<int64_t>(), d_local.as<int32_t>(), (int64_t)local.size(), slots,
+                                         (int32_t)g->local_capacity, d_dist.as<int32_t>(), d_nodes.as<int32_t>(), g->st));
+        HIP_TRY(hipMemcpyAsync(nodes.data(), d_nodes.p, local.size() * 4, hipMemcpyDeviceToHost, g->st));
+        HIP_TRY(hipStreamSynchronize(g->st));
     }
     const double t1 = now_ms();
     g->ms[1] = t1 - t0;
@@ -786,25 +750,25 @@ int nabo_refgraph_group_hops(nabo_refgraph *g, int64_t n_groups, const int64_t *
         std::vector<int64_t> fill(start.begin(), start.end() - 1);
         for (size_t p = 0; p < pairs.size(); ++p) sorted[fill[pair_sweep[p] < 0 ? n_sweeps : pair_sweep[p]]++] = pairs[p];
         const std::vector<int64_t> sweep_ptr(start.begin(), start.begin() + n_sweeps + 1);
-        DevMem d_pairs;
-        PATHS_TRY(d_pairs.alloc(sorted.size() * sizeof(PathsPair)));
-        PATHS_TRY(hipMemcpyAsync(d_pairs.p, sorted.data(), sorted.size() * sizeof(PathsPair), hipMemcpyHostToDevice, g->st));
-        PATHS_TRY(nabo::paths_prefill_launch(d_pairs.p, (int64_t)sorted.size(), d_dist.as<int32_t>(), g->st));
+        DevBuf d_pairs;
+        HIP_TRY(d_pairs.alloc(sorted.size() * sizeof(PathsPair)));
+        HIP_TRY(hipMemcpyAsync(d_pairs.p, sorted.data(), sorted.size() * sizeof(PathsPair), hipMemcpyHostToDevice, g->st));
+        HIP_TRY(nabo::paths_prefill_launch(d_pairs.p, (int64_t)sorted.size(), d_dist.as<int32_t>(), g->st));
         if (n_sweeps > 0) {
             rc = run_global(g, sources, sweep_ptr, d_pairs.as<PathsPair>(), d_dist.as<int32_t>());
             if (rc) return rc;
         }
-        PATHS_TRY(hipStreamSynchronize(g->st));
+        HIP_TRY(hipStreamSynchronize(g->st));
     }
     const double t2 = now_ms();
     g->ms[2] = t2 - t1;
-    PATHS_TRY(nabo::paths_reduce_launch(d_off.as<int64_t>(), n_groups, d_dist.as<int32_t>(), d_sum.as<int64_t>(), d_unr.as<int64_t>(), g->st));
+    HIP_TRY(nabo::paths_reduce_launch(d_off.as<int64_t>(), n_groups, d_dist.as<int32_t>(), d_sum.as<int64_t>(), d_unr.as<int64_t>(), g->st));
     if (n_groups) {
-        PATHS_TRY(hipMemcpyAsync(out_sum, d_sum.p, (size_t)n_groups * 8, hipMemcpyDeviceToHost, g->st));
-        PATHS_TRY(hipMemcpyAsync(out_unreached, d_unr.p, (size_t)n_groups * 8, hipMemcpyDeviceToHost, g->st));
+        HIP_TRY(hipMemcpyAsync(out_sum, d_sum.p, (size_t)n_groups * 8, hipMemcpyDeviceToHost, g->st));
+        HIP_TRY(hipMemcpyAsync(out_unreached, d_unr.p, (size_t)n_groups * 8, hipMemcpyDeviceToHost, g->st));
     }
-    if (out_pair_hops && P) PATHS_TRY(hipMemcpyAsync(out_pair_hops, d_dist.p, (size_t)P * 4, hipMemcpyDeviceToHost, g->st));
-    PATHS_TRY(hipStreamSynchronize(g->st));
+    if (out_pair_hops && P) HIP_TRY(hipMemcpyAsync(out_pair_hops, d_dist.p, (size_t)P * 4, hipMemcpyDeviceToHost, g->st));
+    HIP_TRY(hipStreamSynchronize(g->st));
     g->ms[3] = now_ms() - t0;
     return NABO_OK;
 }

@@ -14,6 +14,7 @@
 // (duplicates, pathological gaps) are re-solved by the exact kernels below, which brute-force the
 // whole reference set in float64 on the GPU.  There is no CPU path.
 #include "knn_common.h"
+#include "launch.h"
 
 namespace nabo {
 
@@ -726,9 +727,8 @@ hipError_t refine_launch(const double *X, int64_t row0, int64_t m, const double 
                          const float *cand_tau, int S, int L, const double *xnorm, double err_coef,
                          double ymax_sqrt, double tau_scale, int k, int drop, int64_t base, int64_t n_valid_total,
                          const uint32_t *masked_list, int n_masked_list, int64_t *out_idx, double *out_dist,
-                         uint32_t *fail_rows, unsigned int *fail_count, hipStream_t st, int metric = 0,
-                         double cb_f = 0.0, float cb_plateau = 0.0f, int lvalid = 0, const uint32_t *rperm = nullptr,
-                         const uint32_t *tperm = nullptr, float *fail_seed = nullptr)
+                         uint32_t *fail_rows, unsigned int *fail_count, hipStream_t st, int metric, double cb_f,
+                         float cb_plateau, int lvalid, const uint32_t *rperm, const uint32_t *tperm, float *fail_seed)
 {
     const int ncl = (S * L + 63) / 64;
     if (m <= row0) return hipSuccess;
@@ -768,8 +768,8 @@ hipError_t refine_launch(const double *X, int64_t row0, int64_t m, const double 
 hipError_t refine_cand_launch(const double *X, int64_t row0, int64_t m, const double *Y, int g, const uint32_t *cand_idx,
                               const float *cand_tau, int S, int L, const double *xnorm, double err_coef,
                               double ymax_sqrt, double tau_scale, int kout, int64_t base, int64_t n_valid_total,
-                              int64_t *out_idx, double *out_dist, double *out_bound, hipStream_t st, int metric = 0,
-                              int lvalid = 0, const uint32_t *rperm = nullptr, const uint32_t *tperm = nullptr)
+                              int64_t *out_idx, double *out_dist, double *out_bound, hipStream_t st, int metric,
+                              int lvalid, const uint32_t *rperm, const uint32_t *tperm)
 {
     const int ncl = (S * L + 63) / 64;
     if (m <= row0) return hipSuccess;

@@ -16,6 +16,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstring>
+#include <vector>
+
+#include "host_common.h"
+
 namespace nabo {
 
 __device__ __forceinline__ uint64_t null_key(uint64_t seed, uint32_t p, uint64_t t, int key_bits)
@@ -172,3 +177,149 @@ hipError_t null_score_launch(int64_t n_ref, const int64_t *row_ptr, const int64_
 }
 
 }  // namespace nabo
+
+// ---- C ABI (include/nabo_knn.h: nabo_score_null, nabo_score_null_edges) ----------------------------------------------------
+using nabo::api_fail;
+using nabo::DevBuf;
+using nabo::use_device;
+
+namespace {
+
+// row_ptr != NULL: edges in CSR by reference node (edge_r unused); row_ptr == NULL: COO, E = n_edges, the CSR is built
+// on the device by a stable sort (csr_build.hip).
+int score_null_impl(int32_t device, int64_t n_ref, const int64_t *row_ptr, int64_t n_edges, const int64_t *edge_r,
+                    const int64_t *edge_t, const double *edge_w, int64_t n_t, const uint8_t *group, int32_t n_perm,
+                    uint64_t seed, int32_t key_bits, double multiplier, double *out_obs, int64_t *out_nge,
+                    double *out_mean, double *out_sd, int64_t *out_sizes)
+{
+    const bool coo = row_ptr == nullptr;
+    if (!group || !out_obs || !out_nge || !out_mean || !out_sd) return api_fail(NABO_E_INVALID, "NULL argument");
+    if (n_ref < 1 || n_t < 1) return api_fail(NABO_E_INVALID, "empty operand");
+    if (n_perm < 1 || n_perm > 4096) return api_fail(NABO_E_UNSUPPORTED, "n_perm=%d: 1..4096 supported", n_perm);
+    if (key_bits < 8 || key_bits > 64 || key_bits % 8) return api_fail(NABO_E_INVALID, "key_bits must be 8, 16, .., 64");
+    if (n_ref >= 0x7FFFFFFFll) return api_fail(NABO_E_UNSUPPORTED, "n_ref too large for one launch");
+    const int64_t E = coo ? n_edges : row_ptr[n_ref];
+    if (coo) {
+        if (E < 0) return api_fail(NABO_E_INVALID, "n_edges < 0");
+        if (E >= 0xFFFFFFFFll) return api_fail(NABO_E_UNSUPPORTED, "n_edges=%lld: fewer than 2^32-1 supported", (long long)E);
+        if (E > 0 && !edge_r) return api_fail(NABO_E_INVALID, "NULL edge arrays");
+    } else {
+        if (row_ptr[0] != 0 || E < 0) return api_fail(NABO_E_INVALID, "row_ptr must start at 0");
+        for (int64_t r = 0; r < n_ref; ++r)
+            if (row_ptr[r + 1] < row_ptr[r]) return api_fail(NABO_E_INVALID, "row_ptr must be non-decreasing");
+        if (E > 0 && (!edge_t || !edge_w)) return api_fail(NABO_E_INVALID, "NULL edge arrays");
+        for (int64_t e = 0; e < E; ++e)
+            if (edge_t[e] < 0 || edge_t[e] >= n_t) return api_fail(NABO_E_INVALID, "edge_t[%lld] out of range", (long long)e);
+    }
+    if (E > 0 && (!edge_t || !edge_w)) return api_fail(NABO_E_INVALID, "NULL edge arrays");
+    int64_t n_a = 0;
+    for (int64_t t = 0; t < n_t; ++t) n_a += group[t] ? 1 : 0;
+    if (n_a < 1) return api_fail(NABO_E_INVALID, "the group of interest is empty");
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int P = n_perm, W = (P + 1 + 31) / 32;
+    hipStream_t st = nullptr;
+    DevBuf d_rp, d_et, d_ew, d_grp, d_pre, d_hist, d_bits, d_nl, d_obs, d_nge, d_mean, d_sd;
+    DevBuf c_r, c_t, c_w, c_ka, c_kb, c_pa, c_pb, c_tmp, c_flag;          // COO staging + sort scratch
+    if ((rc = d_rp.reserve((size_t)(n_ref + 1) * 8)) || (rc = d_et.reserve((size_t)(E ? E : 1) * 8)) ||
+        (rc = d_ew.reserve((size_t)(E ? E : 1) * 8)) || (rc = d_grp.reserve((size_t)n_t)) ||
+        (rc = d_pre.reserve((size_t)P * 8)) || (rc = d_hist.reserve((size_t)P * 256 * 4)) ||
+        (rc = d_bits.reserve((size_t)n_t * W * 4)) || (rc = d_nl.reserve((size_t)P * 8)) ||
+        (rc = d_obs.reserve((size_t)n_ref * 8)) || (rc = d_nge.reserve((size_t)n_ref * 8)) ||
+        (rc = d_mean.reserve((size_t)n_ref * 8)) || (rc = d_sd.reserve((size_t)n_ref * 8)))
+        return rc;
+    if (!coo) {
+        HIP_TRY(hipMemcpyAsync(d_rp.p, row_ptr, (size_t)(n_ref + 1) * 8, hipMemcpyHostToDevice, st));
+        if (E) {
+            HIP_TRY(hipMemcpyAsync(d_et.p, edge_t, (size_t)E * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_ew.p, edge_w, (size_t)E * 8, hipMemcpyHostToDevice, st));
+        }
+    } else {
+        size_t tb = 0;
+        HIP_TRY(nabo::csr_sort_temp_bytes(E, n_ref, &tb));
+        const size_t e1 = (size_t)(E ? E : 1);
+        if ((rc = c_r.reserve(e1 * 8)) || (rc = c_t.reserve(e1 * 8)) || (rc = c_w.reserve(e1 * 8)) ||
+            (rc = c_ka.reserve(e1 * 4)) || (rc = c_kb.reserve(e1 * 4)) || (rc = c_pa.reserve(e1 * 4)) ||
+            (rc = c_pb.reserve(e1 * 4)) || (rc = c_tmp.reserve(tb ? tb : 1)) || (rc = c_flag.reserve(sizeof(unsigned int))))
+            return rc;
+        if (E) {
+            HIP_TRY(hipMemcpyAsync(c_r.p, edge_r, (size_t)E * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(c_t.p, edge_t, (size_t)E * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(c_w.p, edge_w, (size_t)E * 8, hipMemcpyHostToDevice, st));
+        }
+        HIP_TRY(nabo::csr_build_launch(c_r.as<int64_t>(), c_t.as<int64_t>(), c_w.as<double>(), E, n_ref, n_t,
+                                       c_ka.as<uint32_t>(), c_pa.as<uint32_t>(), c_kb.as<uint32_t>(), c_pb.as<uint32_t>(),
+                                       c_tmp.p, tb, d_rp.as<int64_t>(), d_et.as<int64_t>(), d_ew.as<double>(),
+                                       c_flag.as<unsigned int>(), st));
+        unsigned int bad = 0;
+        HIP_TRY(hipMemcpyAsync(&bad, c_flag.p, sizeof(bad), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (bad) return api_fail(NABO_E_INVALID, "%s out of range", (bad & 1u) ? "edge_ref" : "edge_t");
+        DevBuf *stage[] = {&c_r, &c_t, &c_w, &c_ka, &c_kb, &c_pa, &c_pb, &c_tmp};
+        for (DevBuf *b : stage) b->release();
+    }
+    HIP_TRY(hipMemcpyAsync(d_grp.p, group, (size_t)n_t, hipMemcpyHostToDevice, st));
+    // radix select of the n_A-th smallest key of every permutation, 8 bits per pass
+    std::vector<uint64_t> prefix((size_t)P, 0), below((size_t)P, 0), rank((size_t)P, (uint64_t)n_a);
+    std::vector<int64_t> sizes((size_t)P, 0);
+    std::vector<unsigned int> hist((size_t)P * 256);
+    for (int done = 0; done < key_bits; done += 8) {
+        HIP_TRY(hipMemcpyAsync(d_pre.p, prefix.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_hist.p, 0, (size_t)P * 256 * 4, st));
+        HIP_TRY(nabo::null_hist_launch(n_t, P, seed, key_bits, d_pre.as<uint64_t>(), done, d_hist.as<unsigned int>(), st));
+        HIP_TRY(hipMemcpyAsync(hist.data(), d_hist.p, (size_t)P * 256 * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int p = 0; p < P; ++p) {
+            const unsigned int *h = &hist[(size_t)p * 256];
+            uint64_t cum = 0;
+            int b = 0;
+            for (; b < 256; ++b) {
+                if (cum + h[b] >= rank[p]) break;
+                cum += h[b];
+            }
+            if (b == 256) return api_fail(NABO_E_HIP, "internal: radix select lost rank (permutation %d)", p);
+            prefix[p] = (prefix[p] << 8) | (uint64_t)b;
+            below[p] += cum;
+            rank[p] -= cum;
+            if (done + 8 >= key_bits) sizes[p] = (int64_t)(below[p] + h[b]);      // keys <= T_p (ties at T_p included)
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(d_pre.p, prefix.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));        // thresholds T_p
+    HIP_TRY(hipMemcpyAsync(d_nl.p, sizes.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(nabo::null_label_launch(n_t, P, W, seed, key_bits, d_pre.as<uint64_t>(), d_grp.as<uint8_t>(), d_bits.as<uint32_t>(), st));
+    HIP_TRY(nabo::null_score_launch(n_ref, d_rp.as<int64_t>(), d_et.as<int64_t>(), d_ew.as<double>(), P, W,
+                                    d_bits.as<uint32_t>(), d_nl.as<int64_t>(), n_a, multiplier, d_obs.as<double>(),
+                                    d_nge.as<int64_t>(), d_mean.as<double>(), d_sd.as<double>(), st));
+    HIP_TRY(hipMemcpyAsync(out_obs, d_obs.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_nge, d_nge.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_mean, d_mean.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_sd, d_sd.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (out_sizes) memcpy(out_sizes, sizes.data(), (size_t)P * 8);
+    return NABO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nabo_score_null(int32_t device, int64_t n_ref, const int64_t *row_ptr, const int64_t *edge_t,
+                    const double *edge_w, int64_t n_t, const uint8_t *group, int32_t n_perm, uint64_t seed,
+                    int32_t key_bits, double multiplier, double *out_obs, int64_t *out_nge, double *out_mean,
+                    double *out_sd, int64_t *out_sizes)
+{
+    if (!row_ptr) return api_fail(NABO_E_INVALID, "NULL argument");
+    return score_null_impl(device, n_ref, row_ptr, 0, nullptr, edge_t, edge_w, n_t, group, n_perm, seed, key_bits,
+                           multiplier, out_obs, out_nge, out_mean, out_sd, out_sizes);
+}
+
+int nabo_score_null_edges(int32_t device, int64_t n_ref, int64_t n_edges, const int64_t *edge_ref, const int64_t *edge_t,
+                          const double *edge_w, int64_t n_t, const uint8_t *group, int32_t n_perm, uint64_t seed,
+                          int32_t key_bits, double multiplier, double *out_obs, int64_t *out_nge, double *out_mean,
+                          double *out_sd, int64_t *out_sizes)
+{
+    return score_null_impl(device, n_ref, nullptr, n_edges, edge_ref, edge_t, edge_w, n_t, group, n_perm, seed, key_bits,
+                           multiplier, out_obs, out_nge, out_mean, out_sd, out_sizes);
+}
+
+}  // extern "C"

@@ -65,35 +65,13 @@
 #include <vector>
 
 #include "../../include/nabo_knn.h"
-
-namespace nabo {
-hipError_t merge_parts_launch(const double *parts_d, const int64_t *parts_i, int n_parts, int64_t m, int kp, int k,
-                              int drop, int64_t *out_idx, double *out_dist, hipStream_t st);
-hipError_t gather_rows_launch(const double *X, const uint32_t *rows, int64_t nrows, int g, double *out, hipStream_t st);
-// api.hip
-int api_fail(int code, const char *fmt, ...);
-int index_device(const nabo_index *ix);
-int index_g(const nabo_index *ix);
-int64_t index_n(const nabo_index *ix);
-int index_metric(const nabo_index *ix);
-bool index_can_emit_candidates(const nabo_index *ix);
-void index_set_shard_mode(nabo_index *ix, bool on);
-void index_set_cand_slack(nabo_index *ix, int s);
-}  // namespace nabo
+#include "host_common.h"
 
 namespace {
 
 using nabo::api_fail;
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess) {                                                                   \
-            (void)hipGetLastError(); /* (the thread's sticky copy: a later launch check must not report THIS failure) */ \
-            return api_fail(e__ == hipErrorOutOfMemory ? NABO_E_NOMEM : NABO_E_HIP, "%s failed: %s", \
-                            #expr, hipGetErrorString(e__));                                        \
-        }                                                                                          \
-    } while (0)
+using nabo::DevBuf;
+using nabo::use_device;
 
 // ---- librccl.so, resolved at run time -------------------------------------------------------------------
 struct Rccl {
@@ -177,27 +155,6 @@ struct LoopHub {
     bool aborted = false;
     std::vector<const void *> ptr;
     std::vector<int64_t> vals;          // [n][NABO_AGREE_MAX]
-};
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    int reserve(size_t bytes)
-    {
-        if (bytes <= cap) return NABO_OK;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        const size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { p = nullptr; return api_fail(NABO_E_NOMEM, "hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e)); }
-        cap = want;
-        return NABO_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
 double now_s()
@@ -566,12 +523,6 @@ __global__ void widen_kernel(const int64_t *__restrict__ si, const double *__res
     od[e] = c < kq ? sd[r * kq + c] : __builtin_inf();
 }
 
-int use_dev(int device)
-{
-    HIP_TRY(hipSetDevice(device));
-    return NABO_OK;
-}
-
 int comm_alloc(nabo_comm **out, int kind, int device, int rank, int world)
 {
     nabo_comm *c = new (std::nothrow) nabo_comm();
@@ -786,7 +737,7 @@ int nabo_comm_allreduce_max_f64(nabo_comm *c, double *value)
 {
     if (!c || !value) return api_fail(NABO_E_INVALID, "NULL argument");
     if (c->aborted) return comm_dead(c);
-    int rc = use_dev(c->device);
+    int rc = use_device(c->device);
     if (rc) return rc;
     if (c->world == 1) return NABO_OK;
     if ((rc = c->scratch.reserve(64))) { comm_abort(c); return rc; }
@@ -871,7 +822,7 @@ static int sharded_query_impl(nabo_comm *c, nabo_index *ix, const double *X, int
     if (!ix || !X || !out_idx || !out_dist) rc = api_fail(NABO_E_INVALID, "NULL argument");
     else if (m < 1 || k < 1) rc = api_fail(NABO_E_INVALID, "bad shape m=%lld k=%d", (long long)m, k);
     else if (nabo::index_device(ix) != c->device) rc = api_fail(NABO_E_INVALID, "index and communicator live on different devices");
-    else rc = use_dev(c->device);
+    else rc = use_device(c->device);
     const int64_t mr = m > 0 ? (m + N - 1) / N : 0, m_pad = mr * N, row0 = (int64_t)c->rank * mr;
     // 2-D layout: R reference pieces x N / R target slices; my group = the R ranks [gfirst, gfirst + R) that hold the
     // pieces for my slice, rows [s0, s0 + R mr) (ms of them exist).  R = N: one group, the whole batch (the 1-D form).

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/nabo_knn.h"
+#include "../../nabo_amd/csrc/launch.h"
 #include "hip_shim.h"
 
 thread_local dim3 blockIdx, threadIdx, blockDim;

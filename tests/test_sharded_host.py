@@ -35,7 +35,8 @@ QUERY_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_v
 @pytest.fixture(scope="module")
 def host():
     srcs = [os.path.join(REPO, "nabo_amd", "csrc", "sharded.hip"), os.path.join(SHIM, "host_index.cpp")]
-    deps = srcs + [os.path.join(SHIM, "hip_shim.h"), os.path.join(REPO, "include", "nabo_knn.h")]
+    deps = srcs + [os.path.join(SHIM, "hip_shim.h"), os.path.join(REPO, "include", "nabo_knn.h"),
+                   os.path.join(REPO, "nabo_amd", "csrc", "launch.h"), os.path.join(REPO, "nabo_amd", "csrc", "host_common.h")]
     os.makedirs(os.path.dirname(SO), exist_ok=True)
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-x", "c++", "-DNABO_SHARDED_HOST", "-I" + SHIM]
