@@ -61,8 +61,8 @@ def _compile(args):
 
 
 def build(force=False, verbose=False, extra=None, out=None):
-    """out: build a VARIANT of the library (extra compiler flags) into another file, with its own object directory --
-    tools/ab/*.sh load it through NABO_KNN_SO; the product's libnabo_knn.so is never touched by experiments."""
+    """out: build ANOTHER copy of the library (another commit's sources, extra compiler flags) into that file, with its own
+    object directory -- a parent / branch A/B loads it through NABO_KNN_SO; the product's libnabo_knn.so is never touched."""
     extra = list(extra or [])
     global SO
     so_saved = SO
@@ -97,7 +97,7 @@ def _build(force, verbose, extra, objdir):
 
 
 if __name__ == "__main__":
-    # python -m nabo_amd._build [--force] [--verbose] [--out tools/ab/x.so -DFLAG ... [-- more hipcc flags]]
+    # python -m nabo_amd._build [--force] [--verbose] [--out other.so -DFLAG ... [-- more hipcc flags]]
     args = sys.argv[1:]
     out = args[args.index("--out") + 1] if "--out" in args else None
     extra = [a for a in args if a.startswith("-D")] + (args[args.index("--") + 1:] if "--" in args else [])

@@ -4,7 +4,7 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# NABO_KNN_SO: load another build of the library (kernel A/B experiments, tools/ab) WITHOUT overwriting the product's
+# NABO_KNN_SO: load another build of the library (a parent / branch A/B; _build.build(out=...)) WITHOUT overwriting the product's
 SO_PATH = os.environ.get("NABO_KNN_SO") or os.path.join(HERE, "libnabo_knn.so")
 
 EUCLIDEAN = 0

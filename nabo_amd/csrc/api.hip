@@ -33,7 +33,7 @@ int pick_ksteps(int g)
 // Tuning options of an index (nabo_index_set_option; the defaults are the product's behaviour).  EVERY setting returns the
 // same bits -- an option chooses how a launch is cut or which filter pass answers a row, never what the answer is.  The
 // library reads two environment variables, once, in nabo_index_create: NABO_L2_MODE and NABO_CANBERRA_MODE (which first
-// filter); experiments builds (tools/ab) also take every option below as NABO_OPT_<NAME> (options_from_env).
+// filter).
 struct Options {
     int splits = 0;            // reference splits of a filter launch (0: the cost model decides)
     int tail_split = 1;        // the last, partially filled round of workgroups gets its own split count
@@ -75,20 +75,6 @@ bool option_set(Options &o, const char *name, int64_t value)
         }
     return false;
 }
-
-#ifdef NABO_EXPERIMENTS
-void options_from_env(Options &o)
-{
-    for (const OptionName &e : OPTION_NAMES) {
-        char key[64] = "NABO_OPT_";
-        size_t k = strlen(key);
-        for (const char *c = e.name; *c && k + 1 < sizeof(key); ++c) key[k++] = (char)(*c >= 'a' && *c <= 'z' ? *c - 32 : *c);
-        key[k] = 0;
-        const char *v = getenv(key);
-        if (v && *v) o.*(e.field) = atoi(v);
-    }
-}
-#endif
 
 constexpr int RERUN_WIDE = 2;     // nabo_index::rerun: the set of the frame that sends rows to the 64-entry lists
 
@@ -383,9 +369,6 @@ int nabo_index_create(nabo_index **out, int32_t device, int64_t n_ref, int32_t g
     ix->metric = metric;
     ix->f = dist_factor;
     ix->base = ref_index_base;
-#ifdef NABO_EXPERIMENTS
-    options_from_env(ix->opt);
-#endif
     {   // NABO_CANBERRA_MODE = exact | swar | bits pins the modified-Canberra path (default: by the size of the reference set)
         const char *cmode = getenv("NABO_CANBERRA_MODE");
         ix->cb_mode = !cmode ? 0 : strcmp(cmode, "exact") == 0 ? 1 : strcmp(cmode, "swar") == 0 ? 2 : strcmp(cmode, "bits") == 0 ? 3 : 0;
@@ -860,7 +843,6 @@ struct Query {
     unsigned int n_fail = 0;         // set by the route: counters[0], [1], [3] of nabo_index_last_stats
     int S = 1;
     int64_t n_wg = 0;
-    bool timing_only = false;        // debug_ablate: the route stopped behind the filter and set ms[1] itself
 };
 
 // Rows of the exact kernels' distance workspace: ~1 GiB of float64 rows, at least one, at most `rows` and `cap`.
@@ -1136,15 +1118,6 @@ static int query_l2(nabo_index *ix, Query &q)
     bool beside = false;
     if ((rc = l2_filter(ix, q, P, part, (seedable && ix->pass_level == 1) ? ix->seed_tau : nullptr, &beside))) return rc;
     HIP_TRY(hipEventRecord(ix->ev[2], st));
-    if (nabo::debug_ablate() != 0) {     // experiments builds only: kernel-timing runs, results are garbage
-        for (int i = 3; i <= 5; ++i) HIP_TRY(hipEventRecord(ix->ev[i], st));
-        HIP_TRY(hipStreamSynchronize(st));
-        float tt = 0;
-        HIP_TRY(hipEventElapsedTime(&tt, ix->ev[1], ix->ev[2]));
-        ix->ms[1] = tt;
-        q.timing_only = true;
-        return NABO_OK;
-    }
     float *fail_seed = nullptr;          // seeds for a seeded pass of the rows that fail (pass 0 on the l2c kernel)
     if (seedable && ix->pass_level == 0) {
         if ((rc = ix->failseed.reserve((size_t)m * sizeof(float)))) return rc;
@@ -1287,8 +1260,6 @@ static int canberra_filter(nabo_index *ix, Query &q, const CbPlan &C, bool *done
                            (rc = p.tau->reserve((size_t)p.rows * p.SL * sizeof(float) + 16))))
             return rc;
     if ((rc = ix->fails.reserve((size_t)m * sizeof(uint32_t)))) return rc;
-    const bool dbg_counts = (nabo::debug_ablate() & 4) != 0;
-    if (dbg_counts) HIP_TRY(hipMemsetAsync(ix->cand_tau.as<float>() + (size_t)C.rows_main * part[0].SL, 0, 8, st));
     HIP_TRY(hipMemsetAsync(ix->cbflag.p, 0, 4 * sizeof(unsigned int), st));
     unsigned int *d_failcnt = ix->cbflag.as<unsigned int>() + 1, *d_flag = ix->cbflag.as<unsigned int>();
     HIP_TRY(nabo::cbf_pack_targets_launch(q.dX, m, g, gp, ix->f, ix->xpk.as<float>(), d_flag, st));
@@ -1312,13 +1283,6 @@ static int canberra_filter(nabo_index *ix, Query &q, const CbPlan &C, bool *done
                                             p.idx->as<uint32_t>(), p.tau->as<float>(), st));
     }
     HIP_TRY(hipEventRecord(ix->ev[2], st));
-    if (dbg_counts) {
-        unsigned int c2[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(c2, ix->cand_tau.as<float>() + (size_t)C.rows_main * part[0].SL, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        fprintf(stderr, "[nabo debug] canberra filter (main launch): splits=%d survivors=%u (%.1f per row) batches=%u\n",
-                C.Sf, c2[0], (double)c2[0] / (double)C.rows_main, c2[1]);
-    }
     for (auto &p : part)
         if (p.rows > 0)
             HIP_TRY(nabo::refine_launch(q.dX, p.row0, p.row0 + p.rows, ix->dY, g, p.idx->as<uint32_t>(), p.tau->as<float>(), p.SL,
@@ -1467,7 +1431,7 @@ static int query_body(nabo_index *ix, const double *X, int32_t x_on_device, int6
     }
     HIP_TRY(hipEventRecord(ix->ev[0], st));
     rc = exact_route ? query_exact(ix, q) : ix->metric != NABO_METRIC_MOD_CANBERRA ? query_l2(ix, q) : query_canberra(ix, q);
-    if (rc || q.timing_only) return rc;
+    if (rc) return rc;
     return finish_query(ix, q, out_idx, out_dist, out_on_device);
 }
 

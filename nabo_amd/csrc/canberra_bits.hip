@@ -41,16 +41,10 @@
 
 namespace nabo {
 
-#ifndef NABO_CBB_B
-#define NABO_CBB_B 64
-#endif
-constexpr int CBB_B = NABO_CBB_B;         // quantile buckets per dimension (survivors of the count: 7e-3 of the pairs at 32, 2.6e-3 at 64)
+constexpr int CBB_B = 64;         // quantile buckets per dimension (survivors of the count: 7e-3 of the pairs at 32, 2.6e-3 at 64)
 constexpr int CBB_ROWS = CBB_B;           // STORED cumulative rows per dimension: rows 1 .. CBB_B (row 0, the empty set, is a zero row in LDS)
 constexpr int CBB_BLK = 2048;             // references per block: 64 lanes x 32 bits
 constexpr int CBB_T = 8;                  // target rows per wave (six count planes each, in registers: < 128 VGPRs per wave)
-#ifndef NABO_CBB_TB
-#define NABO_CBB_TB 8
-#endif
 constexpr int CBB_NW = 16;                // waves per workgroup (four per SIMD): they share the LDS copy of the table rows
 constexpr int CBB_WLN = 128;              // work-list ring of a wave (entries)
 constexpr int CBB_DIM_BYTES = CBB_ROWS * 256;                          // the rows of one dimension of one block: 16 KiB
@@ -65,13 +59,8 @@ static_assert(CBB_PAIR_BYTES % 1024 == 0, "whole DMA pieces");
 // (Tried in round 4 and dropped: an L2 prefetch of the pair three steps ahead -- a dword per lane and 128-byte line by LDS-DMA
 // into a scratch row, vmcnt leaving it in flight for a step: 544 -> 571 ms.  The pass is not waiting for table misses; its
 // SIMDs issue an instruction every 4.9 cycles, 82 % of what they can: what counts is the instruction count.)
-#ifndef NABO_CBB_SEED
-#define NABO_CBB_SEED 512
-#endif
-#ifndef NABO_CBB_DMAW
-#define NABO_CBB_DMAW 4          // (16 waves x 2 pieces: 527 ms at 1M x 1M; 8 x 4: 507; 4 x 8: 503; 2 x 16: 512)
-#endif
-constexpr int CBB_DMAW = NABO_CBB_DMAW;                                // waves 0 .. DMAW-1 request the table pieces
+// (16 waves x 2 pieces: 527 ms at 1M x 1M; 8 x 4: 507; 4 x 8: 503; 2 x 16: 512)
+constexpr int CBB_DMAW = 4;                                            // waves 0 .. DMAW-1 request the table pieces
 constexpr int CBB_PPW = CBB_PIECES / CBB_DMAW;                         // consecutive pieces a DMA wave requests per pair
 static_assert(CBB_PIECES % CBB_DMAW == 0 && CBB_DMAW <= CBB_NW && CBB_PPW >= 1 && (CBB_PPW <= 4 || CBB_PPW % 4 == 0), "pieces per DMA wave: up to four per statement (13-bit immediate offset)");
 static_assert(CBB_BUF_BYTES <= CBB_BUF1 && CBB_BUF_BYTES <= 65536, "row addresses (16 bits) and the buffer bit must not overlap");
@@ -201,12 +190,6 @@ template <int NP>
 __device__ __forceinline__ void cbb_glds16(const void *gbase /* wave-uniform */, uint32_t lane_off, uint32_t lds_dst)
 {
     static_assert(NP >= 1 && NP <= 4, "immediate offsets up to 3072");
-#ifdef NABO_CBB_M0PER            // (A/B: the immediate offset moving the global address only)
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(lane_off), "s"(gbase), "s"(lds_dst) : "memory", "m0");
-#pragma unroll
-    for (int pc = 1; pc < NP; ++pc)
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3" : : "v"(lane_off), "s"(gbase), "s"(lds_dst + pc * 1024u), "n"(pc * 1024) : "memory", "m0");
-#else
     if constexpr (NP == 1)
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(lane_off), "s"(gbase), "s"(lds_dst) : "memory", "m0");
     else if constexpr (NP == 2)
@@ -217,15 +200,9 @@ __device__ __forceinline__ void cbb_glds16(const void *gbase /* wave-uniform */,
                      "global_load_lds_dwordx4 %0, %1 offset:2048\n\tglobal_load_lds_dwordx4 %0, %1 offset:3072"
                      : : "v"(lane_off), "s"(gbase), "s"(lds_dst) : "memory", "m0");
     static_assert(NP != 3, "1, 2 or 4 pieces");
-#endif
 }
 __device__ __forceinline__ void cbb_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-#ifdef NABO_CBB_NOBARRIER         // timing experiment (garbage results): the steps run without their workgroup barrier
-#define CBB_STEP_BARRIER() do { } while (0)
-#else
-#define CBB_STEP_BARRIER() __syncthreads()
-#endif
 typedef uint32_t cbb_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t cbb_u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const cbb_u32x4 cbb_lds_u4;
@@ -402,13 +379,7 @@ void cbb_filter_kernel(const float2 *__restrict__ xq, const uint16_t *__restrict
     const uint32_t lane_off = (uint32_t)lane * 16u;
     const bool dma_wave = CBB_DMAW == CBB_NW || wave < CBB_DMAW;
     const uint32_t fdst = (uint32_t)wave * (uint32_t)(CBB_PPW * 1024);
-#ifdef NABO_CBB_NODMA            // timing experiment (garbage results): only the very first pair is ever fetched
-    bool fetched = false;
-#endif
     auto fetch = [&](int buf) {
-#ifdef NABO_CBB_NODMA
-        if (!fetched)
-#endif
         if (dma_wave) {
             if constexpr (CBB_PPW <= 4) {
                 cbb_glds16<CBB_PPW>(fsrc, lane_off, ((uint32_t)buf << 16) + fdst);
@@ -418,12 +389,6 @@ void cbb_filter_kernel(const float2 *__restrict__ xq, const uint16_t *__restrict
                     cbb_glds16<4>(fsrc + q4 * 4096, lane_off, ((uint32_t)buf << 16) + fdst + (uint32_t)(q4 * 4096));
             }
         }
-#ifdef NABO_CBB_DMA2X            // timing experiment (same results): every piece is requested twice
-        if (dma_wave) cbb_glds16<CBB_PPW>(fsrc, lane_off, ((uint32_t)buf << 16) + fdst);
-#endif
-#ifdef NABO_CBB_NODMA
-        fetched = true;
-#endif
         fsrc += CBB_PAIR_BYTES;
     };
     if (b_begin < b_end) fetch(0);                           // (an empty split requests nothing: its range may lie past the table)
@@ -442,7 +407,7 @@ void cbb_filter_kernel(const float2 *__restrict__ xq, const uint16_t *__restrict
     // first block's count then lets a fraction of its references through instead of all, and its extraction skips the seeded words.
     // (Measured, same box: 1M x 1M kernel 504 -> 486 / 480 / 460-470 / 462 ms with 128 / 256 / 512 / 1024 seeds, 100k x 100k
     // 16.3 -> 13.0 / 11.5 / 10.6 / 11.4: the later blocks gain from the tighter start too.)
-    constexpr int CBB_SEED = NABO_CBB_SEED;                  // references, a multiple of 128 (whole lanes of the block), <= 2048
+    constexpr int CBB_SEED = 512;                            // references, a multiple of 128 (whole lanes of the block), <= 2048
     static_assert(CBB_SEED % 128 == 0 && CBB_SEED >= 0 && CBB_SEED <= CBB_BLK, "seeded references: whole lanes of the first block");
     if (CBB_SEED > 0 && b_begin < b_end) {
         const int64_t j0 = b_begin * CBB_BLK;
@@ -547,7 +512,7 @@ void cbb_filter_kernel(const float2 *__restrict__ xq, const uint16_t *__restrict
                 __builtin_amdgcn_sched_barrier(0);                                                                           \
             }                                                                                                                \
             cbb_dma_wait();                                                                                                  \
-            CBB_STEP_BARRIER();                                                                                              \
+            __syncthreads();                                                                                                 \
             buf ^= 1;                                                                                                        \
         }
         int dp0 = 0;

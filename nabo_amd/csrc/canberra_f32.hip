@@ -242,7 +242,7 @@ __global__ __launch_bounds__(64, 2)
 void cbf_filter_kernel(const float2 *__restrict__ xq, const uint2 *__restrict__ xh, int64_t m,
                        const float *__restrict__ yrow, const uint32_t *__restrict__ ych, int64_t n, int g,
                        const uint8_t *__restrict__ mask, int64_t n_chunks, int64_t chunks_per_split, float slack,
-                       float plateau, uint32_t *__restrict__ cand_idx, float *__restrict__ cand_tau, int dbg)
+                       float plateau, uint32_t *__restrict__ cand_idx, float *__restrict__ cand_tau)
 {
     constexpr int L = 32 * EPL, CAP = L + 16 * EPL;     // kept + pending entries per list
     constexpr int GH = GP / 4;           // packed words: four dimensions each
@@ -309,11 +309,6 @@ void cbf_filter_kernel(const float2 *__restrict__ xq, const uint2 *__restrict__ 
         const uint32_t e = act ? (uint32_t)wl_t[slot] : 0u;
         wl_head = (wl_head + nb) & (WLN - 1);
         wl_n -= nb;
-        if ((dbg & 4) && lane == 0) {                       // experiments: survivors / batches of the whole launch
-            unsigned int *ctr = reinterpret_cast<unsigned int *>(cand_tau + m * gridDim.y);
-            atomicAdd(ctr, (unsigned int)nb);
-            atomicAdd(ctr + 1, 1u);
-        }
         const int t_p = (int)(e & 0xFFu);
         const float2 *xp = xf + t_p * GPS;                                               // LDS, lane-varying row
         const float4 *yp = reinterpret_cast<const float4 *>(yrow + (int64_t)j * GP);     // 4 dimensions per 16 bytes
@@ -412,7 +407,7 @@ void cbf_filter_kernel(const float2 *__restrict__ xq, const uint2 *__restrict__ 
                 sm[c] = __builtin_amdgcn_ballot_w64(inw[c] >= thr_in) & vmask[c];
                 any |= sm[c];
             }
-            if (any != 0 && !(dbg & 1)) {
+            if (any != 0) {
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
                     const uint64_t bm = sm[c];
@@ -513,7 +508,7 @@ static hipError_t cbf_launch_one(const float *xq, const void *xh, int64_t m, con
     dim3 grid((unsigned)((m + T - 1) / T), S), block(64);
     hipLaunchKernelGGL(kern, grid, block, lds, st, reinterpret_cast<const float2 *>(xq),
                        reinterpret_cast<const uint2 *>(xh), m, ycf, reinterpret_cast<const uint32_t *>(ych), n, g, mask,
-                       n_chunks, cps, slack, plateau, cand_idx, cand_tau, debug_ablate());
+                       n_chunks, cps, slack, plateau, cand_idx, cand_tau);
     return hipGetLastError();
 }
 

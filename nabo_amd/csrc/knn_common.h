@@ -8,13 +8,6 @@
 // split, all ones = "no reference"; api.hip raises the split count of larger sets
 #define NABO_LIST_SPLIT_REFS (((int64_t)1 << 25) - 1)
 
-// A filter launch cut into PIECES (l2c_topk.hip, experiments builds; the host side was removed from api.hip): device arrays.
-//   pieces   [n_pieces] int4 (column-workgroup, list slot of that column, first reference tile, end tile), one workgroup each,
-//            longest first
-//   ranges   [columns x S] int4 (first tile, end tile, tournament tiles, tiles per tournament group) per (column, slot);
-//            an unused slot is (0, 0, 0, 0)
-struct L2cPieces { const int *pieces; int n_pieces; const int *ranges = nullptr; int rows_per_col = 0; };
-
 namespace nabo {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -22,19 +15,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WAVE = 64;
 
-// NABO_DEBUG_ABLATE (kernel-timing experiments whose RESULTS ARE GARBAGE: no-hit runs, L2-resident streams, counters)
-// exists only in builds made with -DNABO_EXPERIMENTS (tools/ab builds such variants next to the product through
-// `python -m nabo_amd._build --out ...`; besides it they only read the options from NABO_OPT_<NAME>); the shipped
-// library never reads the variable.
-static inline int debug_ablate()
-{
-#ifdef NABO_EXPERIMENTS
-    static const int v = getenv("NABO_DEBUG_ABLATE") ? atoi(getenv("NABO_DEBUG_ABLATE")) : 0;
-    return v;
-#else
-    return 0;
-#endif
-}
 constexpr int TILE = 32;                 // cells per MFMA tile (32x32x2 f32)
 
 // ---------------------------------------------------------------------------------------
@@ -65,7 +45,7 @@ __device__ __forceinline__ bool kv_less(K ka, uint32_t va, K kb, uint32_t vb)
 
 // Lane exchange with lane ^ m for the sorting networks.  __shfl_xor is ds_bpermute_b32: an LDS round trip (~120 cycles)
 // per exchange, and a bitonic sort is a chain of 21 DEPENDENT exchanges -- a 64-entry sort measured 5400 cycles
-// (tools: -DNABO_LISTS_PROF), almost all of it waiting.  For m < 32 the data-parallel-primitive forms are used instead
+// (shader-clock sums of an instrumented build), almost all of it waiting.  For m < 32 the data-parallel-primitive forms are used instead
 // (a VALU operand modifier: no LDS, no address register): quad_perm for m = 1, 2; two bank-masked row shifts for
 // m = 4; row_ror:8 for m = 8; ds_swizzle (bit-mask mode, crossbar only) for m = 16; m = 32 keeps the permute.
 // `m` must be a compile-time constant after unrolling (the dpp controls are immediates).

@@ -47,7 +47,7 @@ struct RefTile {
 // 4 KB blocks in the scalar offset -- from SGPRs.  With flat `global_load`s hipcc keeps 64-bit per-lane addresses in
 // VGPR pairs for every load past the first 4 KB of a tile (and for all of them if asked nicely), and on gfx950, where
 // the fp32 MFMA shares the vector ALU's operand paths, each such load costs ~20 ms per step at 1M x 1M
-// (tools/ab: 7 of 11 loads per tile with VGPR-pair addresses 785 ms, all 11: 867 ms).
+// (A/B: 7 of 11 loads per tile with VGPR-pair addresses 785 ms, all 11: 867 ms).
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256, (R * KSTEPS <= 25 && EPL == 1 ? 3 : R * KSTEPS
                                                                                   uint32_t *__restrict__ cand_idx,
                                                                                   float *__restrict__ cand_key,
                                                                                   float *__restrict__ cand_tau,
-                                                                                  int dbg /* ablation, 0 in production */)
+                                                                                  int dbg /* always 0: see tau0 */)
 {
     constexpr int L2_NREC = l2_nrec(R, EPL);
     using C = ListCfg<EPL, ROWN, R, L2_NREC>;
@@ -202,6 +202,8 @@ __global__ __launch_bounds__(256, (R * KSTEPS <= 25 && EPL == 1 ? 3 : R * KSTEPS
     }
     unsigned char *wl = smem_raw + (size_t)wave * C::BYTES;          // this wave's lists (topk_lists.h)
     float tauv[R];
+    // (dbg, a former ablation switch, stays a run-time 0: folded away the 1M x 1M kernel measured 690.5 / 692.6 ms against
+    // the parent's 690.3 / 690.8 in one call, beyond the parent's own spread)
     const float tau0 = (dbg & 1) ? -__builtin_inff() : __builtin_inff();
 #pragma unroll
     for (int rb = 0; rb < R; ++rb) tauv[rb] = tau0;
@@ -247,14 +249,13 @@ template <int KSTEPS, int R, int EPL, int ROWN>
 static hipError_t launch_one(const float *Xpk, const float *Ypk, int tiles_per_split, int S, int gx, int64_t tile_off,
                              int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau, hipStream_t st)
 {
-    const int dbg = debug_ablate();
     const size_t lds = (size_t)4 * ListCfg<EPL, ROWN, R, l2_nrec(R, EPL)>::BYTES;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&l2_topk_kernel<KSTEPS, R, EPL, ROWN>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     dim3 grid(gx, S), block(256);
     hipLaunchKernelGGL((l2_topk_kernel<KSTEPS, R, EPL, ROWN>), grid, block, lds, st, Xpk, Ypk, tiles_per_split, tile_off,
-                       lkeep, cand_idx, cand_key, cand_tau, dbg);
+                       lkeep, cand_idx, cand_key, cand_tau, 0);
     return hipGetLastError();
 }
 

@@ -10,7 +10,7 @@
 // certificate implies and only collects what lies below it), then through the f16x3 / fp32 filter.  On 1M x 1M x 50 the
 // bound costs 3 % more staged scores and 0.7 % of the rows.  KS = 1 .. 4: every g <= 125.
 //
-// What a tile costs was measured on the l2q kernel at KS = 2 (tools/r3_coarse_ab.sh, 1M x 1M): the bare MFMA loop
+// What a tile costs was measured on the l2q kernel at KS = 2 (profiles/r3_coarse_experiments.txt, 1M x 1M): the bare MFMA loop
 // 62 ms = the matrix pipe's rate, + 24 ms of filter instructions (14 per 8 MFMAs, bunched behind the chains they read),
 // + 12-15 ms for the tile refills (fenced into the last chain of a tile), + 32 ms of hits -- nothing overlapped.  Hence:
 //   * the filter of a pair of row-blocks is 10 instructions (2 x (3 v_min3 + v_min + v_cmp)): no NaN canonicalisation --
@@ -33,9 +33,7 @@
 
 #include <hip/hip_fp16.h>
 
-#ifndef NABO_L2C_INLINE_DRAIN
-#define NABO_DRAIN_CALL 1
-#endif
+#define NABO_DRAIN_CALL 1             // topk_lists.h: this file drains its lists through a real call
 #include "knn_common.h"
 #include "launch.h"
 #include "topk_lists.h"
@@ -44,16 +42,6 @@ namespace nabo {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-#ifdef NABO_L2C_BUILTIN
-constexpr bool L2C_BUILTIN = true;
-#else
-constexpr bool L2C_BUILTIN = false;
-#endif
-#ifdef NABO_L2C_ABL
-constexpr bool L2C_ABLATED = true;
-#else
-constexpr bool L2C_ABLATED = false;
-#endif
 // Three geometries (claunch_one), by the list length a pass wants:
 //   A  one wave per SIMD: 4 waves x 128 rows, lists of <= 32 kept entries (33-entry rows), 64 staging records;
 //   B  TWO waves per SIMD: 4 waves x 96 rows per workgroup, TWO workgroups per CU (round 3: one of 8 waves), lists of <= 23
@@ -63,10 +51,7 @@ constexpr bool L2C_ABLATED = false;
 //      (BASELINE configs[4]: k = 50), which the fp32-MFMA kernel served before.
 constexpr int L2C_NREC = 64;        // staging records (8 scores each) per wave, geometry A
 constexpr int L2C_ROW = 33;         // list entries per row (odd), geometry A
-#ifndef NABO_L2C_NREC_B
-#define NABO_L2C_NREC_B 32
-#endif
-constexpr int L2C_NREC_B = NABO_L2C_NREC_B;
+constexpr int L2C_NREC_B = 32;
 constexpr int L2C_ROW_B = 23;
 constexpr int L2C_ROW_C = 65;
 
@@ -286,7 +271,7 @@ __device__ __forceinline__ void cstage2(const cacc &acc, const cmins &m, int p, 
 // 2: 256 registers, a ring of two).  Geometry B is WAVES = 4, WPS = 2: TWO 384-row workgroups per CU -- the same occupancy
 // as one 768-row workgroup of eight waves, at half the granularity: 100k target rows are 261 workgroups on 512 slots (every
 // CU busy, each wave alone on its SIMD) instead of 131 on 256 (half the chip idle), and the last round of a long query is cut finer.
-template <int KS, int EPL, int ROWN, int NBv, int NRECv, int WAVES, int WPS, bool PCS = false>
+template <int KS, int EPL, int ROWN, int NBv, int NRECv, int WAVES, int WPS>
 __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigned char *__restrict__ Xpk,
                                                           const unsigned char *__restrict__ Ypk,
                                                           int tiles_per_split, int64_t tile_off, int lkeep,
@@ -294,26 +279,13 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                                                           float *__restrict__ cand_key,
                                                           float *__restrict__ cand_tau, int64_t pad_tile, int dbg_arg,
                                                           int64_t rows_valid, const float *__restrict__ tau_init,
-                                                          int tau_stride, int64_t tau_row0,
-                                                          const int4 *__restrict__ pieces, int piece_S)
+                                                          int tau_stride, int64_t tau_row0)
 {
-    // PIECES (host side removed: see git history): with fewer column-workgroups than the chip has slots a launch of (columns x splits)
-    // workgroups either leaves slots empty or spills a few workgroups into a second round that costs as much as the first.
-    // Instead the linear space (column, reference tile) is cut into ~`slots` equal chunks, a chunk that crosses a column
-    // boundary into two pieces, and the launch is ONE WORKGROUP PER PIECE = (column, list slot of the column, first tile, end
-    // tile), longest first: the slots that finish a short piece pick up the next one.  Every piece has its own lists,
-    // thresholds and emitted list (row, slot) of piece_S.
-    // dbg: timing ablations of the experiment builds (knn_common.h: debug_ablate; the shipped library always passes 0).
-    // The four-step kernel on the 64-entry lists keeps it a RUN-TIME value in the product build too: with the ablation
-    // selects compiled in -- a few scalar instructions and never-taken branches per tile, same loads, same waits, same
-    // MFMA statements -- that one instantiation runs 16 % faster than with them folded away (cosine 1M x 1M, d = 100,
-    // k = 50, same box: 308 against 365 ms; no such effect, or 1-4 % the other way, in the other instantiations:
-    // profiles/r3_coarse_experiments.txt item 13).  Not understood; measured.
-#ifdef NABO_EXPERIMENTS
-    constexpr bool DBG_RT = true;
-#else
+    // dbg: the run-time switch of timing ablations that are gone; every launch passes 0.  The four-step kernel on the
+    // 64-entry lists keeps it a RUN-TIME value, never-taken selects and all: that one instantiation runs 16 % faster with
+    // them than with them folded away (cosine 1M x 1M, d = 100, k = 50, same box: 308 against 365 ms; no such effect, or
+    // 1-4 % the other way, in the others: profiles/r3_coarse_experiments.txt item 13).  Not understood; measured.
     constexpr bool DBG_RT = KS == 4 && EPL == 2;
-#endif
     const int dbg = DBG_RT ? dbg_arg : 0;
     constexpr int NB = NBv;                            // row-blocks of 16 targets per wave
     constexpr int NP = NB / 2;                         // pairs
@@ -325,14 +297,9 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
     const int lane = lane_id();
     const int lq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // (PCS: its own instantiation; one workgroup per piece, longest pieces first -- a loop over a chunk's pieces inside the
-    // kernel kept every kernel argument alive to the end and cost the 256-register geometry spills in its staging path)
-    int4 piece = make_int4((int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.y * tiles_per_split, ((int)blockIdx.y + 1) * tiles_per_split);
-    if (PCS) piece = pieces[blockIdx.x];
-    const int colx = PCS ? __builtin_amdgcn_readfirstlane(piece.x) : (int)blockIdx.x;
-    const int split = PCS ? __builtin_amdgcn_readfirstlane(piece.y) : (int)blockIdx.y;
-    const int S = PCS ? piece_S : (int)gridDim.y;
-    const int64_t ltile0 = ((int64_t)colx * WAVES + wave) * (NB / 2);        // in 32-row tiles
+    const int split = blockIdx.y;
+    const int S = gridDim.y;
+    const int64_t ltile0 = ((int64_t)(int)blockIdx.x * WAVES + wave) * (NB / 2);     // in 32-row tiles
     const int64_t ttile0 = tile_off + ltile0;
 
     f16x8 xb[NB][KS];
@@ -373,8 +340,8 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
         tauv[rb] = r < rows_valid ? ((tau_init && !(dbg & 1)) ? seed_of(r) : tau0) : -__builtin_inff();
     }
     uint32_t scnt = 0;
-    const int t_begin = PCS ? __builtin_amdgcn_readfirstlane(piece.z) : split * tiles_per_split;
-    const int t_end = PCS ? __builtin_amdgcn_readfirstlane(piece.w) : t_begin + tiles_per_split;
+    const int t_begin = split * tiles_per_split;
+    const int t_end = t_begin + tiles_per_split;
     lists_init<C>(wl, lkeep, tau0, (uint32_t)t_begin * 32u);
     {
         const int64_t nv = rows_valid - row0;            // valid rows of this wave
@@ -401,7 +368,7 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
     // past the split's last tile: an all-padding tile (+inf norms, nothing passes) -- the loop runs in fours (twos)
     auto tile_ptr = [&](int ts) {
         const int64_t tc = ts < t_end ? (int64_t)ts : pad_tile;
-        // dbg & 2 / dbg & 4 (timing experiments, garbage results): the stream wraps inside a window of 128 tiles / of 2
+        // (dbg & 2 / dbg & 4, never set: the stream wrapped inside a window of 128 tiles / of 2 -- kept for DBG_RT's sake)
         return Ypk + ((dbg & 2) ? (int64_t)(t_begin + ((ts - t_begin) & 127)) : (dbg & 4) ? (int64_t)(t_begin + ((ts - t_begin) & 1)) : tc) * TB;
     };
     auto tile_load = [&](f16x8(&a)[2][KS], int ts) {
@@ -436,10 +403,6 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
 #pragma unroll
             for (int h = 0; h < 2; ++h) accO[p].v[r][h] = f32x4{__builtin_inff(), __builtin_inff(), __builtin_inff(), __builtin_inff()};
 
-#ifdef NABO_L2C_ABL
-    float abl_run = 1e30f;
-    int abl_cnt = 0;
-#endif
     // chains of tile t into `cur` (set `a`; set `an` receives tile t + 3), filter of tile t - 1 (`old`) beside them
     auto tile_step = [&](const f16x8(&a)[2][KS], f16x8(&an)[2][KS], cacc(&cur)[NP], const cacc(&old)[NP], int t) {
         tile_load(an, t + RING - 1);
@@ -447,26 +410,11 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
         uint64_t hit[NP];
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-#if defined(NABO_L2C_ABL) && NABO_L2C_ABL == 1          // timing ablations (tools/ab): no filter at all
-            asm volatile("" ::"v"(old[p].v[0][0]), "v"(old[p].v[0][1]), "v"(old[p].v[1][0]), "v"(old[p].v[1][1]));
-            hit[p] = 0;
-#elif defined(NABO_L2C_ABL) && NABO_L2C_ABL == 2        // the minimum trees, no compare
-            mm[p] = cmin8x2(old[p]);
-            abl_run = fminf(abl_run, fminf(mm[p].m0, mm[p].m1));
-            hit[p] = 0;
-#elif defined(NABO_L2C_ABL) && NABO_L2C_ABL == 3        // trees + compares, verdicts folded into a register, no branch
-            mm[p] = cmin8x2(old[p]);
-            abl_cnt += ((mm[p].m0 < tauv[2 * p]) | (mm[p].m1 < tauv[2 * p + 1])) ? 1 : 0;
-            hit[p] = 0;
-#else
-            if constexpr ((KS == 2 || KS == 4) && !L2C_BUILTIN) {
+            if constexpr (KS == 2 || KS == 4) {
                 cpair<KS, (WPS == 1)>(a, xb[2 * p], xb[2 * p + 1], cur[p], old[p], tauv[2 * p], tauv[2 * p + 1], mm[p], hit[p]);
-            } else {                                    // hipcc's own schedule of builtin MFMAs (other shapes; A/B runs)
+            } else {                                    // hipcc's own schedule of builtin MFMAs (the other shapes)
                 mm[p] = cmin8x2(old[p]);
                 hit[p] = __builtin_amdgcn_ballot_w64((mm[p].m0 < tauv[2 * p]) | (mm[p].m1 < tauv[2 * p + 1]));
-            }
-#endif
-            if constexpr ((KS != 2 && KS != 4) || L2C_BUILTIN || L2C_ABLATED) {
                 cur[p] = cchain<KS>(a, xb[2 * p], xb[2 * p + 1]);
                 // one MFMA, then at most two of the filter's instructions (what fits beside a 16-cycle MFMA)
                 L2C_SG(2) L2C_SG(2) L2C_SG(1) L2C_SG(1) L2C_SG(1) L2C_SG(1) L2C_SG(1) L2C_SG(1)
@@ -483,12 +431,7 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
             bool drained = false;
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
-                if (hit[p] != 0) {
-                    NABO_PROF_T0();
-                    cstage2<C, NB, NREC>(old[p], mm[p], p, jb, wl, scnt, lkeep, tauv, drained);
-                    NABO_PROF_ADD(wl, 0, 1);
-                    NABO_PROF_ADD(wl, 1, NABO_PROF_DT() >> 4);
-                }
+                if (hit[p] != 0) cstage2<C, NB, NREC>(old[p], mm[p], p, jb, wl, scnt, lkeep, tauv, drained);
             }
             if (drained) {
 #pragma unroll
@@ -500,9 +443,8 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
     // Every load of the preamble lands HERE (s_waitcnt vmcnt(0), once per wave).  hipcc's scheduler is free to reorder the
     // preamble's tile loads, and its wait-count pass merges the preamble's pending loads with the loop's at the loop
     // header: with the first tile's loads issued last, the FIRST step of every round waited for all but the newest tile
-    // (vmcnt(8) where 24 loads may be in flight) -- a ring of four that emptied once per round.  Seen in the product build of
-    // every ring-of-four geometry, not in the experiment builds (whose extra branches happened to keep the order):
-    // cosine 1M x 1M, d = 100, k = 50: kernel 425 -> 318 ms.
+    // (vmcnt(8) where 24 loads may be in flight) -- a ring of four that emptied once per round.  Seen in every
+    // ring-of-four geometry: cosine 1M x 1M, d = 100, k = 50: kernel 425 -> 318 ms.
     __builtin_amdgcn_s_waitcnt(0x0F70);
     int t = t_begin;
     if (RING == 4) {
@@ -518,9 +460,6 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
             tile_step(a1, a0, accO, accE, t + 1);
         }
     }
-#ifdef NABO_L2C_ABL
-    if (abl_run + (float)abl_cnt == 12345.0f) cand_tau[0] = abl_run;
-#endif
     // the last step's scores (a padding step when the split's length is no multiple of four: all +inf); its MFMAs are
     // inline assembly, so the wait states between them and the first reader are ours to insert (12 for this shape)
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
@@ -583,9 +522,9 @@ __global__ __launch_bounds__(256) void l2c_pre_kernel(const unsigned char *__res
         for (int j = 0; j < QM; ++j) srt[rb][j] = __builtin_inff();
     int t_begin = split * tiles_per_split, t_end = t_begin + tiles_per_split;
     if (ranges) {
-        // a launch cut into pieces: the tournament of (column, slot) looks at the first tiles of THAT piece (a wave's rows lie
-        // in one column: the columns are whole multiples of a wave's rows); no tournament for a short or unused piece --
-        // its seeds stay +inf (the caller's fill)
+        // ranges [columns x S] int4 (first tile, end tile, tournament tiles, tiles per tournament group): every (column of
+        // rows_per_col rows, split) brings its own stream and tournament length (a wave's rows lie in one column: the
+        // columns are whole multiples of a wave's rows); (0, 0, 0, 0) = no tournament, its seeds stay +inf (the caller's fill)
         const int4 r = ranges[(ltile0 * 32 / rows_per_col) * S + split];
         t_begin = __builtin_amdgcn_readfirstlane(r.x);
         t_end = __builtin_amdgcn_readfirstlane(r.y);
@@ -705,42 +644,17 @@ template <int KS, int EPL, int ROWN, int NBv, int NRECv, int WAVES, int WPS>
 static hipError_t claunch_geo(const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S, int gx,
                               int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
                               int64_t pad_tile, hipStream_t st, int64_t rows_valid, const float *tau_init, int tau_stride,
-                              int64_t tau_row0, const L2cPieces &pcs)
+                              int64_t tau_row0)
 {
-    const int dbg = debug_ablate();
     constexpr size_t lds = (size_t)WAVES * ListCfg<EPL, ROWN, NBv, NRECv, 16, (ROWN >= 64)>::BYTES;
     static_assert(lds <= 163840, "LDS budget");
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&l2c_topk_kernel<KS, EPL, ROWN, NBv, NRECv, WAVES, WPS, false>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&l2c_topk_kernel<KS, EPL, ROWN, NBv, NRECv, WAVES, WPS>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     dim3 block(64 * WAVES);
-#ifndef NABO_EXPERIMENTS
-    if (pcs.pieces) return hipErrorInvalidValue;        // (the launch cut into pieces lost to uniform splits: experiments build only)
-#else
-    if (pcs.pieces) {
-        // pieces: one workgroup per chunk of the (column, tile) space; gx / S then only describe the emitted lists
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&l2c_topk_kernel<KS, EPL, ROWN, NBv, NRECv, WAVES, WPS, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((l2c_topk_kernel<KS, EPL, ROWN, NBv, NRECv, WAVES, WPS, true>), dim3(pcs.n_pieces, 1), block, lds, st, Xpk, Ypk,
-                           tiles_per_split, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, dbg, rows_valid, tau_init, tau_stride,
-                           tau_row0, reinterpret_cast<const int4 *>(pcs.pieces), S);
-    } else
-#endif
-    {
-        hipLaunchKernelGGL((l2c_topk_kernel<KS, EPL, ROWN, NBv, NRECv, WAVES, WPS, false>), dim3(gx, S), block, lds, st, Xpk, Ypk,
-                           tiles_per_split, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, dbg, rows_valid, tau_init, tau_stride,
-                           tau_row0, nullptr, S);
-    }
-#ifdef NABO_LISTS_PROF
-    {
-        unsigned long long h[8];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(nabo_lists_prof), sizeof(h));
-        fprintf(stderr, "[lists prof, cumulative] episodes %llu (x16 cyc %llu) drains %llu (x16 cyc %llu) rounds %llu (%llu) "
-                        "records %llu appended %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
-    }
-#endif
+    hipLaunchKernelGGL((l2c_topk_kernel<KS, EPL, ROWN, NBv, NRECv, WAVES, WPS>), dim3(gx, S), block, lds, st, Xpk, Ypk,
+                       tiles_per_split, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, 0, rows_valid, tau_init, tau_stride,
+                       tau_row0);
     return hipGetLastError();
 }
 
@@ -748,18 +662,18 @@ template <int KS>
 static hipError_t claunch_one(int geo, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S, int gx,
                               int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
                               int64_t pad_tile, hipStream_t st, int64_t rows_valid, const float *tau_init, int tau_stride,
-                              int64_t tau_row0, const L2cPieces &pcs)
+                              int64_t tau_row0)
 {
     if constexpr (KS <= 2) {
         if (geo == 1)
             return claunch_geo<KS, 1, L2C_ROW_B, 6, L2C_NREC_B, 4, 2>(Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx,
-                                                                  cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, pcs);
+                                                                  cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
     }
     if (geo == 2)
         return claunch_geo<KS, 2, L2C_ROW_C, 4, L2C_NREC, 4, 1>(Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key,
-                                                            cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, pcs);
+                                                            cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
     return claunch_geo<KS, 1, L2C_ROW, 8, L2C_NREC, 4, 1>(Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau,
-                                                      pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, pcs);
+                                                      pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
 }
 
 // Which geometry serves lists of `lkeep_want` kept entries: 1 = B (two waves per SIMD) up to 23 entries and KS <= 2 (its
@@ -796,18 +710,16 @@ int l2c_pick_kc(int g)
 hipError_t l2c_topk_launch(int kc, int geo, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
                            int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
                            int64_t pad_tile, hipStream_t st, int64_t rows_valid, const float *tau_init, int tau_stride,
-                           int64_t tau_row0, const L2cPieces *pieces)
+                           int64_t tau_row0)
 {
-    const L2cPieces pcs = pieces ? *pieces : L2cPieces{nullptr, 0, nullptr, 0};
-    if (pcs.pieces && pcs.n_pieces < 1) return hipErrorInvalidValue;
     if ((int64_t)tiles_per_split * 32 >= NABO_LIST_SPLIT_REFS) return hipErrorInvalidValue;   // topk_lists.h: 25 bits of offset per entry
     if (geo < 0 || geo > 2 || (geo == 1 && (kc > 4 || lkeep > L2C_ROW_B)) || (geo == 0 && lkeep > 32) || lkeep > 64)
         return hipErrorInvalidValue;
     switch (kc) {
-    case 2: return claunch_one<1>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, pcs);
-    case 4: return claunch_one<2>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, pcs);
-    case 6: return claunch_one<3>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, pcs);
-    case 8: return claunch_one<4>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, pcs);
+    case 2: return claunch_one<1>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
+    case 4: return claunch_one<2>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
+    case 6: return claunch_one<3>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
+    case 8: return claunch_one<4>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
     default: return hipErrorInvalidValue;
     }
 }

@@ -37,9 +37,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int L2Q_NREC = 64;        // staging records (8 scores each) per wave
 constexpr int L2Q_ROW = 33;         // list entries per row (odd)
-#ifndef L2Q_HOME
-#define L2Q_HOME 8                   // tiles of the home pre-pass (locality order)
-#endif
 
 struct qacc { f32x4 v[2][2]; };     // [row-block of the pair][reference half]
 
@@ -63,14 +60,12 @@ __device__ __forceinline__ qacc qchain(f16x8 (&a)[2][KS], const f16x8 (&b0)[KS],
         for (int s = 0; s < KS + ((RELOAD && c == 3) ? 1 : 0); ++s) {
             if (s < KS)
                 acc.v[c >> 1][c & 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[c & 1][s], (c >> 1) ? b1[s] : b0[s], acc.v[c >> 1][c & 1], 0, 0, 0);
-#ifndef NABO_L2H_NORELOAD
             if (RELOAD && c == 3) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (s < KS) a[0][s] = reinterpret_cast<const f16x8 *>(next)[s * 64 + lane];
                 if (s >= 1) a[1][s - 1] = reinterpret_cast<const f16x8 *>(next)[(KS + s - 1) * 64 + lane];
                 __builtin_amdgcn_sched_barrier(0);
             }
-#endif
         }
     }
     return acc;
@@ -101,7 +96,6 @@ __device__ __forceinline__ void qfilter_stage(const qacc &acc, const qverdict &v
                                               uint32_t &scnt, int lkeep, float (&tauv)[NB])
 {
     if (__builtin_expect(v.any != 0, 0)) {          // (unlikely: the staging code goes out of line, the common path falls through)
-        NABO_PROF_T0();
         float s0[8], s1[8];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -109,8 +103,6 @@ __device__ __forceinline__ void qfilter_stage(const qacc &acc, const qverdict &v
             s1[i] = acc.v[1][0][i]; s1[4 + i] = acc.v[1][1][i];
         }
         stage_hits2<C, EPL, NB, NREC>(s0, v.m0, s1, v.m1, rb0, jb, w, scnt, lkeep, tauv);
-        NABO_PROF_ADD(w, 0, 1);
-        NABO_PROF_ADD(w, 1, NABO_PROF_DT() >> 4);
     }
 }
 
@@ -123,16 +115,13 @@ __device__ __forceinline__ void qfilter(const qacc &acc, int rb0, uint32_t jb, u
 }
 
 // Grid: x = target super-blocks (4 waves x 128 rows), y = reference splits.
-// HOMEP: the locality-ordered form (its host side, order.hip, was removed: see git history) -- compiled separately so that the default kernel carries
-// none of its per-tile index arithmetic.
-template <int KC, int EPL, int ROWN, bool HOMEP = false>
+template <int KC, int EPL, int ROWN>
 __global__ __launch_bounds__(256, 1) void l2q_topk_kernel(const unsigned char *__restrict__ Xpk,
                                                           const unsigned char *__restrict__ Ypk,
                                                           int tiles_per_split, int64_t tile_off, int lkeep,
                                                           uint32_t *__restrict__ cand_idx,
                                                           float *__restrict__ cand_key,
-                                                          float *__restrict__ cand_tau, int64_t pad_tile, int dbg,
-                                                          const int32_t *__restrict__ wave_start)
+                                                          float *__restrict__ cand_tau, int64_t pad_tile)
 {
     constexpr int KS = KC / 2;                         // steps of 32 slots
     constexpr int NB = 8;                              // row-blocks of 16 targets per wave
@@ -162,7 +151,7 @@ __global__ __launch_bounds__(256, 1) void l2q_topk_kernel(const unsigned char *_
     }
     unsigned char *wl = smem_raw + (size_t)wave * C::BYTES;          // this wave's lists (topk_lists.h)
     float tauv[NB];
-    const float tau0 = (dbg & 1) ? -__builtin_inff() : __builtin_inff();
+    const float tau0 = __builtin_inff();
 #pragma unroll
     for (int rb = 0; rb < NB; ++rb) tauv[rb] = tau0;
     uint32_t scnt = 0;
@@ -170,31 +159,9 @@ __global__ __launch_bounds__(256, 1) void l2q_topk_kernel(const unsigned char *_
 
     const int t_begin = split * tiles_per_split;
     const int t_end = t_begin + tiles_per_split;
-    // Locality order (host side removed, see HOMEP): before the common stream a wave visits L2Q_HOME tiles around the tile that holds its
-    // rows' neighbourhood (wave_start, per 128 target rows): its thresholds are near their final values when the stream
-    // proper begins, and that stream still runs from the split's first tile in step with every other wave of the XCD
-    // (one copy of the stream in L2 -- a cyclic start per wave gave 4x fewer episodes and a 14 % SLOWER kernel: every wave
-    // then streams its own window).  Step ts of the loops below is tile tmap(ts): the home tiles, then the split's tiles
-    // in order without them.
-    int h0 = t_begin, H = 0;
-    if (HOMEP && wave_start && tiles_per_split >= 4 * L2Q_HOME) {
-        H = L2Q_HOME;
-        h0 = __builtin_amdgcn_readfirstlane(wave_start[ttile0 / (NB / 2)]) - L2Q_HOME / 2;
-        h0 = h0 < t_begin ? t_begin : (h0 > t_end - L2Q_HOME ? t_end - L2Q_HOME : h0);
-    }
-    auto tmap = [&](int ts) {
-        if (!HOMEP) return ts;
-        if (ts - t_begin < H) return h0 + (ts - t_begin);
-        const int j = ts - H;
-        return j < h0 ? j : j + H;
-    };
     // past the split's last tile: an all-padding tile (+inf norms, nothing passes) -- the loop always runs two steps
     auto tile_ptr = [&](int ts) {
-        const int t = tmap(ts);
-        const int64_t tc = ts < t_end ? (int64_t)t : pad_tile;
-        // dbg & 2 / dbg & 4 (timing experiments, garbage results): the stream wraps inside a window of 128 tiles (stays in
-        // the XCD's L2) / of 2 tiles (stays in the CU's vector L1)
-        return Ypk + ((dbg & 2) ? (int64_t)(t_begin + ((t - t_begin) & 127)) : (dbg & 4) ? (int64_t)(t_begin + ((t - t_begin) & 1)) : tc) * TB;
+        return Ypk + (ts < t_end ? (int64_t)ts : pad_tile) * TB;
     };
 
     f16x8 a0[2][KS], a1[2][KS];
@@ -220,29 +187,17 @@ __global__ __launch_bounds__(256, 1) void l2q_topk_kernel(const unsigned char *_
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             const int prev = (p + NP - 1) % NP;
-            const uint32_t jbp = (uint32_t)(tmap(p == 0 ? t - 1 : t) * 32 + 4 * lq);     // (a padding step stages nothing)
+            const uint32_t jbp = (uint32_t)((p == 0 ? t - 1 : t) * 32 + 4 * lq);     // (a padding step stages nothing)
             if (p & 1) {
-#ifndef NABO_L2H_NOFILTER
                 const qverdict v = qfilter_eval<NB>(accA, 2 * prev, tauv);
-#endif
                 if (p == NP - 1) accP = qchain<KS, true>(a, xb[2 * p], xb[2 * p + 1], next2, lane);
                 else accP = qchain<KS, false>(a, xb[2 * p], xb[2 * p + 1], next2, lane);
-#ifndef NABO_L2H_NOFILTER
                 qfilter_stage<C, EPL, NB, NREC>(accA, v, 2 * prev, jbp, wl, scnt, lkeep, tauv);
-#else
-                asm volatile("" ::"v"(accA.v[0][0]), "v"(accA.v[0][1]), "v"(accA.v[1][0]), "v"(accA.v[1][1]));
-#endif
             } else {
-#ifndef NABO_L2H_NOFILTER
                 const qverdict v = qfilter_eval<NB>(accP, 2 * prev, tauv);
-#endif
                 if (p == NP - 1) accA = qchain<KS, true>(a, xb[2 * p], xb[2 * p + 1], next2, lane);
                 else accA = qchain<KS, false>(a, xb[2 * p], xb[2 * p + 1], next2, lane);
-#ifndef NABO_L2H_NOFILTER
                 qfilter_stage<C, EPL, NB, NREC>(accP, v, 2 * prev, jbp, wl, scnt, lkeep, tauv);
-#else
-                asm volatile("" ::"v"(accP.v[0][0]), "v"(accP.v[0][1]), "v"(accP.v[1][0]), "v"(accP.v[1][1]));
-#endif
             }
         }
     };
@@ -256,47 +211,26 @@ __global__ __launch_bounds__(256, 1) void l2q_topk_kernel(const unsigned char *_
     }
     {
         const int tl = t_begin + ((tiles_per_split + 1) & ~1) - 1;          // the last step run (t_end - 1 or the padding step)
-        qfilter<C, EPL, NB, NREC>(accP, NB - 2, (uint32_t)(tmap(tl) * 32 + 4 * lq), wl, scnt, lkeep, tauv);
+        qfilter<C, EPL, NB, NREC>(accP, NB - 2, (uint32_t)(tl * 32 + 4 * lq), wl, scnt, lkeep, tauv);
     }
 
     lists_flush<C, EPL, NB>(wl, scnt, ltile0 * 32, split, S, lkeep, tauv, cand_idx, cand_key, cand_tau);
 }
 
-template <int KC, int EPL, int ROWN, bool HOMEP>
-static hipError_t qlaunch_k(const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S, int gx,
-                            int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
-                            int64_t pad_tile, hipStream_t st, const int32_t *wave_start)
-{
-    const int dbg = debug_ablate();
-    constexpr size_t lds = (size_t)4 * ListCfg<EPL, ROWN, 8, L2Q_NREC, 16>::BYTES;
-    static_assert(lds <= 163840, "LDS budget");
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&l2q_topk_kernel<KC, EPL, ROWN, HOMEP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    dim3 grid(gx, S), block(256);
-    hipLaunchKernelGGL((l2q_topk_kernel<KC, EPL, ROWN, HOMEP>), grid, block, lds, st, Xpk, Ypk, tiles_per_split, tile_off,
-                       lkeep, cand_idx, cand_key, cand_tau, pad_tile, dbg, wave_start);
-#ifdef NABO_LISTS_PROF
-    {
-        unsigned long long h[8];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(nabo_lists_prof), sizeof(h));
-        fprintf(stderr, "[lists prof, cumulative] episodes %llu (x16 cyc %llu) drains %llu (x16 cyc %llu) rounds %llu (%llu) "
-                        "records %llu appended %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
-    }
-#endif
-    return hipGetLastError();
-}
-
 template <int KC, int EPL, int ROWN>
 static hipError_t qlaunch_one(const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S, int gx,
                               int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
-                              int64_t pad_tile, hipStream_t st, const int32_t *wave_start)
+                              int64_t pad_tile, hipStream_t st)
 {
-    return wave_start ? qlaunch_k<KC, EPL, ROWN, true>(Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key,
-                                                       cand_tau, pad_tile, st, wave_start)
-                      : qlaunch_k<KC, EPL, ROWN, false>(Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key,
-                                                        cand_tau, pad_tile, st, nullptr);
+    constexpr size_t lds = (size_t)4 * ListCfg<EPL, ROWN, 8, L2Q_NREC, 16>::BYTES;
+    static_assert(lds <= 163840, "LDS budget");
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&l2q_topk_kernel<KC, EPL, ROWN>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    dim3 grid(gx, S), block(256);
+    hipLaunchKernelGGL((l2q_topk_kernel<KC, EPL, ROWN>), grid, block, lds, st, Xpk, Ypk, tiles_per_split, tile_off,
+                       lkeep, cand_idx, cand_key, cand_tau, pad_tile);
+    return hipGetLastError();
 }
 
 // 512 rows per workgroup, one workgroup per CU (one wave per SIMD with the whole register file), lists of <= 32 kept
@@ -331,10 +265,10 @@ int l2q_pick_kc1(int g)
 
 hipError_t l2q_topk_launch(int kc, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
                            int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
-                           int64_t pad_tile, hipStream_t st, const int32_t *wave_start)
+                           int64_t pad_tile, hipStream_t st)
 {
     if ((int64_t)tiles_per_split * 32 >= NABO_LIST_SPLIT_REFS) return hipErrorInvalidValue;   // topk_lists.h: 25 bits of offset per entry
-#define NABO_Q(KCV) case KCV: return qlaunch_one<KCV, 1, L2Q_ROW>(Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, wave_start);
+#define NABO_Q(KCV) case KCV: return qlaunch_one<KCV, 1, L2Q_ROW>(Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st);
     switch (kc) {
         NABO_Q(2) NABO_Q(4) NABO_Q(6) NABO_Q(8) NABO_Q(10) NABO_Q(12)
     default: return hipErrorInvalidValue;

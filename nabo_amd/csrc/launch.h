@@ -11,7 +11,6 @@
 #include <hip/hip_runtime.h>
 #endif
 
-struct L2cPieces;      // knn_common.h
 struct nabo_index;     // api.hip
 
 namespace nabo {
@@ -51,7 +50,7 @@ void l2_topk_geometry(int ksteps, int epl, int *rows_per_wg, int *wg_per_cu, int
 int l2q_pick_kc(int g);
 hipError_t l2q_topk_launch(int kc, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
                            int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
-                           int64_t pad_tile, hipStream_t st, const int32_t *wave_start = nullptr);
+                           int64_t pad_tile, hipStream_t st);
 void l2q_topk_geometry(int kc, int *rows_per_wg, int *wg_per_cu, int *lkeep_max);
 // the one-product first pass (l2c_topk.hip; operands packed with layout16, nseg = 1)
 int l2c_pick_kc(int g);
@@ -60,7 +59,7 @@ void l2c_topk_geometry(int kc, int lkeep_want, int pin, int *rows_per_wg, int *w
 hipError_t l2c_topk_launch(int kc, int geo, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
                            int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
                            int64_t pad_tile, hipStream_t st, int64_t rows_valid, const float *tau_init, int tau_stride = 0,
-                           int64_t tau_row0 = 0, const L2cPieces *pieces = nullptr);
+                           int64_t tau_row0 = 0);
 // tournament seeds for the one-product pass (l2c_topk.hip: l2c_pre_kernel)
 void l2c_pre_plan(int kc, int lkeep, int tiles_per_split, int scale_pct, int *pre_tiles, int *gt);
 hipError_t l2c_pre_launch(int kc, int lkeep, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,

@@ -70,13 +70,7 @@ struct ListCfg {
     static constexpr int OFF_GMAX = OFF_BASE + 16;           // gmax [NROWS][NGRP] doubles (GRP only)
     static constexpr int GMAX_BYTES = GRPv ? NROWS * NGRP * 8 : 0;
     __device__ static double *gmax(unsigned char *w) { return reinterpret_cast<double *>(w + OFF_GMAX); }
-#ifdef NABO_LISTS_PROF
-    static constexpr int OFF_PROF = OFF_BASE + 16 + GMAX_BYTES;   // 16 u32 event counters / cycle sums (profiling builds only)
-    static constexpr int BYTES = OFF_PROF + 64;
-    __device__ static uint32_t *prof(unsigned char *w) { return reinterpret_cast<uint32_t *>(w + OFF_PROF); }
-#else
     static constexpr int BYTES = OFF_BASE + 16 + GMAX_BYTES;
-#endif
     static constexpr int IDX_BITS = 25;                      // entry low word: (slot << IDX_BITS) | offset of the reference
     static constexpr uint32_t IDX_MASK = (1u << IDX_BITS) - 1u;   // (all ones: no reference -- a sentinel entry)
     static_assert(ROWN <= 128, "seven bits of slot");
@@ -90,24 +84,7 @@ struct ListCfg {
     __device__ static uint32_t *owner(unsigned char *w) { return reinterpret_cast<uint32_t *>(w + OFF_OWNER); }
 };
 
-// Profiling builds (-DNABO_LISTS_PROF, tools only): per-wave event counts and shader-clock sums in LDS, added to a
-// global array by lists_flush and printed by the launch wrapper: [0] episodes [1] cycles staging (drains inside an
-// episode included) [2] drains [3] cycles draining [4] drain rounds [5] - [6] records [7] entries written to a list.
-#ifdef NABO_LISTS_PROF
-static __device__ unsigned long long nabo_lists_prof[8];
-#define NABO_PROF_ADD(w, i, v)                                                    \
-    do {                                                                          \
-        if (lane_id() == 0) atomicAdd(&C::prof(w)[i], (uint32_t)(v));            \
-    } while (0)
-#define NABO_PROF_T0() const uint64_t prof_t0 = __builtin_readcyclecounter()
-#define NABO_PROF_DT() (uint32_t)(__builtin_readcyclecounter() - prof_t0)
-#else
-#define NABO_PROF_ADD(w, i, v) do { } while (0)
-#define NABO_PROF_T0() do { } while (0)
-#define NABO_PROF_DT() 0u
-#endif
-
-// Sentinel kept lists, thresholds +inf (tau0 = -inf: "no hits" timing experiments).
+// Sentinel kept lists, thresholds tau0 = +inf (-inf: a row that collects nothing).
 template <typename C>
 __device__ __forceinline__ void lists_init(unsigned char *w, int lkeep, float tau0, uint32_t idx_base)
 {
@@ -135,16 +112,11 @@ __device__ __forceinline__ void lists_init(unsigned char *w, int lkeep, float ta
         C::tauL(w)[r] = tau0;
         C::pmax(w)[r] = 0u;
     }
-#ifdef NABO_LISTS_PROF
-    if (lane < 16) C::prof(w)[lane] = 0u;
-#endif
 }
 
 // Batched list updates: one lane per staged record (see the header comment).
-#ifndef NABO_RESCAN
-#define NABO_RESCAN 12
-#endif
-// Largest entry of a row (as a double: the header comment) from slot I0 on, NABO_RESCAN entries per LDS round trip (a
+constexpr int LISTS_RESCAN = 12;
+// Largest entry of a row (as a double: the header comment) from slot I0 on, LISTS_RESCAN entries per LDS round trip (a
 // one-at-a-time scan is a chain of lkeep dependent LDS latencies).  Batches are compile-time pieces of the row's ROW
 // slots -- the last one ends with the row -- and run while they begin below lkeep (wave-uniform): what a batch reads
 // past lkeep has a -inf key (lists_init), so nothing needs a bounds test.
@@ -153,7 +125,7 @@ __device__ __forceinline__ void lists_rescan(const uint2 *kept, int lkeep, doubl
 {
     if constexpr (I0 < C::ROW) {
         if (I0 < lkeep) {
-            constexpr int LEN = C::ROW - I0 < NABO_RESCAN ? C::ROW - I0 : NABO_RESCAN;
+            constexpr int LEN = C::ROW - I0 < LISTS_RESCAN ? C::ROW - I0 : LISTS_RESCAN;
             double e[LEN];
 #pragma unroll
             for (int j = 0; j < LEN; ++j) e[j] = reinterpret_cast<const double *>(kept)[I0 + j];
@@ -202,7 +174,6 @@ __device__ __forceinline__ void lists_drain_body(unsigned char *w, uint32_t scnt
     }
     uint2 *kept = C::rows(w) + row * C::ROW;
     while (__builtin_amdgcn_ballot_w64(q != 0) != 0) {
-        NABO_PROF_ADD(w, 4, 1);
         // one contender per row goes now, the others in a later round
         if (q != 0) owner[row] = (uint32_t)lane;
         const bool go = q != 0 && owner[row] == (uint32_t)lane;
@@ -219,9 +190,6 @@ __device__ __forceinline__ void lists_drain_body(unsigned char *w, uint32_t scnt
                 if (repl) {
                     // evict the largest kept entry
                     kept[pm] = make_uint2((pm << C::IDX_BITS) | (jb + (uint32_t)((i & 3) + C::JSTRIDE * (i >> 2))), __float_as_uint(key));
-#ifdef NABO_LISTS_PROF
-                    atomicAdd(&C::prof(w)[7], 1u);
-#endif
                 }
             }
             if (__builtin_amdgcn_ballot_w64(repl) != 0) {       // new maximum of the rows that changed
@@ -273,30 +241,22 @@ __device__ __noinline__ void lists_drain_fn(uint32_t w_off, uint32_t scnt, int l
 template <typename C>
 __device__ __forceinline__ void lists_drain_only(unsigned char *w, uint32_t scnt, int lkeep)
 {
-    NABO_PROF_T0();
 #ifdef NABO_DRAIN_CALL
     lists_drain_fn<C>((uint32_t)(uintptr_t)w, scnt, lkeep);
 #else
     lists_drain_body<C>(w, scnt, lkeep);
 #endif
-    NABO_PROF_ADD(w, 2, 1);
-    NABO_PROF_ADD(w, 3, NABO_PROF_DT() >> 4);
-    NABO_PROF_ADD(w, 6, scnt);
 }
 
 // drain + refresh of the register copies of the thresholds (lane = row of its row-block)
 template <typename C, int NB>
 __device__ __forceinline__ void lists_drain(unsigned char *w, uint32_t scnt, int lkeep, float (&tauv)[NB])
 {
-    NABO_PROF_T0();
 #ifdef NABO_DRAIN_CALL
     lists_drain_fn<C>((uint32_t)(uintptr_t)w, scnt, lkeep);
 #else
     lists_drain_body<C>(w, scnt, lkeep);
 #endif
-    NABO_PROF_ADD(w, 2, 1);
-    NABO_PROF_ADD(w, 3, NABO_PROF_DT() >> 4);
-    NABO_PROF_ADD(w, 6, scnt);
 #pragma unroll
     for (int rb = 0; rb < NB; ++rb) tauv[rb] = C::tauL(w)[rb * C::RPB + (lane_id() & (C::RPB - 1))];
 }
@@ -379,13 +339,10 @@ __device__ __forceinline__ void filter_and_stage(const f32x16 &acc, int rb, uint
 #pragma unroll
     for (int r = 1; r < 16; ++r) m = fminf(m, acc[r]);
     if (__builtin_amdgcn_ballot_w64(m < tauv[rb]) != 0) {
-        NABO_PROF_T0();
         float a[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) a[r] = acc[r];
         stage_hits<C, EPL, NB, NREC>(a, m, rb, jb, w, scnt, lkeep, tauv);
-        NABO_PROF_ADD(w, 0, 1);
-        NABO_PROF_ADD(w, 1, NABO_PROF_DT() >> 4);           // (drains inside the episode are counted here too)
     }
 }
 
@@ -411,13 +368,10 @@ __device__ __forceinline__ void filter_stage(const f32x16 &acc, const FilterVerd
 {
     static_assert(C::RS == 16, "32x32 accumulator layout");
     if (v.any != 0) {
-        NABO_PROF_T0();
         float a[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) a[r] = acc[r];
         stage_hits<C, EPL, NB, NREC>(a, v.m, rb, jb, w, scnt, lkeep, tauv);
-        NABO_PROF_ADD(w, 0, 1);
-        NABO_PROF_ADD(w, 1, NABO_PROF_DT() >> 4);
     }
 }
 
@@ -432,9 +386,6 @@ __device__ __forceinline__ void lists_flush(unsigned char *w, uint32_t scnt, int
     constexpr int LMAX = C::LMAX;
     const int lane = lane_id();
     if (scnt > 0) lists_drain<C, NB>(w, scnt, lkeep, tauv);
-#ifdef NABO_LISTS_PROF
-    if (lane < 8) atomicAdd(&nabo_lists_prof[lane], (unsigned long long)C::prof(w)[lane]);
-#endif
     const uint2 *rows = C::rows(w);
     for (int row = 0; row < C::NROWS; ++row) {
         // kept entries in list order (unsorted: refine.hip orders candidates by their exact distances anyway)

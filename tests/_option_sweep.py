@@ -41,7 +41,7 @@ OPTION_VALUES = {
     "wide_retry": (0, 1),
     "refine_overlap": (0, 1),
     "prepass": (0, 50, 100, 400),
-    "pieces": (0, 1),                                  # experiments builds only: a no-op in the product library
+    "pieces": (0, 1),                                  # removed; accepted as a no-op
     "merge_lists": (0, 1),
     "one_round": (0, 1),
     "l2c_geo": (-1, 0, 1, 2),
@@ -49,7 +49,7 @@ OPTION_VALUES = {
     "split_refs_max": (0, "fit"),
     "cosine_centre": (0, 1),                           # takes effect at the next set_ref
     "coarse_kernel_q": (0, 1),
-    "order_flags": (0, 1),                             # experiments builds only: REFUSED in the product library
+    "order_flags": (0, 1),                             # removed; REFUSED by nabo_index_set_option
 }
 REFUSED_OPTIONS = ("order_flags",)                     # never drawn into a case; tests check the refusal itself
 

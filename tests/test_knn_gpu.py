@@ -462,7 +462,7 @@ def test_both_filter_kernels_give_the_same_bits(gpu_lib, m, n, g, k, drop):
     is instantiated: g <= 125 and k + drop + 4 <= 64; rows it cannot certify go on to the seeded pass and the filter behind
     it), the f16x3 split as the first pass (NABO_L2_MODE=f16x3: l2q_topk.hip, g < 64 and k' <= 28) -- or on the fp32 MFMA
     (everything else, or NABO_L2_MODE=f32): the float64 refine + certification make all of them return exactly what the
-    oracle does.  (The 32x32x16 kernels of rounds 1-2, l2h_topk.hip / l2s_topk.hip, live in the experiments build.)"""
+    oracle does.  (The 32x32x16 kernels of rounds 1-2, l2h_topk.hip / l2s_topk.hip, were removed.)"""
     Y = pca_like(n, g, seed=1000 + n + g)
     X = Y[:m].copy() if drop else pca_like(m, g, seed=2000 + m + g)
     oi, od = oracle.knn(X, Y, k, 0, drop_first=drop, nthreads=8)
@@ -1131,8 +1131,8 @@ def test_tournament_seeds_change_no_result(gpu_lib, m, n, g, k, drop, metric, sp
                                                  (45000, 9000, 20, 11, 0, 0), (101000, 40000, 50, 15, 0, 0),
                                                  (110000, 300000, 50, 15, 0, 0)])      # (a long stream: one split more + a tail launch)
 def test_cut_launches_and_merged_lists_change_no_result(gpu_lib, m, n, g, k, drop, metric):
-    """Fewer column-workgroups than slots.  (Experiments builds: the one-product launch cut into equal pieces of the (column,
-    reference tile) space -- api.hip: cut_pieces; option "pieces", a no-op in the product library.)  The several lists of a row are merged by their
+    """Fewer column-workgroups than slots.  (The one-product launch cut into equal pieces of the (column, reference tile)
+    space -- option "pieces" -- was removed; accepted as a no-op.)  The several lists of a row are merged by their
     filter keys before the float64 re-evaluation (refine.hip: merge_lists_kernel); by default such a query is cut into ONE round
     of workgroups -- uniform splits, the columns that do not fit as a tail launch (api.hip: plan_l2, one_round).  The cut
     launch, the one-round plan, the cost model's plan, merged and unmerged lists and caller-chosen splits return the same bits; rows sampled against the oracle (all three geometries,

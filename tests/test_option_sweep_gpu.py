@@ -201,7 +201,7 @@ def test_candidate_mode_under_cand_slack_and_masks(gpu_lib, metric):
 
 
 def test_refused_options_leave_the_index_usable(gpu_lib):
-    """Unknown names, order_flags (experiments builds only) and a split_refs_max that would need more than 1024 / L splits
+    """Unknown names, order_flags (removed) and a split_refs_max that would need more than 1024 / L splits
     are refused (ValueError); after each refusal the same index answers with the oracle's bits."""
     from nabo_amd._synth import pca_like
     n, g, m, k = 5000, 30, 400, 11

@@ -1,4 +1,4 @@
-"""Turn a tools/r3_pmc.sh (round 2: tools/r2_callB.sh) output directory into profiles/pmc.json, the record bench.py's roofline reads:
+"""Turn the output directory of a rocprofv3 --pmc collection (profiles/README.md) into profiles/pmc.json, the record bench.py's roofline reads:
 HBM-side bytes and matrix-pipe occupancy of the Euclidean filter kernel, vector instructions of the mod-Canberra
 filter, each keyed by workload and by a digest of the kernel's SOURCES (nabo_amd/_lib.py: src_digest(KERNEL_SOURCES[...]) --
 reproducible after a rebuild, unlike the bytes of the .so).
@@ -41,7 +41,7 @@ rec["traffic"][be["config"]["workload"]] = {
     "clock_ghz_held": gui / 8.0 / (be["roofline"]["kernel_ms"] * 1e6),
     "insts": {k: c[k] for k in c if k.startswith("SQ_INSTS")},
     "wave_cycles": {k: c[k] for k in ("SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY", "SQ_ACTIVE_INST_VALU") if k in c},
-    "source": dst_prefix + "pmc_euclid_summary.csv (rocprofv3 --pmc, one counter group per pass, tools/r3_pmc.sh)"}
+    "source": dst_prefix + "pmc_euclid_summary.csv (rocprofv3 --pmc, one counter group per pass)"}
 bc = bench_line(os.path.join(src, "pmc_canberra_pass1.json"))
 ca = summary(os.path.join(src, "pmc_canberra_summary.csv"))
 kc = max([k for k in ca if "cbf_filter_kernel" in k or "cbb_filter_kernel" in k], key=lambda k: ca[k].get("SQ_INSTS_VALU", 0))
