@@ -285,9 +285,10 @@ int nabo_knn_devices(const double *X, int64_t m, const double *Y, int64_t n, int
                      int32_t n_devices, int32_t transport, int64_t *out_idx, double *out_dist);
 
 /* ---- SNN edge counts on device (consumer of the top-k: nabo/_mapping.py:186-198) --------
- * t_idx [m,k], r_idx [n,k] int64 DEVICE arrays (first k of the order rows).  For every
- * (t, slot s) writes out_snn[t*k+s] = | set(t_idx[t]) & set(r_idx[t_idx[t,s]]) | (int32,
- * device).  The weight round(snn/(2(k-1)-snn),2) and the snn>0 filter stay with the caller. */
+ * t_idx [m,k], r_idx [n,k] int64 DEVICE arrays (first k of the order rows): rows of DISTINCT entries; entries < 0
+ * are absent (nabo_sharded_query above) and belong to neither set.  For every (t, slot s) with j = t_idx[t,s] in
+ * [0, n) writes out_snn[t*k+s] = | set(t_idx[t]) & set(r_idx[j]) | (int32, device); 0 when j is absent or >= n.
+ * The weight round(snn/(2(k-1)-snn),2) and the snn>0 filter stay with the caller. */
 int nabo_snn_counts(int32_t device, const int64_t *t_idx, int64_t m,
                     const int64_t *r_idx, int64_t n, int32_t k, int32_t *out_snn);
 
@@ -314,7 +315,8 @@ int nabo_group_edges(int64_t n_nodes, int64_t n_rows, const int64_t *node, const
  *   permutation p: key(t,p) = top key_bits of splitmix64(seed + (p+1)*0x9E3779B97F4A7C15 + t*0xD1B54A32D192ED03),
  *                  label_p[t] = key <= (n_A-th smallest key); out_sizes[p] = #labelled (n_A unless keys tie)
  *   out_nge[r]  = #{p : multiplier * sum_{e in row r, label_p[t_e]} w_e / out_sizes[p]  >=  out_obs[r]}
- *   out_mean/out_sd[r] = mean and population sd of the permuted scores.  Edge sums are float64, in row order.
+ *   out_mean/out_sd[r] = mean and population sd of the permuted scores, sd two-pass: sqrt(sum_p (S_p - mean)^2 / n_perm).
+ *   Edge sums are float64, in row order.
  * key_bits in {8,16,..,64} (64 in production; small values force ties, for tests); n_perm <= 4096. */
 int nabo_score_null(int32_t device, int64_t n_ref, const int64_t *row_ptr, const int64_t *edge_t,
                     const double *edge_w, int64_t n_t, const uint8_t *group, int32_t n_perm, uint64_t seed,

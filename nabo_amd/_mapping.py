@@ -155,13 +155,31 @@ def pyset_iteration_order(rows):
     return perm.astype(np.int64)
 
 
+def _iteration_order_of_real_entries(t_idx):
+    """`pyset_iteration_order` for rows that may hold absent entries (< 0: a sharded query's short row, nabo_knn.h):
+    the real entries in the order `set(real entries)` iterates them, the absent ones behind (their counts are 0)."""
+    real = t_idx >= 0
+    if real.all():
+        return pyset_iteration_order(t_idx)
+    k = t_idx.shape[1]
+    front = np.argsort(~real, axis=1, kind="stable")                     # real entries first, in their own order
+    perm = front.copy()
+    n_real = real.sum(axis=1)
+    for kr in np.unique(n_real[n_real > 0]):
+        rows = np.flatnonzero(n_real == kr)
+        cols = front[rows, :kr]
+        order = pyset_iteration_order(np.take_along_axis(t_idx[rows], cols, axis=1))
+        perm[rows, :kr] = np.take_along_axis(cols, order, axis=1)
+    return perm
+
+
 def snn_edges_from_counts(t_idx, cnt, k):
     """Host half of `snn_edges`: shared-neighbour counts [m,k] -> (t, j, weight) edge list, a cell's edges in
     the order the reference's set iteration yields them (`pyset_iteration_order`)."""
     t_idx = np.asarray(t_idx)[:, :k]
     cnt = np.asarray(cnt)[:, :k]
     tab = snn_weight_table(k)
-    perm = pyset_iteration_order(t_idx)
+    perm = _iteration_order_of_real_entries(t_idx)
     t_idx = np.take_along_axis(t_idx, perm, axis=1)
     cnt = np.take_along_axis(cnt, perm, axis=1)
     tt, ss = np.nonzero(cnt > 0)

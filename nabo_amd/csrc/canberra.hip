@@ -208,7 +208,8 @@ __global__ __launch_bounds__(256) void merge_kernel(const double *__restrict__ p
     if (n_found && lane == 0) n_found[row] = nreal;
 }
 
-// SNN shared-neighbour counts (nabo/_mapping.py:190-193): thread per (target, slot).
+// SNN shared-neighbour counts (nabo/_mapping.py:190-193): thread per (target, slot).  Rows hold distinct entries;
+// an entry < 0 is absent (a sharded query's short row) and is never a shared neighbour.
 __global__ void snn_counts_kernel(const int64_t *__restrict__ t_idx, int64_t m, const int64_t *__restrict__ r_idx,
                                   int64_t n, int k, int32_t *__restrict__ out)
 {
@@ -221,6 +222,7 @@ __global__ void snn_counts_kernel(const int64_t *__restrict__ t_idx, int64_t m, 
         const int64_t *a = t_idx + t * k, *b = r_idx + j * k;
         for (int p = 0; p < k; ++p) {
             const int64_t ap = a[p];
+            if (ap < 0) continue;
             for (int q = 0; q < k; ++q)
                 if (ap == b[q]) { ++snn; break; }
         }

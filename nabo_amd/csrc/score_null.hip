@@ -8,7 +8,8 @@
 //   Permutation p relabels the pooled cells: key(t,p) = top key_bits of splitmix64(seed, p, t),
 //   T_p = the n_A-th smallest key, label_p[t] = (key <= T_p), n_p = #labelled (= n_A unless keys tie at T_p),
 //   S_p[r] = mult * sum_{e: r_e = r, label_p[t_e]} w_e / n_p.
-//   Outputs per reference node: S_obs, n_ge = #{p: S_p >= S_obs}, mean and sd of S_p over p.
+//   Outputs per reference node: S_obs, n_ge = #{p: S_p >= S_obs}, mean and population sd of S_p over p (two-pass:
+//   sd = sqrt(sum_p (S_p - mean)^2 / P)).
 //
 // Integer results (thresholds, labels, n_p, n_ge) are bit-exact against the oracle; edge sums run in float64 in
 // CSR order like the oracle's.  HBM-bound byte work: a label BIT-matrix [n_t][ceil(P/32)] is built once
@@ -75,7 +76,8 @@ __global__ __launch_bounds__(256) void null_label_kernel(int64_t n_t, int P, int
 }
 
 // One workgroup per reference node (CSR row): thread q accumulates permutations q, q+256, ... (and slot P,
-// the observed grouping) over the row's edges in order, then the row's statistics are reduced.
+// the observed grouping) over the row's edges in order, then the row's statistics are reduced: the mean first, then
+// the squared deviations from it (the scores stay in registers between the two tree reductions).
 template <int NACC>
 __global__ __launch_bounds__(256) void null_score_kernel(const int64_t *__restrict__ row_ptr,
                                                          const int64_t *__restrict__ edge_t,
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(256) void null_score_kernel(const int64_t *__restri
                                                          int64_t *__restrict__ out_nge, double *__restrict__ out_mean,
                                                          double *__restrict__ out_sd)
 {
-    __shared__ double s_sum[256], s_sq[256];
+    __shared__ double s_red[256];
     __shared__ unsigned int s_ge;
     __shared__ double s_obs;
     const int64_t r = blockIdx.x;
@@ -108,34 +110,49 @@ __global__ __launch_bounds__(256) void null_score_kernel(const int64_t *__restri
     if (q == (P & 255)) s_obs = __ddiv_rn(__dmul_rn(mult, acc[P >> 8]), (double)n_a);
     __syncthreads();
     const double obs = s_obs;
-    double sum = 0.0, sq = 0.0;
+    double sum = 0.0;
     unsigned int ge = 0;
 #pragma unroll
     for (int i = 0; i < NACC; ++i) {
         const int p = q + 256 * i;
         if (p < P) {
             const double s = __ddiv_rn(__dmul_rn(mult, acc[i]), (double)n_lab[p]);
+            acc[i] = s;                       // kept for the second pass
             sum += s;
-            sq += s * s;
             ge += (s >= obs) ? 1u : 0u;
         }
     }
-    s_sum[q] = sum;
-    s_sq[q] = sq;
+    s_red[q] = sum;
     if (ge) atomicAdd(&s_ge, ge);
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
-        if (q < o) { s_sum[q] += s_sum[q + o]; s_sq[q] += s_sq[q + o]; }
+        if (q < o) s_red[q] += s_red[q + o];
+        __syncthreads();
+    }
+    // two-pass: squared deviations from the mean.  sum(s^2)/P - mean^2 cancels to nothing once the spread of the
+    // permuted scores falls below ~1e-8 of their size (a node every pooled cell has an equal edge to)
+    const double mean = s_red[0] / (double)P;
+    __syncthreads();
+    double dev = 0.0;
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) {
+        const int p = q + 256 * i;
+        if (p < P) {
+            const double d = acc[i] - mean;
+            dev += d * d;
+        }
+    }
+    s_red[q] = dev;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (q < o) s_red[q] += s_red[q + o];
         __syncthreads();
     }
     if (q == 0) {
-        const double mean = s_sum[0] / (double)P;
-        double var = s_sq[0] / (double)P - mean * mean;
-        if (var < 0.0) var = 0.0;
         out_obs[r] = obs;
         out_nge[r] = (int64_t)s_ge;
         out_mean[r] = mean;
-        out_sd[r] = sqrt(var);
+        out_sd[r] = sqrt(s_red[0] / (double)P);
     }
 }
 

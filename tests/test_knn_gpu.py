@@ -666,8 +666,13 @@ def test_mapping_score_permutation_null_vs_oracle(gpu_lib, n_ref, n_t, k, P, bit
         assert (ref["sizes"] > int(group.sum())).any()                    # 8-bit keys tie at the threshold
     assert np.array_equal(res["obs"], ref["obs"])                         # same float64 operations, same order
     assert np.array_equal(res["n_ge"], ref["n_ge"])
-    assert np.allclose(res["null_mean"], ref["null_mean"], rtol=1e-12, atol=1e-12)    # reduction order differs
-    assert np.allclose(res["null_sd"], ref["null_sd"], rtol=1e-9, atol=1e-9)
+    # reduction order differs: the derived bound on a float64 mean / two-pass sd (tests/_consumer_refs.py) against the
+    # longdouble statistics of the oracle's score matrix
+    import _consumer_refs as cr
+    mean_ld, sd_ld = cr.null_stats_ld(ref["scores"])
+    tol_mean, tol_sd = cr.null_bounds(ref["scores"])
+    assert (np.abs(res["null_mean"] - mean_ld) <= tol_mean).all()
+    assert (np.abs(res["null_sd"] - sd_ld) <= tol_sd).all()
     # the observed score is the reference's mapping score of the sample of interest (nabo/_graph.py:644-653)
     keep = group[edge_t] != 0
     sc = nabo_amd.mapping_score_from_edges(n_ref, edge_r[keep], w[keep], int(group.sum()))
