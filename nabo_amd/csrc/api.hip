@@ -128,6 +128,12 @@ struct nabo_index {
     bool packed_f32 = false, packed_c16 = false, packed_c1 = false;
     int64_t ref_tiles = 0, ref_tiles_alloc = 0;
     double ymax_sqrt = 0.0, ymax_sqrt_c = 0.0;
+    // the largest reference norm of the last pack, on its way to the host (ensure_packed / ymax_resolve): pinned word,
+    // the event behind its copy, which of the two values it becomes and the scale it was packed with
+    unsigned int *ymax_host = nullptr;
+    hipEvent_t ev_ymax = nullptr;
+    bool ymax_pending = false, ymax_f32 = false;
+    double ymax_scale = 1.0;
     // Canberra path: exact kernel operands (yt) and the fp32 lower-bound filter's (ycf)
     DevBuf yt, ycf, yrow, cbflag, ych, cbscale, xh;    // ych/xh: 7-bit operands of the counting pass, cbscale [2g] doubles (min, 1/step)
     int cb_gp = 0;
@@ -236,6 +242,8 @@ static int note_row_pass(nabo_index *ix, const uint32_t *d_rows, int64_t nf, uin
     return NABO_OK;
 }
 
+static int ymax_resolve(nabo_index *ix);
+
 // Pack the resident references for the fp32-MFMA kernel (want = 0), the f16x3 kernels (1: K-concatenated f16 tiles) or
 // the one-product pass of the l2q kernel (2).
 static int ensure_packed(nabo_index *ix, int want)
@@ -244,6 +252,7 @@ static int ensure_packed(nabo_index *ix, int want)
     if (want == 2 ? ix->packed_c1 : want == 1 ? ix->packed_c16 : ix->packed_f32) return NABO_OK;
     hipStream_t st = ix->stream;
     int rc;
+    if ((rc = ymax_resolve(ix))) return rc;                   // (a pack of other operands still owes its norm: normmax is reused)
     // normmax: [0] = max ||y~||^2 (float bits, SCALED units), [2..3] = max |y~ component| (double bits)
     if ((rc = ix->normmax.reserve(4 * sizeof(unsigned int)))) return rc;
     HIP_TRY(hipMemsetAsync(ix->normmax.p, 0, 4 * sizeof(unsigned int), st));
@@ -282,14 +291,31 @@ static int ensure_packed(nabo_index *ix, int want)
         HIP_TRY(nabo::pack_ref_launch(ix->dYp, ix->n, ix->g, ix->centre.as<double>(), ix->fscale, ix->ksteps,
                                       ix->ref_tiles_alloc, ix->dmask, ix->ypk.as<float>(), ix->normmax.as<unsigned int>(), st));
     }
-    HIP_TRY(hipMemcpyAsync(bits, ix->normmax.p, sizeof(bits), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    // The largest norm is read by nobody before the refine launch takes it as an argument: the copy goes to pinned memory
+    // behind the pack and the host goes on enqueueing (target pack, tournament, filter); ymax_resolve waits for it.
+    if (!ix->ymax_host) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ix->ymax_host), sizeof(unsigned int), hipHostMallocDefault));
+    HIP_TRY(hipMemcpyAsync(ix->ymax_host, ix->normmax.p, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(ix->ev_ymax, st));
+    ix->ymax_pending = true;
+    ix->ymax_f32 = !want_h;
+    ix->ymax_scale = scale;
+    if (want == 2) ix->packed_c1 = true;
+    else if (want_h) ix->packed_c16 = true;
+    else ix->packed_f32 = true;
+    return NABO_OK;
+}
+
+// ymax_sqrt / ymax_sqrt_c of the last pack, once its copy has arrived (every reader of the two calls this first)
+static int ymax_resolve(nabo_index *ix)
+{
+    if (!ix->ymax_pending) return NABO_OK;
+    HIP_TRY(hipEventSynchronize(ix->ev_ymax));
+    ix->ymax_pending = false;
     float fmax;
-    memcpy(&fmax, &bits[0], sizeof(fmax));
-    const double v = std::sqrt((double)fmax) / scale * (1.0 + 1e-6);      // unscaled units
-    if (want == 2) { ix->ymax_sqrt_c = v; ix->packed_c1 = true; }
-    else if (want_h) { ix->ymax_sqrt_c = v; ix->packed_c16 = true; }
-    else { ix->ymax_sqrt = v; ix->packed_f32 = true; }
+    memcpy(&fmax, ix->ymax_host, sizeof(fmax));
+    const double v = std::sqrt((double)fmax) / ix->ymax_scale * (1.0 + 1e-6);      // unscaled units
+    if (ix->ymax_f32) ix->ymax_sqrt = v;
+    else ix->ymax_sqrt_c = v;
     return NABO_OK;
 }
 
@@ -382,6 +408,7 @@ int nabo_index_create(nabo_index **out, int32_t device, int64_t n_ref, int32_t g
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&ix->stream2, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ix->ev_main, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ix->ev_ref, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ix->ev_ymax, hipEventDisableTiming);
     if (e != hipSuccess) {
         nabo_index_destroy(ix);
         return api_fail(NABO_E_HIP, "stream/event creation failed: %s", hipGetErrorString(e));
@@ -413,6 +440,8 @@ int nabo_index_destroy(nabo_index *ix)
     if (ix->stream2) { (void)hipStreamSynchronize(ix->stream2); (void)hipStreamDestroy(ix->stream2); }
     if (ix->ev_main) (void)hipEventDestroy(ix->ev_main);
     if (ix->ev_ref) (void)hipEventDestroy(ix->ev_ref);
+    if (ix->ev_ymax) (void)hipEventDestroy(ix->ev_ymax);
+    if (ix->ymax_host) (void)hipHostFree(ix->ymax_host);
     if (ix->stream) (void)hipStreamDestroy(ix->stream);
     delete ix;                       // every DevBuf member frees its allocation (the device is current)
     return NABO_OK;
@@ -440,6 +469,7 @@ int nabo_index_set_ref(nabo_index *ix, const double *Y, int32_t y_on_device, con
         ix->ref_tiles = (ix->n + 31) / 32;
         ix->ref_tiles_alloc = ix->ref_tiles + 64;      // room for split padding (+inf-norm tiles; up to 32 splits)
         ix->packed_f32 = ix->packed_c16 = ix->packed_c1 = false;
+        ix->ymax_pending = false;                      // (a read still in flight belongs to operands that are gone)
         ix->coarse_weak = false;
         if ((rc = ix->centre.reserve((size_t)ix->g * sizeof(double)))) return rc;
         if (ix->metric == NABO_METRIC_COSINE) {
@@ -592,6 +622,7 @@ int nabo_index_set_mask(nabo_index *ix, const uint8_t *ref_mask)
     }
     if (ix->metric != NABO_METRIC_MOD_CANBERRA && ix->ksteps > 0) {       // masked cells carry ||y||^2 = +inf in the packed tiles
         ix->packed_f32 = ix->packed_c16 = ix->packed_c1 = false;
+        ix->ymax_pending = false;                      // (a read still in flight belongs to operands that are gone)
         ix->coarse_weak = false;
         if ((rc = ensure_packed(ix, ix->coarse ? 2 : ix->mode == 1 ? 1 : 0))) return rc;
     }
@@ -964,6 +995,8 @@ static int l2_refine(nabo_index *ix, const Query &q, const L2Plan &P, L2Part (&p
     const double err_coef = P.use_h ? 1.05 * ((16.0 * P.kcq + 8.0) * std::ldexp(1.0, -24) + std::ldexp(1.0, -20) + std::ldexp(1.0, -21))
                                     : 1.05 * (2.0 * ix->ksteps + 4.0) * std::ldexp(1.0, -24);
     const double tau_scale = P.use_h ? 1.0 / (ix->hscale * ix->hscale) : 1.0 / (ix->fscale * ix->fscale);
+    int rc;
+    if ((rc = ymax_resolve(ix))) return rc;
     const double ymax_sqrt = P.use_h ? ix->ymax_sqrt_c : ix->ymax_sqrt;
     const int metric = ix->metric == NABO_METRIC_COSINE ? 2 : 0;
     const int64_t n_valid = ix->n - ix->n_masked;

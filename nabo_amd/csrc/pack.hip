@@ -132,10 +132,16 @@ __global__ void maxabs_kernel(const double *__restrict__ V, int64_t n, int g, co
                               unsigned long long *__restrict__ out_bits)
 {
     double m = 0.0;
-    const int64_t tot = n * g;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (int64_t)gridDim.x * blockDim.x) {
-        const double a = fabs(V[i] - centre[i % g]);
+    const int64_t tot = n * g, stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int re = (int)(stride % g);
+    int e = (int)(i % g);                                   // component of element i, carried along (no 64-bit modulo per element)
+#pragma unroll 4
+    for (; i < tot; i += stride) {
+        const double a = fabs(V[i] - centre[e]);
         if (a > m) m = a;                                   // NaN never wins
+        e += re;
+        if (e >= g) e -= g;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -171,45 +177,80 @@ hipError_t maxabs_launch(const double *V, int64_t n, int g, const double *centre
 //                slots 16 s + 8 (l >> 5) + j;
 //   L16 = true  (v_mfma_f32_16x16x32_f16; l2q kernel): register h (kc/2) + s, h < 2, s < kc/2, lane l: cell 16 h + (l & 15),
 //                slots 32 s + 8 (l >> 4) + j.
+// How the kernel goes through memory: the tile's 32 rows are read ONCE, by consecutive lanes at consecutive addresses (they
+// are one contiguous run of 32 g doubles unless `perm` reorders them), centred, scaled, rounded to fp32 and kept in LDS
+// (row stride g | 1 floats: the lanes of the norm pass, one row each, fall on distinct banks).  Lane c < 32 then walks
+// row c of the staged copy for the range check and ||rep||^2 -- a sequential float64 sum in component order, the order
+// every derived slot (nh, nl, ey / tx) and the certificate depend on -- and the cell's lanes fetch its norm slots with a
+// shuffle and convert their own 8 slots per register from the staged copy.  The largest reference norm goes out as at most
+// one atomicMax per wave (a maximum: the order it is taken in cannot change it).
+constexpr int PACK_WAVES = 4;       // tiles (waves) per block
+constexpr int PACK_BATCH = 8;       // staging loads a lane has in flight before the first one is used
 template <bool IS_REF, bool L16, int NSEG>
-__global__ __launch_bounds__(64) void pack_ctiles_kernel(const double *__restrict__ V, int64_t ncell, int g,
+__global__ __launch_bounds__(64 * PACK_WAVES) void pack_ctiles_kernel(const double *__restrict__ V, int64_t ncell, int g,
                                                          const double *__restrict__ centre, double scale, int kc,
                                                          int64_t ntiles_total, const uint8_t *__restrict__ mask,
                                                          unsigned char *__restrict__ out, double *__restrict__ norm64,
                                                          unsigned int *__restrict__ norm_max_bits,
                                                          const uint32_t *__restrict__ perm)
 {
-    const int64_t tile = blockIdx.x;
-    if (tile >= ntiles_total) return;
-    const int lane = threadIdx.x;
+    extern __shared__ float pack_stage[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tile = (int64_t)blockIdx.x * PACK_WAVES + wave;
+    const bool on = tile < ntiles_total;                     // (no early return: the block meets at a barrier)
     const int g1 = g + 1;
-    unsigned char *o = out + tile * (int64_t)kc * 1024;
-    const int nh_cells = L16 ? 2 : 1;                        // cells this lane packs
-    const int ks = L16 ? kc / 2 : kc;                        // registers per cell
-    const int grp = L16 ? lane >> 4 : lane >> 5;             // which 8 slots of a step this lane supplies
-    for (int hc = 0; hc < nh_cells; ++hc) {
-        const int c = L16 ? 16 * hc + (lane & 15) : lane & 31;
-        const int64_t cell = tile * 32 + c;
+    const int gs = g | 1;
+    float *stage = pack_stage + wave * 32 * gs;
+    {   // staging: flat element i = 64 it + lane of the tile is component e of its cell c.  A lane beyond the tile or the
+        // cells loads element 0 of the array instead (in range: ncell >= 1) and stores nothing.
+        const int q64 = 64 / g, r64 = 64 - q64 * g;
+        int c = lane / g, e = lane - c * g;
+        for (int base = 0; base < 32 * g; base += 64 * PACK_BATCH) {
+            double v[PACK_BATCH], ce[PACK_BATCH];
+            int slot[PACK_BATCH];
+#pragma unroll
+            for (int u = 0; u < PACK_BATCH; ++u) {
+                const int64_t cell = tile * 32 + c;
+                const bool ok = on && c < 32 && cell < ncell;
+                const int64_t row = ok ? cell : 0;
+                const int64_t src = perm ? (int64_t)perm[row] : row;
+                v[u] = V[ok ? src * g + e : 0];
+                ce[u] = centre[e];                           // e < g always
+                slot[u] = ok ? c * gs + e : -1;
+                c += q64;
+                e += r64;
+                if (e >= g) { e -= g; ++c; }
+            }
+#pragma unroll
+            for (int u = 0; u < PACK_BATCH; ++u)
+                if (slot[u] >= 0) stage[slot[u]] = (float)((v[u] - ce[u]) * scale);      // scale: a power of two (exact)
+        }
+    }
+    __syncthreads();
+    // whole-row pass, lane c < 32 for cell c: range check, ||rep||^2, and the norm slots that derive from them
+    float nh = 0.0f, nl = 0.0f, er = 0.0f;
+    int bad_i = 0;
+    unsigned int nmax = 0;
+    if (on && lane < 32) {
+        const int64_t cell = tile * 32 + lane;
         const bool live = cell < ncell;
         // locality order (order.hip, removed: see git history): packed position `cell` holds caller row perm[cell]; norm64 is indexed by POSITION
         const int64_t src = (live && perm) ? (int64_t)perm[cell] : cell;
-        // whole-row pass: range check and ||rep||^2 (every lane of a cell computes the same)
         bool bad = false;
         double ss = 0.0;
         for (int e = 0; e < g && live; ++e) {
-            const float f = (float)((V[src * g + e] - centre[e]) * scale);
+            const float f = stage[lane * gs + e];
             bad = bad || !(fabsf(f) <= 30000.0f);                 // f16 range (targets carry a factor 2); NaN / inf input
             const _Float16 h = (_Float16)f;
             const _Float16 l = (_Float16)(f - (float)h);
             const double rep = (double)(float)h + (double)(float)l;
             ss += rep * rep;
         }
-        float nh = 0.0f, nl = 0.0f, er = 0.0f;
         if (IS_REF) {
             float nf = __builtin_inff();
             if (live && !bad && !(mask && mask[src])) {
                 nf = (float)ss * 3.0517578125e-05f;                // ||y~||^2 (scaled units) * 2^-15
-                if (grp == 0) atomicMax(norm_max_bits, __float_as_uint((float)ss));
+                nmax = __float_as_uint((float)ss);
             }
             const _Float16 h = (_Float16)nf;
             nh = (float)h;
@@ -219,11 +260,33 @@ __global__ __launch_bounds__(64) void pack_ctiles_kernel(const double *__restric
             // segments 0 and 1; NOT scaled by -2: the product is +||y||^2.  (One-product operands: padding rows carry the
             // slots too -- 0 x inf would be the only NaN that kernel could see, and it is compiled with -fno-honor-nans.)
             nh = nl = (live || NSEG == 1) ? 32768.0f : 0.0f;
-            if (grp == 0 && live) norm64[cell] = bad ? __builtin_nan("") : ss / (scale * scale);
+            if (live) norm64[cell] = bad ? __builtin_nan("") : ss / (scale * scale);
             if (NSEG == 1 && live && !bad)
                 er = -fmaxf((float)(sqrt(ss) * (0.001953125 * 1.01 * 1.001953125)), 1.220703125e-4f);
         }
-        for (int s = 0; s < ks; ++s) {
+        bad_i = bad;
+    }
+    if (IS_REF) {
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) {
+            const unsigned int other = (unsigned int)__shfl_xor((int)nmax, o, 64);
+            nmax = other > nmax ? other : nmax;
+        }
+        // The maximum only grows, so a wave whose value is not above what it reads (however stale) has nothing to add: all
+        // but a few waves skip the atomic, and 31k of them on one address were two thirds of this kernel's time.
+        if (lane == 0 && nmax > *(volatile unsigned int *)norm_max_bits) atomicMax(norm_max_bits, nmax);
+    }
+    unsigned char *o = out + tile * (int64_t)kc * 1024;
+    const int nh_cells = L16 ? 2 : 1;                        // cells this lane packs
+    const int ks = L16 ? kc / 2 : kc;                        // registers per cell
+    const int grp = L16 ? lane >> 4 : lane >> 5;             // which 8 slots of a step this lane supplies
+    for (int hc = 0; hc < nh_cells; ++hc) {
+        const int c = L16 ? 16 * hc + (lane & 15) : lane & 31;
+        const bool live = on && tile * 32 + c < ncell;
+        const float nh_c = __shfl(nh, c, 64), nl_c = __shfl(nl, c, 64), er_c = __shfl(er, c, 64);
+        const bool bad = __shfl(bad_i, c, 64) != 0;
+        const float *row = stage + c * gs;
+        for (int s = 0; s < ks && on; ++s) {
             f16x8 v;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -233,9 +296,9 @@ __global__ __launch_bounds__(64) void pack_ctiles_kernel(const double *__restric
                     const int seg = p / g1, e = p - seg * g1;
                     if (seg < 3) {
                         if (e == g) {
-                            val = seg == 0 ? nh : seg == 1 ? nl : 0.0f;
+                            val = seg == 0 ? nh_c : seg == 1 ? nl_c : 0.0f;
                         } else if (live && !bad) {
-                            const float f = (float)((V[src * g + e] - centre[e]) * scale);
+                            const float f = row[e];
                             const _Float16 h = (_Float16)f;
                             const float lo = (float)(_Float16)(f - (float)h);
                             const bool want_lo = IS_REF ? seg == 1 : seg == 2;
@@ -244,11 +307,11 @@ __global__ __launch_bounds__(64) void pack_ctiles_kernel(const double *__restric
                         }
                     }
                 } else {
-                    if (p == g) val = nh;
-                    else if (p == g + 1) val = nl;
-                    else if (p == g + 2) val = er;
+                    if (p == g) val = nh_c;
+                    else if (p == g + 1) val = nl_c;
+                    else if (p == g + 2) val = er_c;
                     else if (p < g && live && !bad) {
-                        val = (float)(_Float16)(float)((V[src * g + p] - centre[p]) * scale);
+                        val = (float)(_Float16)row[p];
                         if (!IS_REF) val *= -2.0f;
                     }
                 }
@@ -259,23 +322,25 @@ __global__ __launch_bounds__(64) void pack_ctiles_kernel(const double *__restric
     }
 }
 
+// one block packs PACK_WAVES tiles; each wave stages its 32 rows as fp32 in LDS
+#define PACK_CTILES_LAUNCH(IS_REF, L16, NSEG, V, ncell, mask, norm64, nmax)                                                   \
+    hipLaunchKernelGGL((pack_ctiles_kernel<IS_REF, L16, NSEG>), dim3((unsigned)((ntiles_total + PACK_WAVES - 1) / PACK_WAVES)), \
+                       dim3(64 * PACK_WAVES), (size_t)PACK_WAVES * 32 * (g | 1) * sizeof(float), st, V, ncell, g, centre, scale, \
+                       kc, ntiles_total, mask, out, norm64, nmax, perm)
+
 // nseg: 3 = f16x3 operands, 1 = the one-product operands
 hipError_t pack_cref_launch(const double *Y, int64_t n, int g, const double *centre, double scale, int kc,
                             int64_t ntiles_total, const uint8_t *mask, unsigned char *out, unsigned int *norm_max_bits,
                             bool layout16, hipStream_t st, const uint32_t *perm, int nseg)
 {
     if (nseg == 1 && layout16)
-        hipLaunchKernelGGL((pack_ctiles_kernel<true, true, 1>), dim3((unsigned)ntiles_total), dim3(64), 0, st, Y, n, g, centre,
-                           scale, kc, ntiles_total, mask, out, (double *)nullptr, norm_max_bits, perm);
+        PACK_CTILES_LAUNCH(true, true, 1, Y, n, mask, (double *)nullptr, norm_max_bits);
     else if (nseg == 1)
-        hipLaunchKernelGGL((pack_ctiles_kernel<true, false, 1>), dim3((unsigned)ntiles_total), dim3(64), 0, st, Y, n, g, centre,
-                           scale, kc, ntiles_total, mask, out, (double *)nullptr, norm_max_bits, perm);
+        PACK_CTILES_LAUNCH(true, false, 1, Y, n, mask, (double *)nullptr, norm_max_bits);
     else if (layout16)
-        hipLaunchKernelGGL((pack_ctiles_kernel<true, true, 3>), dim3((unsigned)ntiles_total), dim3(64), 0, st, Y, n, g, centre,
-                           scale, kc, ntiles_total, mask, out, (double *)nullptr, norm_max_bits, perm);
+        PACK_CTILES_LAUNCH(true, true, 3, Y, n, mask, (double *)nullptr, norm_max_bits);
     else
-        hipLaunchKernelGGL((pack_ctiles_kernel<true, false, 3>), dim3((unsigned)ntiles_total), dim3(64), 0, st, Y, n, g, centre,
-                           scale, kc, ntiles_total, mask, out, (double *)nullptr, norm_max_bits, perm);
+        PACK_CTILES_LAUNCH(true, false, 3, Y, n, mask, (double *)nullptr, norm_max_bits);
     return hipGetLastError();
 }
 
@@ -284,17 +349,13 @@ hipError_t pack_cquery_launch(const double *X, int64_t m, int g, const double *c
                               const uint32_t *perm, int nseg)
 {
     if (nseg == 1 && layout16)
-        hipLaunchKernelGGL((pack_ctiles_kernel<false, true, 1>), dim3((unsigned)ntiles_total), dim3(64), 0, st, X, m, g, centre,
-                           scale, kc, ntiles_total, (const uint8_t *)nullptr, out, xnorm, (unsigned int *)nullptr, perm);
+        PACK_CTILES_LAUNCH(false, true, 1, X, m, (const uint8_t *)nullptr, xnorm, (unsigned int *)nullptr);
     else if (nseg == 1)
-        hipLaunchKernelGGL((pack_ctiles_kernel<false, false, 1>), dim3((unsigned)ntiles_total), dim3(64), 0, st, X, m, g, centre,
-                           scale, kc, ntiles_total, (const uint8_t *)nullptr, out, xnorm, (unsigned int *)nullptr, perm);
+        PACK_CTILES_LAUNCH(false, false, 1, X, m, (const uint8_t *)nullptr, xnorm, (unsigned int *)nullptr);
     else if (layout16)
-        hipLaunchKernelGGL((pack_ctiles_kernel<false, true, 3>), dim3((unsigned)ntiles_total), dim3(64), 0, st, X, m, g, centre,
-                           scale, kc, ntiles_total, (const uint8_t *)nullptr, out, xnorm, (unsigned int *)nullptr, perm);
+        PACK_CTILES_LAUNCH(false, true, 3, X, m, (const uint8_t *)nullptr, xnorm, (unsigned int *)nullptr);
     else
-        hipLaunchKernelGGL((pack_ctiles_kernel<false, false, 3>), dim3((unsigned)ntiles_total), dim3(64), 0, st, X, m, g, centre,
-                           scale, kc, ntiles_total, (const uint8_t *)nullptr, out, xnorm, (unsigned int *)nullptr, perm);
+        PACK_CTILES_LAUNCH(false, false, 3, X, m, (const uint8_t *)nullptr, xnorm, (unsigned int *)nullptr);
     return hipGetLastError();
 }
 
