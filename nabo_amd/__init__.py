@@ -9,6 +9,8 @@ from ._score import (get_mapping_score, mapping_score_from_edges, mapping_score_
                      get_mapping_score_null)
 from ._paths import (RefGraph, group_hops, get_mapping_specificity, get_ref_specificity,  # noqa: F401
                      calc_contiguous_spl)
+from ._classify import (classify_target, classify_from_edges, get_k_path_neighbours, get_de_groups,  # noqa: F401
+                        get_mapped_cells)
 
-__all__ = ["Mapping", "write_dense_pca", "expand_graph", "get_mapping_score", "mapping_score_from_edges", "mapping_score_null", "get_mapping_score_null", "RefGraph", "group_hops", "get_mapping_specificity", "get_ref_specificity", "calc_contiguous_spl", "knn", "knn_devices", "pairwise", "KnnIndex", "snn_counts", "device_count", "EUCLIDEAN", "MOD_CANBERRA", "COSINE",
+__all__ = ["classify_target", "classify_from_edges", "get_k_path_neighbours", "get_de_groups", "get_mapped_cells", "Mapping", "write_dense_pca", "expand_graph", "get_mapping_score", "mapping_score_from_edges", "mapping_score_null", "get_mapping_score_null", "RefGraph", "group_hops", "get_mapping_specificity", "get_ref_specificity", "calc_contiguous_spl", "knn", "knn_devices", "pairwise", "KnnIndex", "snn_counts", "device_count", "EUCLIDEAN", "MOD_CANBERRA", "COSINE",
            "NaboError"]

@@ -35,6 +35,10 @@ GRAPH_SYMBOLS = ["nabo_refgraph_create", "nabo_refgraph_destroy", "nabo_refgraph
                  "nabo_refgraph_last_stats", "nabo_refgraph_last_local_nodes"]
 
 
+# every symbol include/nabo_cluster.h declares (classification of target nodes, levels around node sets)
+CLUSTER_SYMBOLS = ["nabo_classify_targets", "nabo_refgraph_set_levels", "nabo_cluster_last_device_ms"]
+
+
 class NaboError(RuntimeError):
     pass
 
@@ -99,7 +103,10 @@ def lib():
     L.nabo_refgraph_group_hops.argtypes = [vp, i64, vp, vp, vp, vp, vp]
     L.nabo_refgraph_last_stats.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
     L.nabo_refgraph_last_local_nodes.argtypes = [vp, i64, vp]
-    for name in SYMBOLS + GRAPH_SYMBOLS:
+    L.nabo_classify_targets.argtypes = [i32, i64, vp, i32, i64, vp, vp, vp, dbl, i64, dbl, vp, vp, vp, vp]
+    L.nabo_refgraph_set_levels.argtypes = [vp, i64, vp, vp, i32, vp]
+    L.nabo_cluster_last_device_ms.argtypes = [C.POINTER(dbl)]
+    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS:
         if name not in ("nabo_version", "nabo_last_error"):
             getattr(L, name).restype = C.c_int
     _lib = L

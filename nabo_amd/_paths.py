@@ -61,6 +61,18 @@ class _DeviceGraph:
                                                        s.ctypes.data, u.ctypes.data, None if ph is None else ph.ctypes.data))
         return (s, u, ph) if pair_hops else (s, u)
 
+    def set_levels(self, set_ptr, members, max_level=-1):
+        """int32 [n_sets, n]: hops from every node to the nearest member of each set (nabo_refgraph_set_levels,
+        include/nabo_cluster.h); -1 = unreachable or beyond max_level (max_level < 0: no limit)"""
+        set_ptr, members = _i64(set_ptr, "set_ptr"), _i64(members, "members")
+        if set_ptr.shape[0] < 1 or int(set_ptr[-1]) != members.shape[0]:
+            raise ValueError("ERROR: set_ptr must have n_sets + 1 entries ending at len(members)")
+        S = set_ptr.shape[0] - 1
+        out = np.empty((S, self.n), dtype=np.int32)
+        _lib.check(_lib.lib().nabo_refgraph_set_levels(self._h, int(S), set_ptr.ctypes.data, members.ctypes.data,
+                                                       int(max_level), out.ctypes.data))
+        return out
+
     def last_stats(self):
         """{"ms": (build, local, global, total), "local_groups", "global_groups", "sweeps", "max_level"}"""
         ms = (C.c_double * 4)()
@@ -111,8 +123,18 @@ def _open_ref(h5, ref_name):
     return names, {n: i for i, n in enumerate(names)}, h5["name_stash/ref_name"][1].decode("UTF-8")
 
 
-def _target_rows(h5, target, pos):
-    """(target node names in load order, ptr, reference positions) of one mapped sample; KeyError if absent"""
+def _ref_nodes_in_file_order(h5, ref_uid):
+    """Graph.refNodes: the reference's nodes as load_from_h5 meets them (HDF5 name order of its graph group; the
+    columnar layout lists them in that order too, see read_graph_csr)"""
+    from ._mapping import _G_NODES, _G_PTR
+    grp = h5[ref_uid + "_graph"]
+    if _G_PTR in grp:
+        return sorted(x.decode("UTF-8") for x in grp[_G_NODES][:])
+    return [n for n in grp]
+
+
+def _target_rows_w(h5, target, pos):
+    """(target node names in load order, ptr, reference positions, weights) of one mapped sample; KeyError if absent"""
     from ._mapping import read_graph_csr
     uid = None
     if "target_names" in h5["name_stash"]:
@@ -121,8 +143,12 @@ def _target_rows(h5, target, pos):
                 uid = i[1].decode("UTF-8")
     if uid is None:
         raise KeyError(target)
-    nodes, ptr, nbr, _ = read_graph_csr(h5[uid + "_graph"], pos)
-    return nodes, ptr, nbr
+    return read_graph_csr(h5[uid + "_graph"], pos)
+
+
+def _target_rows(h5, target, pos):
+    """(target node names in load order, ptr, reference positions) of one mapped sample; KeyError if absent"""
+    return _target_rows_w(h5, target, pos)[:3]
 
 
 def _mapped_sets(ptr, nbr):
@@ -137,12 +163,7 @@ def _mapped_sets(ptr, nbr):
 
 def _ref_specificity(h5, ref_name, target, target_values, incl_unmapped):
     names, pos, ref_uid = _open_ref(h5, ref_name)
-    grp = h5[ref_uid + "_graph"]
-    from ._mapping import _G_NODES, _G_PTR
-    if _G_PTR in grp:
-        ref_nodes = sorted(x.decode("UTF-8") for x in grp[_G_NODES][:])
-    else:
-        ref_nodes = [n for n in grp]
+    ref_nodes = _ref_nodes_in_file_order(h5, ref_uid)
     t_nodes, ptr, nbr = _target_rows(h5, target, pos)
     return _ref_specificity_rows(ref_nodes, pos, len(names), t_nodes, ptr, nbr, target_values, incl_unmapped)
 
@@ -227,6 +248,10 @@ class RefGraph:
             rows, ptr, nbr, _ = read_graph_csr(h5[ref_uid + "_graph"], self.pos)
         # rows in the group's order -> a CSR by reference position (arc direction does not matter to the device)
         src = np.repeat(np.array([self.pos[r] for r in rows], dtype=np.int64), np.diff(ptr))
+        self.ref_nodes = list(rows)      # Graph.refNodes: read_graph_csr lists rows in the file's node order (either layout)
+        self.selfloop = np.zeros(len(self.names), dtype=bool)
+        self.selfloop[src[src == nbr]] = True
+        self.deTestCells, self.deCtrlCells = None, None
         order = np.argsort(src, kind="stable")
         cptr = np.zeros(len(self.names) + 1, dtype=np.int64)
         np.cumsum(np.bincount(src, minlength=len(self.names)), out=cptr[1:])
@@ -280,6 +305,41 @@ class RefGraph:
         (node names).  Fewer than 2 nodes give NaN (np.mean of nothing); an unknown node raises KeyError; an
         unreachable pair raises ValueError (the reference: networkx.NodeNotFound / NetworkXNoPath)."""
         return _contiguous(self._g, self.names, [self.pos[n] for n in nodes])
+
+    def k_path_neighbours(self, nodes, k_dist, full_trail=False, trail_start=0):
+        """Graph.get_k_path_neighbours (nabo/_graph.py:956-987): the reference nodes at exactly `k_dist` hops from the
+        node list, or with full_trail the rings `1 + trail_start` .. `k_dist` one after the other.  The reference peels
+        rings off a copy of the graph (quadratic in the ring size); here one multi-source sweep gives every node's hop
+        level and the rings are read off it.  The list [list(nodes), ring 1, ..., ring k_dist] goes through the
+        reference's own return expressions (`rings[-1]`, `sum(rings[1 + trail_start:], [])`), so k_dist = 0 returns the
+        nodes as given, and trail_start >= k_dist or a negative trail_start behave as Python slices do.  Quirks kept:
+
+          * names that are not reference nodes are ignored from ring 1 on (but returned as given for k_dist = 0);
+          * a node with a SELF-LOOP appears again in the ring after its own: the reference removes the edges between
+            DISTINCT nodes of a ring only.  (A node listed twice in `nodes` loses its self-loop: combinations() pairs it
+            with itself.)
+          * rings stop growing when the component is exhausted: empty lists, no error.
+
+        The reference returns each ring in set order; here a ring is sorted by reference position."""
+        from ._classify import _k_path_neighbours
+        return _k_path_neighbours(self, nodes, k_dist, full_trail, trail_start)
+
+    def set_de_groups(self, target, min_score, node_dist, from_clusters=None, full_trail=False, trail_start=1,
+                      stringent_control=False, clusters=None):
+        """Graph.set_de_groups (nabo/_graph.py:989-1055): 'Test' = reference nodes whose mapping score for `target` is
+        >= min_score (`get_mapping_score(target, min_score=min_score, all_nodes=False)`, its errors pass through),
+        limited to the clusters `from_clusters` if given (a list, else TypeError; labels compared as str; `clusters` is
+        the dict Graph.import_clusters takes and is validated as in classify_target); 'Control' =
+        k_path_neighbours(Test, node_dist, full_trail, trail_start), without the nodes that have a score when
+        stringent_control; 'Other' = the rest.  A Test node stays Test when it is also in the ring.  Fewer than 5 Test
+        nodes: the reference's warning and None.  Else {"de_group": {reference node: group} in the file's node order,
+        "deTestCells": [...], "deCtrlCells": [...]} (cell names; Test in node order, Control in ring order), the two
+        lists also kept as attributes of those names."""
+        from ._classify import _set_de_groups
+        res = _set_de_groups(self, target, min_score, node_dist, from_clusters, full_trail, trail_start, stringent_control, clusters)
+        if res is not None:
+            self.deTestCells, self.deCtrlCells = res["deTestCells"], res["deCtrlCells"]
+        return res
 
 
 def get_mapping_specificity(mapping_h5_fn, ref_name, target_name, fill_na=True, device=0):

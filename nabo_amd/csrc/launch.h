@@ -144,4 +144,8 @@ hipError_t csr_build_launch(const int64_t *edge_r, const int64_t *edge_t, const 
                             size_t temp_bytes, int64_t *row_ptr, int64_t *out_t, double *out_w, unsigned int *flag,
                             hipStream_t st);
 
+
+// device time of the last classification / set-levels call, read by nabo_cluster_last_device_ms (classify.hip)
+void cluster_set_device_ms(int which, double ms);
+
 }  // namespace nabo

@@ -346,6 +346,71 @@ __global__ __launch_bounds__(256) void paths_clear_kernel(const int32_t *__restr
     }
 }
 
+// ---- levels around node sets (nabo_refgraph_set_levels): the same sweep with one bit per SET -------------------------
+// seeds: member i of the sweep sets bit seed_bit[i] on node seed_node[i].  A node may sit in several sets and a set
+// may name a node twice, so the masks are OR-ed; the thread that finds the node untouched lists it (once) in the
+// frontier and in the touched list.  counters must be zero before the launch.
+__global__ __launch_bounds__(256) void paths_seed_sets_kernel(const int32_t *__restrict__ seed_node, const uint8_t *__restrict__ seed_bit,
+                                                              int64_t n_seeds, int64_t n, uint64_t *__restrict__ visited,
+                                                              uint64_t *__restrict__ front, int32_t *__restrict__ cur,
+                                                              int32_t *__restrict__ touched, int64_t *__restrict__ counters,
+                                                              int32_t *__restrict__ level)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_seeds; i += (int64_t)gridDim.x * 256) {
+        const int32_t v = seed_node[i];
+        const int s = seed_bit[i];
+        const uint64_t was = atomicOr((unsigned long long *)&visited[v], 1ull << s);
+        atomicOr((unsigned long long *)&front[v], 1ull << s);
+        level[(int64_t)s * n + v] = 0;
+        if (was == 0) {
+            cur[atomicAdd((unsigned long long *)&counters[3], 1ull)] = v;
+            touched[atomicAdd((unsigned long long *)&counters[2], 1ull)] = v;
+        }
+    }
+}
+
+// after an expansion nxt[v] holds exactly the bits v gains at this level (expand masks out what v had): record them,
+// and clear the old frontier's masks as paths_check_kernel does
+__global__ __launch_bounds__(256) void paths_record_kernel(const int32_t *__restrict__ next_list, const uint64_t *__restrict__ nxt,
+                                                           const int32_t *__restrict__ cur, uint64_t *__restrict__ front, int64_t n,
+                                                           int32_t lvl, int32_t *__restrict__ level, const int64_t *__restrict__ counters)
+{
+    const int64_t n_next = counters[0], n_cur = counters[3];
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_next; i += stride) {
+        const int32_t v = next_list[i];
+        for (uint64_t b = nxt[v]; b; b &= b - 1) level[(int64_t)(__ffsll((unsigned long long)b) - 1) * n + v] = lvl;
+    }
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_cur; i += stride) front[cur[i]] = 0;
+}
+
+hipError_t paths_seed_sets_launch(const int32_t *seed_node, const uint8_t *seed_bit, int64_t n_seeds, int64_t n, uint64_t *visited,
+                                  uint64_t *front, int32_t *cur, int32_t *touched, int64_t *counters, int32_t *level, hipStream_t st)
+{
+    hipError_t e = hipMemsetAsync(counters, 0, 4 * sizeof(int64_t), st);
+    if (e != hipSuccess || n_seeds == 0) return e;
+    const int64_t want = (n_seeds + 255) / 256;
+    hipLaunchKernelGGL(paths_seed_sets_kernel, dim3((unsigned)(want > 1024 ? 1024 : want)), dim3(256), 0, st, seed_node, seed_bit, n_seeds,
+                       n, visited, front, cur, touched, counters, level);
+    return hipGetLastError();
+}
+
+// one level of a set sweep: expand, record the levels gained, fold the next frontier in
+hipError_t paths_set_level_launch(const int32_t *rowptr, const int32_t *col, const int32_t *cur, int32_t *next_list, uint64_t *visited,
+                                  uint64_t *front, uint64_t *nxt, int32_t *touched, int64_t n, int32_t lvl, int32_t *level,
+                                  int64_t *counters, int64_t n_cur_hint, hipStream_t st)
+{
+    const int64_t want = (n_cur_hint * GLOBAL_SUB + 255) / 256;
+    const unsigned g_exp = (unsigned)(want < 1 ? 1 : want > 4096 ? 4096 : want);
+    hipLaunchKernelGGL(paths_expand_kernel, dim3(g_exp), dim3(256), 0, st, rowptr, col, cur, (const uint64_t *)visited,
+                       (const uint64_t *)front, nxt, next_list, counters);
+    hipLaunchKernelGGL(paths_record_kernel, dim3(1024), dim3(256), 0, st, (const int32_t *)next_list, (const uint64_t *)nxt, cur, front, n,
+                       lvl, level, (const int64_t *)counters);
+    hipLaunchKernelGGL(paths_finalize_kernel, dim3(1024), dim3(256), 0, st, (const int32_t *)next_list, visited, front, nxt, touched,
+                       counters);
+    return hipGetLastError();
+}
+
 hipError_t paths_prefill_launch(const void *pairs, int64_t n, int32_t *pair_dist, hipStream_t st)
 {
     if (n == 0) return hipSuccess;
@@ -434,6 +499,7 @@ hipError_t paths_reduce_launch(const int64_t *pair_off, int64_t n_groups, const 
 #include <new>
 #include <vector>
 
+#include "../../include/nabo_cluster.h"
 #include "../../include/nabo_graph.h"
 #include "../../include/nabo_knn.h"
 #include "host_common.h"
@@ -789,6 +855,84 @@ int nabo_refgraph_last_local_nodes(const nabo_refgraph *g, int64_t n_groups, int
     if (n_groups != (int64_t)g->local_nodes.size())
         return nabo::api_fail(NABO_E_INVALID, "n_groups=%lld, the last call had %lld", (long long)n_groups, (long long)g->local_nodes.size());
     std::copy(g->local_nodes.begin(), g->local_nodes.end(), out);
+    return NABO_OK;
+}
+
+int nabo_refgraph_set_levels(nabo_refgraph *g, int64_t n_sets, const int64_t *set_ptr, const int64_t *members, int32_t max_level,
+                             int32_t *out_level)
+{
+    if (!g) return nabo::api_fail(NABO_E_INVALID, "NULL graph");
+    if (n_sets < 0 || n_sets >= ((int64_t)1 << 31)) return nabo::api_fail(NABO_E_INVALID, "n_sets=%lld out of range", (long long)n_sets);
+    if (!set_ptr) return nabo::api_fail(NABO_E_INVALID, "set_ptr is NULL");
+    if (set_ptr[0] != 0) return nabo::api_fail(NABO_E_INVALID, "set_ptr[0] = %lld, must be 0", (long long)set_ptr[0]);
+    for (int64_t i = 0; i < n_sets; ++i)
+        if (set_ptr[i + 1] < set_ptr[i]) return nabo::api_fail(NABO_E_INVALID, "set_ptr is not monotone at set %lld", (long long)i);
+    const int64_t M = set_ptr[n_sets], n = g->n;
+    if (M > 0 && !members) return nabo::api_fail(NABO_E_INVALID, "members is NULL");
+    if (M >= ((int64_t)1 << 31)) return nabo::api_fail(NABO_E_UNSUPPORTED, "%lld members: fewer than 2^31 per call", (long long)M);
+    if (n_sets > 0 && n > 0 && !out_level) return nabo::api_fail(NABO_E_INVALID, "out_level is NULL");
+    std::vector<int32_t> node((size_t)M);
+    std::vector<uint8_t> bit((size_t)M);
+    for (int64_t s = 0; s < n_sets; ++s)
+        for (int64_t i = set_ptr[s]; i < set_ptr[s + 1]; ++i) {
+            if (members[i] < 0 || members[i] >= n)
+                return nabo::api_fail(NABO_E_INVALID, "members[%lld] = %lld is not a node index in [0, %lld)", (long long)i, (long long)members[i], (long long)n);
+            node[i] = (int32_t)members[i];
+            bit[i] = (uint8_t)(s % 64);
+        }
+    int rc = use_device(g->device);
+    if (rc) return rc;
+    nabo::cluster_set_device_ms(1, 0.0);
+    if (n_sets == 0 || n == 0) return NABO_OK;
+    rc = ensure_global_state(g);
+    if (rc) return rc;
+    const int64_t per_sweep = std::min<int64_t>(64, n_sets);
+    DevBuf d_node, d_bit, d_level;
+    HIP_TRY(d_node.alloc((size_t)M * 4));
+    HIP_TRY(d_bit.alloc((size_t)M));
+    HIP_TRY(d_level.alloc((size_t)per_sweep * n * 4));
+    if (M) {
+        HIP_TRY(hipMemcpyAsync(d_node.p, node.data(), (size_t)M * 4, hipMemcpyHostToDevice, g->st));
+        HIP_TRY(hipMemcpyAsync(d_bit.p, bit.data(), (size_t)M, hipMemcpyHostToDevice, g->st));
+    }
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    HIP_TRY(hipEventCreate(&ev0));
+    HIP_TRY(hipEventCreate(&ev1));
+    struct EventPair {
+        hipEvent_t a, b;
+        ~EventPair() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
+    } events{ev0, ev1};
+    int32_t *cur = g->cur.as<int32_t>(), *nxt_list = g->next_list.as<int32_t>();
+    int64_t *cnt = g->counters.as<int64_t>();
+    double device_ms = 0;
+    for (int64_t s0 = 0; s0 < n_sets; s0 += 64) {
+        const int64_t ns = std::min<int64_t>(64, n_sets - s0), m0 = set_ptr[s0], nm = set_ptr[s0 + ns] - m0;
+        HIP_TRY(hipMemsetAsync(d_level.p, 0xFF, (size_t)ns * n * 4, g->st));
+        HIP_TRY(hipEventRecord(ev0, g->st));
+        HIP_TRY(nabo::paths_seed_sets_launch(d_node.as<int32_t>() + m0, d_bit.as<uint8_t>() + m0, nm, n, g->visited.as<uint64_t>(),
+                                             g->front.as<uint64_t>(), cur, g->touched.as<int32_t>(), cnt, d_level.as<int32_t>(), g->st));
+        HIP_TRY(hipMemcpyAsync(g->host_counters, cnt + 3, 8, hipMemcpyDeviceToHost, g->st));
+        HIP_TRY(hipStreamSynchronize(g->st));
+        int64_t n_cur = g->host_counters[0];
+        for (int32_t level = 1; n_cur > 0 && (max_level < 0 || level <= max_level); ++level) {
+            HIP_TRY(nabo::paths_set_level_launch(g->rowptr.as<int32_t>(), g->col.as<int32_t>(), cur, nxt_list, g->visited.as<uint64_t>(),
+                                                 g->front.as<uint64_t>(), g->nxt.as<uint64_t>(), g->touched.as<int32_t>(), n, level,
+                                                 d_level.as<int32_t>(), cnt, n_cur, g->st));
+            HIP_TRY(hipMemcpyAsync(g->host_counters, cnt, 8, hipMemcpyDeviceToHost, g->st));
+            HIP_TRY(nabo::paths_advance_launch(cnt, g->st));
+            HIP_TRY(hipStreamSynchronize(g->st));
+            n_cur = g->host_counters[0];
+            std::swap(cur, nxt_list);
+        }
+        HIP_TRY(nabo::paths_clear_launch(g->touched.as<int32_t>(), cnt, g->visited.as<uint64_t>(), g->front.as<uint64_t>(), g->st));
+        HIP_TRY(hipEventRecord(ev1, g->st));
+        HIP_TRY(hipMemcpyAsync(out_level + s0 * n, d_level.p, (size_t)ns * n * 4, hipMemcpyDeviceToHost, g->st));
+        HIP_TRY(hipStreamSynchronize(g->st));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+        device_ms += ms;
+    }
+    nabo::cluster_set_device_ms(1, device_ms);
     return NABO_OK;
 }
 
