@@ -38,6 +38,9 @@ GRAPH_SYMBOLS = ["nabo_refgraph_create", "nabo_refgraph_destroy", "nabo_refgraph
 # every symbol include/nabo_cluster.h declares (classification of target nodes, levels around node sets)
 CLUSTER_SYMBOLS = ["nabo_classify_targets", "nabo_refgraph_set_levels", "nabo_cluster_last_device_ms"]
 
+# every symbol include/nabo_de.h declares (the Mann-Whitney differential-expression test)
+DE_SYMBOLS = ["nabo_de_test", "nabo_de_last_device_ms"]
+
 
 class NaboError(RuntimeError):
     pass
@@ -106,7 +109,9 @@ def lib():
     L.nabo_classify_targets.argtypes = [i32, i64, vp, i32, i64, vp, vp, vp, dbl, i64, dbl, vp, vp, vp, vp]
     L.nabo_refgraph_set_levels.argtypes = [vp, i64, vp, vp, i32, vp]
     L.nabo_cluster_last_device_ms.argtypes = [C.POINTER(dbl)]
-    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS:
+    L.nabo_de_test.argtypes = [i32, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, dbl, dbl, i64] + [vp] * 10
+    L.nabo_de_last_device_ms.argtypes = [C.POINTER(dbl), C.POINTER(i64)]
+    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS:
         if name not in ("nabo_version", "nabo_last_error"):
             getattr(L, name).restype = C.c_int
     _lib = L

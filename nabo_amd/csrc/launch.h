@@ -144,6 +144,16 @@ hipError_t csr_build_launch(const int64_t *edge_r, const int64_t *edge_t, const 
                             size_t temp_bytes, int64_t *row_ptr, int64_t *out_t, double *out_w, unsigned int *flag,
                             hipStream_t st);
 
+// differential expression: keys of a gene chunk, their sort and the rank kernel (de_rank.hip)
+hipError_t de_temp_bytes(int64_t nnz_max, int64_t keys_max, int64_t n_seg, size_t *bytes);
+hipError_t de_expand_launch(const int32_t *cell, const float *val, int64_t nnz, const int64_t *gptr, int32_t n_genes_chunk,
+                            const float *sf, const int64_t *inv_ptr, const int32_t *inv_set, int64_t n_sets, uint32_t *cnt,
+                            uint32_t *off, void *temp, size_t temp_bytes, uint64_t *keys, int64_t key_base, hipStream_t st);
+hipError_t de_sort_launch(const uint64_t *keys_a, uint64_t *keys_b, int64_t n_keys, int64_t n_seg, void *temp, size_t temp_bytes,
+                          int64_t *seg, hipStream_t st);
+hipError_t de_rank_launch(const uint64_t *keys, const int64_t *seg, int64_t n_sets, const int64_t *set_size, int64_t n_pairs,
+                          const int32_t *pair_test, const int32_t *pair_ctrl, int64_t n_genes_chunk, double exp_frac_thresh,
+                          double log2_fc_thresh, int32_t *out_status, int64_t *out_i64, double *out_f64, hipStream_t st);
 
 // device time of the last classification / set-levels call, read by nabo_cluster_last_device_ms (classify.hip)
 void cluster_set_device_ms(int which, double ms);
