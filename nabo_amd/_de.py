@@ -230,6 +230,7 @@ class _DatasetFile:
         self.cell_idx = {x: n for n, x in enumerate(self.cells)}
         grp = self.h5["processed_data"] if "processed_data" in self.h5 else {}
         self.keep_genes_idx = [int(x) for x in grp["keep_genes_idx"][:]] if "keep_genes_idx" in grp else list(range(len(self.genes)))
+        self.keep_cells_idx = [int(x) for x in grp["keep_cells_idx"][:]] if "keep_cells_idx" in grp else list(range(len(self.cells)))
         if "sf" in grp:
             self.sf = grp["sf"][:]
             if self.sf.dtype != np.float32:
@@ -241,14 +242,45 @@ class _DatasetFile:
     def close(self):
         self.h5.close()
 
-    def csc(self, genes):
+    @staticmethod
+    def _record(d):
+        """(idx int64 strictly increasing, val float32) of an (idx, val) record; an index listed twice keeps its last
+        value, as the reference's scatter does"""
+        idx, val = np.asarray(d["idx"], dtype=np.int64), np.asarray(d["val"], dtype=np.float32)
+        if idx.shape[0] > 1 and (np.diff(idx) <= 0).any():
+            last = {int(c): k for k, c in enumerate(idx.tolist())}
+            keep = np.array(sorted(last.values()), dtype=np.int64)
+            idx, val = idx[keep], val[keep]
+            o = np.argsort(idx, kind="stable")
+            idx, val = idx[o], val[o]
+        return idx, val
+
+    def csr(self, cells_idx):
+        """(cell_ptr int64, gene int32, val float32, sf) over ALL cells of the file, from the `cell_data/<cell>` records
+        (nabo/_dataset.py:906-908): the rows of `cells_idx` are read, every other row is empty"""
+        n = len(self.cells)
+        counts = np.zeros(n, dtype=np.int64)
+        got = {}
+        cd = self.h5["cell_data"]
+        for i in dict.fromkeys(int(x) for x in cells_idx):
+            got[i] = self._record(cd[self.cells[i]][:])
+            counts[i] = got[i][0].shape[0]
+        order = sorted(got)
+        ptr = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(counts, out=ptr[1:])
+        gene = np.concatenate([got[i][0] for i in order] + [np.zeros(0, np.int64)])
+        if gene.size and (gene.min() < 0 or gene.max() >= len(self.genes)):
+            raise ValueError("ERROR: cell_data holds a gene index outside [0, %d)" % len(self.genes))
+        return ptr, gene.astype(np.int32), np.concatenate([got[i][1] for i in order] + [np.zeros(0, np.float32)]), self.sf
+
+    def csc(self, genes, upper=True):
         """the columns of `genes` as a _csc tuple.  A cell listed twice in a column keeps its last value, as the
-        reference's scatter does."""
+        reference's scatter does.  `upper`: look the names up in upper case, as get_norm_exp does (:186)."""
         ptr, cells, vals = [0], [], []
         gd = self.h5["gene_data"]
         for g in genes:
             try:
-                d = gd[g.upper()][:]
+                d = gd[g.upper() if upper else g][:]
             except KeyError:
                 raise KeyError("ERROR: This gene symbol does not exist in the dataset.")
             idx, val = np.asarray(d["idx"], dtype=np.int64), np.asarray(d["val"], dtype=np.float32)

@@ -41,6 +41,9 @@ CLUSTER_SYMBOLS = ["nabo_classify_targets", "nabo_refgraph_set_levels", "nabo_cl
 # every symbol include/nabo_de.h declares (the Mann-Whitney differential-expression test)
 DE_SYMBOLS = ["nabo_de_test", "nabo_de_last_device_ms"]
 
+# every symbol include/nabo_pca.h declares (PCA projection of sparse cells, per-gene statistics)
+PCA_SYMBOLS = ["nabo_pca_project", "nabo_gene_stats", "nabo_pca_last_device_ms"]
+
 
 class NaboError(RuntimeError):
     pass
@@ -111,7 +114,10 @@ def lib():
     L.nabo_cluster_last_device_ms.argtypes = [C.POINTER(dbl)]
     L.nabo_de_test.argtypes = [i32, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, dbl, dbl, i64] + [vp] * 10
     L.nabo_de_last_device_ms.argtypes = [C.POINTER(dbl), C.POINTER(i64)]
-    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS:
+    L.nabo_pca_project.argtypes = [i32, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, vp, i64, vp, i64, vp]
+    L.nabo_gene_stats.argtypes = [i32, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.nabo_pca_last_device_ms.argtypes = [C.POINTER(dbl), C.POINTER(i64)]
+    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS:
         if name not in ("nabo_version", "nabo_last_error"):
             getattr(L, name).restype = C.c_int
     _lib = L

@@ -155,6 +155,14 @@ hipError_t de_rank_launch(const uint64_t *keys, const int64_t *seg, int64_t n_se
                           const int32_t *pair_test, const int32_t *pair_ctrl, int64_t n_genes_chunk, double exp_frac_thresh,
                           double log2_fc_thresh, int32_t *out_status, int64_t *out_i64, double *out_f64, hipStream_t st);
 
+// PCA projection of sparse cells and per-gene statistics (pca_project.hip)
+hipError_t pca_project_launch(const int64_t *ptr, const int32_t *gene, const float *val, const float *sf_row, int64_t n_rows,
+                              const int32_t *gene_pos, const double *sigma, const double *bias, const double *Tt, int C, double *Z,
+                              hipStream_t st);
+hipError_t gene_stats_launch(const int64_t *gptr, const int32_t *cell, const float *val, const float *sf, const uint8_t *kept,
+                             const uint8_t *keep_gene, int64_t n_genes, int64_t n_keep, int64_t *out_ncells, uint8_t *out_valid,
+                             double *out_m, double *out_nzm, double *out_var, hipStream_t st);
+
 // device time of the last classification / set-levels call, read by nabo_cluster_last_device_ms (classify.hip)
 void cluster_set_device_ms(int which, double ms);
 
