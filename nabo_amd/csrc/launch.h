@@ -11,7 +11,7 @@
 #include <hip/hip_runtime.h>
 #endif
 
-struct nabo_index;     // api.hip
+struct nabo_index;     // index.h
 
 namespace nabo {
 

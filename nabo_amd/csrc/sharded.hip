@@ -773,7 +773,7 @@ int nabo_sharded_query(nabo_comm *c, nabo_index *ix, const double *X, int64_t m,
     if (!c) return api_fail(NABO_E_INVALID, "NULL communicator");
     if (c->aborted) return comm_dead(c);
     // With more than one shard, a shard's local queries must not continue a short row with its MASKED references
-    // (api.hip: tail_len): they would enter the merge as neighbours.  Rows with fewer than k' unmasked references in
+    // (query.hip: tail_len): they would enter the merge as neighbours.  Rows with fewer than k' unmasked references in
     // the WHOLE reference set then end in absent entries (-1 / NaN) instead of the ignored references by index.
     const bool shards = ix && c->world > 1;
     if (shards) nabo::index_set_shard_mode(ix, true);
@@ -886,7 +886,7 @@ static int sharded_query_impl(nabo_comm *c, nabo_index *ix, const double *X, int
                                c->ci.as<int64_t>() + ms * Ls, c->cd.as<double>() + ms * Ls, nx, c->cb.as<double>() + ms, ms_pad - ms);
             if (hipGetLastError() != hipSuccess) rc = api_fail(NABO_E_HIP, "fill_absent_kernel launch failed");
         }
-        // One-product first pass (api.hip): with few pieces a shard's Ls-th candidate is close to the global k'-th, and the
+        // One-product first pass (plan.hip): with few pieces a shard's Ls-th candidate is close to the global k'-th, and the
         // certificate needs the exact distance of the first candidate left out, not the one-product threshold (three
         // kept entries more than emitted); with many pieces it lies far beyond it and the shorter lists win (one rank of
         // eight: 25 instead of 32 ms, one refused row at 1M x 1M).

@@ -15,10 +15,10 @@ import numpy as np
 from nabo_amd._synth import pca_like
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-API_SOURCE = os.path.join(REPO, "nabo_amd", "csrc", "api.hip")
+API_SOURCE = os.path.join(REPO, "nabo_amd", "csrc", "plan.hip")
 
 NABO_MAX_K = 56                 # include/nabo_knn.h: k + drop_first of the filter kernels; beyond it the exact route
-CB_BITMAP_REFS = 12 * 2048      # api.hip: a modified-Canberra index builds bitmaps from this many references on
+CB_BITMAP_REFS = 12 * 2048      # set_ref.hip: a modified-Canberra index builds bitmaps from this many references on
 L2_MODES = (None, "f16x3", "f32")                    # NABO_L2_MODE (read once, in nabo_index_create)
 CANBERRA_MODES = (None, "exact", "swar", "bits")     # NABO_CANBERRA_MODE (None: by the size of the reference set)
 DIST_FACTORS = (0.1, 0.25, 1.0, 3.0)
@@ -55,7 +55,7 @@ REFUSED_OPTIONS = ("order_flags",)                     # never drawn into a case
 
 
 def option_names(path=API_SOURCE):
-    """The names of OPTION_NAMES[] in api.hip, in table order."""
+    """The names of OPTION_NAMES[] in plan.hip, in table order."""
     src = open(path).read()
     body = re.search(r"OPTION_NAMES\[\]\s*=\s*\{(.*?)\n\};", src, re.S).group(1)
     return re.findall(r'\{\s*"([a-z0-9_]+)"\s*,', body)
@@ -72,7 +72,7 @@ def resolve(name, value, n, kk):
     if value == "list":
         return 64
     if value == "fit":
-        # api.hip: split_tiles = (split_refs_max - 1) / 32, s_min = ceil(ref_tiles / split_tiles) <= 1024 / 64 = 16
+        # plan.hip: split_tiles = (split_refs_max - 1) / 32, s_min = ceil(ref_tiles / split_tiles) <= 1024 / 64 = 16
         tiles = (n + 31) // 32
         split_tiles = max(2, -(-tiles // 16))
         return 32 * split_tiles + 1

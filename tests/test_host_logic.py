@@ -92,7 +92,7 @@ def test_list_entries_order_as_doubles_like_their_fp32_keys():
 
 # ---- the launch planner (nabo_query_plan: a pure function of shapes and options -- no index, no device) -----------------------
 def test_query_plan_fills_the_chip_and_follows_the_list_rules():
-    """api.hip: plan_l2 through nabo_query_plan.  BASELINE's shapes: the default first pass is the one-product kernel in the
+    """plan.hip: plan_l2 through nabo_query_plan.  BASELINE's shapes: the default first pass is the one-product kernel in the
     geometry its lists want; a query with enough work is cut into at least as many workgroups as the part has CUs
     (configs[1], 100k x 100k, was 131 workgroups on 256 CUs in round 3); list lengths, split bounds and the tournament
     follow their documented rules; the fp32 / f16x3 modes and the exact route are planned, not discovered on the device."""

@@ -379,7 +379,7 @@ def test_config3_full_size_1M_every_filter_gives_the_same_bits_on_all_rows(gpu_l
 
 def test_canberra_tail_round_rows_are_exact(gpu_lib):
     """Many target rows: the last, partially filled round of workgroups is launched with its own reference
-    split (api.hip); rows of both launches must equal the oracle."""
+    split (plan.hip); rows of both launches must equal the oracle."""
     n, g, k = 20000, 30, 11
     m = 2048 * 16 + 700                       # one full round of one-wave workgroups + a tail
     Y = pca_like(n, g, seed=95)
@@ -498,7 +498,7 @@ def test_both_filter_kernels_give_the_same_bits(gpu_lib, m, n, g, k, drop):
 @pytest.mark.parametrize("mode,full_round", [("f32", 547), ("f16x3", 274)])
 def test_tail_round_split_rows_are_exact(gpu_lib, mode, full_round):
     """More target workgroups than resident slots: the last, partially filled round is launched with its
-    own reference split (api.hip "tail round").  Rows of BOTH launches must match the oracle."""
+    own reference split (plan.hip "tail round").  Rows of BOTH launches must match the oracle."""
     m, n = 140000, 20000     # fp32 kernel: 547 workgroups of 256 rows on 512 slots; f16x3: 274 of 512 rows on 256 slots
     Y = pca_like(n, 50, seed=71)
     X = pca_like(m, 50, seed=72)
@@ -959,7 +959,7 @@ def test_small_query_pads_cost_no_list_work(gpu_lib):
 @pytest.mark.parametrize("m,mode", [(300, ""), (70000, ""), (300, "f16x3"), (300, "f32")])
 def test_large_reference_sets_take_more_splits(gpu_lib, monkeypatch, m, mode):
     """A list entry holds the reference as a 25-bit offset into its split (topk_lists.h: the entry is a double -- key,
-    slot | offset -- so that a rescan is one v_max_f64 per entry); api.hip raises the split count of larger sets.  With the
+    slot | offset -- so that a rescan is one v_max_f64 per entry); plan.hip raises the split count of larger sets.  With the
     bound lowered to 5000 references per split, 60 000 references need 13 splits where the planner would take fewer (one
     for 70 000 rows, main and tail launch): same neighbours, same distances, and entries of every split carry the split's
     first reference back (indices beyond 2^25 / 5000 come out right)."""
@@ -1139,7 +1139,7 @@ def test_cut_launches_and_merged_lists_change_no_result(gpu_lib, m, n, g, k, dro
     """Fewer column-workgroups than slots.  (The one-product launch cut into equal pieces of the (column, reference tile)
     space -- option "pieces" -- was removed; accepted as a no-op.)  The several lists of a row are merged by their
     filter keys before the float64 re-evaluation (refine.hip: merge_lists_kernel); by default such a query is cut into ONE round
-    of workgroups -- uniform splits, the columns that do not fit as a tail launch (api.hip: plan_l2, one_round).  The cut
+    of workgroups -- uniform splits, the columns that do not fit as a tail launch (plan.hip: plan_l2, one_round).  The cut
     launch, the one-round plan, the cost model's plan, merged and unmerged lists and caller-chosen splits return the same bits; rows sampled against the oracle (all three geometries,
     cosine, the positional self-drop)."""
     Y = pca_like(n, g, seed=61)
@@ -1209,7 +1209,7 @@ def test_asynchronous_queries_overlap_and_return_the_same_bits(gpu_lib):
 
 @pytest.mark.parametrize("m,n,expect", [(4000, 30000, "cbb_filter"), (3000, 120000, "cbb_filter"), (4000, 20000, "cbf_filter")])
 def test_canberra_default_counting_pass_by_size(gpu_lib, m, n, expect):
-    """Which counting pass a modified-Canberra index picks when nobody pins it (api.hip: the bitmaps from 12 blocks = 24 576
+    """Which counting pass a modified-Canberra index picks when nobody pins it (set_ref.hip: the bitmaps from 12 blocks = 24 576
     references on, round 4; the SWAR count below), a masked reference set included -- equal to the oracle either way."""
     g, k = 50, 15
     Y = pca_like(n, g, seed=111)

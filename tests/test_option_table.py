@@ -1,4 +1,4 @@
-"""The option sweep's reach, checked without a GPU: every option of api.hip has sweep values and a line in the header,
+"""The option sweep's reach, checked without a GPU: every option of plan.hip has sweep values and a line in the header,
 the sweep's queries are planned down every launch shape nabo_query_plan describes, and no tool or test sets an
 environment variable that nothing reads."""
 import ast
@@ -16,7 +16,7 @@ REPO = S.REPO
 def test_every_option_has_sweep_values_and_is_documented():
     names = S.option_names()
     assert len(names) == len(set(names))
-    assert set(names) == set(S.OPTION_VALUES), "OPTION_NAMES (api.hip) and OPTION_VALUES (tests/_option_sweep.py) differ"
+    assert set(names) == set(S.OPTION_VALUES), "OPTION_NAMES (plan.hip) and OPTION_VALUES (tests/_option_sweep.py) differ"
     hdr = open(os.path.join(REPO, "include", "nabo_knn.h")).read()
     para = hdr[hdr.index("/* Tuning options of ONE index"):hdr.index("int nabo_index_set_option")]
     missing = [n for n in names if '"%s"' % n not in para]
