@@ -73,11 +73,15 @@ int nabo_gene_stats(int32_t device, int64_t n_genes, int64_t n_cells, const int6
 
 /* The benchmark's timer (tools/bench_pca.py).  Device time in ms, between HIP events and summed over the chunks, of the
  * calling thread's last nabo_pca_project -- ms[0] the uploads, ms[1] the kernel, ms[2] the download of Z -- or of its
- * last nabo_gene_stats -- ms[1] the kernel, ms[0] = ms[2] = 0 -- and the number of chunks that call took. */
+ * last nabo_gene_stats -- ms[1] the kernel, ms[0] = ms[2] = 0 -- or of its last nabo_pca_cov (nabo_pca_fit.h) -- ms[0]
+ * the uploads, ms[1] all kernels, ms[2] the downloads -- and the number of chunks that call took. */
 int nabo_pca_last_device_ms(double ms[3], int64_t *n_chunks);
 
 #ifdef __cplusplus
 }
 #endif
+
+/* the exact PCA fit's device half: mean and covariance of the scaled cells */
+#include "nabo_pca_fit.h"
 
 #endif /* NABO_PCA_H */

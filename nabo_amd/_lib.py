@@ -44,6 +44,9 @@ DE_SYMBOLS = ["nabo_de_test", "nabo_de_last_device_ms"]
 # every symbol include/nabo_pca.h declares (PCA projection of sparse cells, per-gene statistics)
 PCA_SYMBOLS = ["nabo_pca_project", "nabo_gene_stats", "nabo_pca_last_device_ms"]
 
+# every symbol include/nabo_pca_fit.h declares (mean and covariance of the scaled cells: the exact PCA fit)
+PCA_FIT_SYMBOLS = ["nabo_pca_cov", "nabo_pca_cov_last_phase_ms"]
+
 
 class NaboError(RuntimeError):
     pass
@@ -117,7 +120,9 @@ def lib():
     L.nabo_pca_project.argtypes = [i32, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, vp, i64, vp, i64, vp]
     L.nabo_gene_stats.argtypes = [i32, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.nabo_pca_last_device_ms.argtypes = [C.POINTER(dbl), C.POINTER(i64)]
-    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS:
+    L.nabo_pca_cov.argtypes = [i32, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, i64, vp, vp]
+    L.nabo_pca_cov_last_phase_ms.argtypes = [C.POINTER(dbl)]
+    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS:
         if name not in ("nabo_version", "nabo_last_error"):
             getattr(L, name).restype = C.c_int
     _lib = L

@@ -163,6 +163,24 @@ hipError_t gene_stats_launch(const int64_t *gptr, const int32_t *cell, const flo
                              const uint8_t *keep_gene, int64_t n_genes, int64_t n_keep, int64_t *out_ncells, uint8_t *out_valid,
                              double *out_m, double *out_nzm, double *out_var, hipStream_t st);
 
+// the exact PCA fit: dense centred rows, their column sums and Y^T Y by f64 MFMA (pca_fit.hip)
+int pca_fit_tile();                     // genes per side of an output tile; a row of the chunk holds a multiple of it
+int pca_fit_row_pad();                  // the chunk holds a multiple of this many rows
+int pca_fit_splits(int64_t n_tiles);    // partial tiles per tile, at most
+int pca_fit_sum_slices();               // partial column sums per column, at most
+hipError_t pca_densify_launch(const int64_t *ptr, const int32_t *gene, const float *val, const float *sf_row, int64_t n_rows, int64_t n_rows_pad,
+                              const int32_t *gene_pos, const double *mu, const double *sigma, const double *fill, const double *mean, int G,
+                              int Gp, double *Y, hipStream_t st);
+hipError_t pca_colsum_launch(const double *Y, int64_t n_rows, int Gp, double *partial, double *colsum, hipStream_t st);
+hipError_t pca_syrk_launch(const double *Y, int64_t n_rows_pad, int Gp, double *partial, double *acc, hipStream_t st);
+hipError_t pca_cov_finish_launch(const double *acc, int G, int64_t n, double *cov, hipStream_t st);
+// host checks the PCA entry points share, and what nabo_pca_last_device_ms reports (pca_project.hip)
+int pca_check_sparse(const char *major, const char *minor, int64_t n_major, int64_t n_minor, const int64_t *ptr, const int32_t *idx,
+                     const float *val, const float *sf, bool sf_by_major);
+int pca_check_selection(int64_t n_raw_genes, const int32_t *gene_pos, int64_t G, const double *sigma, int64_t n_cells, int64_t n_rows,
+                        const int64_t *rows);
+void pca_set_device_ms(const double ms[3], int64_t n_chunks);
+
 // device time of the last classification / set-levels call, read by nabo_cluster_last_device_ms (classify.hip)
 void cluster_set_device_ms(int which, double ms);
 

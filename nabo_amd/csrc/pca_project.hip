@@ -187,6 +187,56 @@ hipError_t gene_stats_launch(const int64_t *gptr, const int32_t *cell, const flo
     return hipGetLastError();
 }
 
+// a compressed sparse matrix with `n_major` lists over `n_minor` indices: pointers, order, range, and the float32
+// products (the size factor belongs to the cell: the list for rows of cells, the index for columns of genes)
+int pca_check_sparse(const char *major, const char *minor, int64_t n_major, int64_t n_minor, const int64_t *ptr, const int32_t *idx,
+                     const float *val, const float *sf, bool sf_by_major)
+{
+    const char *pn = sf_by_major ? "cell_ptr" : "gene_ptr";
+    if (!ptr) return api_fail(NABO_E_INVALID, "%s is NULL", pn);
+    if (ptr[0] != 0) return api_fail(NABO_E_INVALID, "%s[0] = %lld, must be 0", pn, (long long)ptr[0]);
+    for (int64_t i = 0; i < n_major; ++i)
+        if (ptr[i + 1] < ptr[i]) return api_fail(NABO_E_INVALID, "%s is not monotone at %s %lld", pn, major, (long long)i);
+    if (ptr[n_major] > 0 && (!idx || !val)) return api_fail(NABO_E_INVALID, "%s or val is NULL", minor);
+    if ((sf_by_major ? n_major : n_minor) > 0 && !sf) return api_fail(NABO_E_INVALID, "sf is NULL");
+    for (int64_t i = 0; i < n_major; ++i) {
+        int64_t last = -1;
+        for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) {
+            const int64_t j = idx[e];
+            if (j < 0 || j >= n_minor)
+                return api_fail(NABO_E_INVALID, "%s[%lld] = %lld is not a %s in [0, %lld)", minor, (long long)e, (long long)j, minor, (long long)n_minor);
+            if (j <= last)
+                return api_fail(NABO_E_INVALID, "the %ss of %s %lld are not strictly increasing at entry %lld", minor, major, (long long)i, (long long)e);
+            last = j;
+            const float v = val[e], x = v * sf[sf_by_major ? i : j];
+            if (!(v >= 0.0f) || std::isinf(v) || !(x >= 0.0f) || std::isinf(x))
+                return api_fail(NABO_E_INVALID, "entry %lld (%s %lld, %s %lld): value %g, scaled value %g: both must be finite and >= 0",
+                                (long long)e, major, (long long)i, minor, (long long)j, (double)v, (double)x);
+        }
+    }
+    return NABO_OK;
+}
+
+// gene_pos, sigma and rows of the projection and of the fit
+int pca_check_selection(int64_t n_raw_genes, const int32_t *gene_pos, int64_t G, const double *sigma, int64_t n_cells, int64_t n_rows,
+                        const int64_t *rows)
+{
+    std::vector<uint8_t> seen((size_t)G, 0);
+    for (int64_t j = 0; j < n_raw_genes; ++j) {
+        const int64_t p = gene_pos[j];
+        if (p < -1 || p >= G) return api_fail(NABO_E_INVALID, "gene_pos[%lld] = %lld is neither -1 nor a position in [0, %lld)", (long long)j, (long long)p, (long long)G);
+        if (p >= 0 && seen[p]) return api_fail(NABO_E_INVALID, "gene_pos[%lld] = %lld: another raw gene has this position already", (long long)j, (long long)p);
+        if (p >= 0) seen[p] = 1;
+    }
+    for (int64_t p = 0; p < G; ++p)
+        if (!(sigma[p] > 0.0) || std::isinf(sigma[p]))
+            return api_fail(NABO_E_INVALID, "sigma[%lld] = %g: must be finite and > 0", (long long)p, sigma[p]);
+    for (int64_t r = 0; rows && r < n_rows; ++r)
+        if (rows[r] < 0 || rows[r] >= n_cells)
+            return api_fail(NABO_E_INVALID, "rows[%lld] = %lld is not a cell in [0, %lld)", (long long)r, (long long)rows[r], (long long)n_cells);
+    return NABO_OK;
+}
+
 }  // namespace nabo
 
 // ---- the C ABI --------------------------------------------------------------------------------------------------------
@@ -209,37 +259,15 @@ struct Events {
     }
 };
 
-// a compressed sparse matrix with `n_major` lists over `n_minor` indices: pointers, order, range, and the float32
-// products (the size factor belongs to the cell: the list for rows of cells, the index for columns of genes)
-int check_sparse(const char *major, const char *minor, int64_t n_major, int64_t n_minor, const int64_t *ptr, const int32_t *idx,
-                 const float *val, const float *sf, bool sf_by_major)
-{
-    const char *pn = sf_by_major ? "cell_ptr" : "gene_ptr";
-    if (!ptr) return nabo::api_fail(NABO_E_INVALID, "%s is NULL", pn);
-    if (ptr[0] != 0) return nabo::api_fail(NABO_E_INVALID, "%s[0] = %lld, must be 0", pn, (long long)ptr[0]);
-    for (int64_t i = 0; i < n_major; ++i)
-        if (ptr[i + 1] < ptr[i]) return nabo::api_fail(NABO_E_INVALID, "%s is not monotone at %s %lld", pn, major, (long long)i);
-    if (ptr[n_major] > 0 && (!idx || !val)) return nabo::api_fail(NABO_E_INVALID, "%s or val is NULL", minor);
-    if ((sf_by_major ? n_major : n_minor) > 0 && !sf) return nabo::api_fail(NABO_E_INVALID, "sf is NULL");
-    for (int64_t i = 0; i < n_major; ++i) {
-        int64_t last = -1;
-        for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) {
-            const int64_t j = idx[e];
-            if (j < 0 || j >= n_minor)
-                return nabo::api_fail(NABO_E_INVALID, "%s[%lld] = %lld is not a %s in [0, %lld)", minor, (long long)e, (long long)j, minor, (long long)n_minor);
-            if (j <= last)
-                return nabo::api_fail(NABO_E_INVALID, "the %ss of %s %lld are not strictly increasing at entry %lld", minor, major, (long long)i, (long long)e);
-            last = j;
-            const float v = val[e], x = v * sf[sf_by_major ? i : j];
-            if (!(v >= 0.0f) || std::isinf(v) || !(x >= 0.0f) || std::isinf(x))
-                return nabo::api_fail(NABO_E_INVALID, "entry %lld (%s %lld, %s %lld): value %g, scaled value %g: both must be finite and >= 0",
-                                      (long long)e, major, (long long)i, minor, (long long)j, (double)v, (double)x);
-        }
-    }
-    return NABO_OK;
-}
-
 }  // namespace
+
+namespace nabo {
+void pca_set_device_ms(const double ms[3], int64_t n_chunks)
+{
+    for (int i = 0; i < 3; ++i) g_pca_ms[i] = ms[i];
+    g_pca_chunks = n_chunks;
+}
+}  // namespace nabo
 
 extern "C" {
 
@@ -258,29 +286,15 @@ int nabo_pca_project(int32_t device, int64_t n_cells, int64_t n_raw_genes, const
     if (!rows) n_rows = n_cells;
     if (n_rows < 0) return nabo::api_fail(NABO_E_INVALID, "n_rows=%lld is negative", (long long)n_rows);
     if (n_rows > 0 && !out_z) return nabo::api_fail(NABO_E_INVALID, "the output array is NULL");
-    int rc = check_sparse("cell", "gene", n_cells, n_raw_genes, cell_ptr, gene, val, sf, true);
+    int rc = nabo::pca_check_sparse("cell", "gene", n_cells, n_raw_genes, cell_ptr, gene, val, sf, true);
     if (rc) return rc;
-    {
-        std::vector<uint8_t> seen((size_t)G, 0);
-        for (int64_t j = 0; j < n_raw_genes; ++j) {
-            const int64_t p = gene_pos[j];
-            if (p < -1 || p >= G) return nabo::api_fail(NABO_E_INVALID, "gene_pos[%lld] = %lld is neither -1 nor a position in [0, %lld)", (long long)j, (long long)p, (long long)G);
-            if (p >= 0 && seen[p]) return nabo::api_fail(NABO_E_INVALID, "gene_pos[%lld] = %lld: another raw gene has this position already", (long long)j, (long long)p);
-            if (p >= 0) seen[p] = 1;
-        }
-    }
-    for (int64_t p = 0; p < G; ++p) {
-        if (!(sigma[p] > 0.0) || std::isinf(sigma[p]))
-            return nabo::api_fail(NABO_E_INVALID, "sigma[%lld] = %g: must be finite and > 0", (long long)p, sigma[p]);
+    if ((rc = nabo::pca_check_selection(n_raw_genes, gene_pos, G, sigma, n_cells, n_rows, rows))) return rc;
+    for (int64_t p = 0; p < G; ++p)
         if (!std::isfinite(mu[p]) || !std::isfinite(mean[p]))
             return nabo::api_fail(NABO_E_INVALID, "mu[%lld] = %g, mean[%lld] = %g: must be finite", (long long)p, mu[p], (long long)p, mean[p]);
-    }
     for (int64_t i = 0; i < (int64_t)C * G; ++i)
         if (!std::isfinite(components[i]))
             return nabo::api_fail(NABO_E_INVALID, "components[%lld][%lld] = %g: must be finite", (long long)(i / G), (long long)(i % G), components[i]);
-    for (int64_t r = 0; rows && r < n_rows; ++r)
-        if (rows[r] < 0 || rows[r] >= n_cells)
-            return nabo::api_fail(NABO_E_INVALID, "rows[%lld] = %lld is not a cell in [0, %lld)", (long long)r, (long long)rows[r], (long long)n_cells);
     // chunks of rows within the budget
     const int64_t budget = mem_budget_bytes > 0 ? mem_budget_bytes : PCA_DEFAULT_BUDGET;
     const int64_t per_row_fixed = 12 + 8 * (int64_t)C;
@@ -417,7 +431,7 @@ int nabo_gene_stats(int32_t device, int64_t n_genes, int64_t n_cells, const int6
     if (n_genes < 0 || n_genes >= ((int64_t)1 << 31) - 1) return nabo::api_fail(NABO_E_INVALID, "n_genes=%lld out of range [0, 2^31 - 1)", (long long)n_genes);
     if (n_cells < 0 || n_cells >= ((int64_t)1 << 31) - 1) return nabo::api_fail(NABO_E_INVALID, "n_cells=%lld out of range [0, 2^31 - 1)", (long long)n_cells);
     if (n_genes > 0 && (!out_ncells || !out_valid || !out_m || !out_nzm || !out_variance)) return nabo::api_fail(NABO_E_INVALID, "an output array is NULL");
-    int rc = check_sparse("gene", "cell", n_genes, n_cells, gene_ptr, cell, val, sf, false);
+    int rc = nabo::pca_check_sparse("gene", "cell", n_genes, n_cells, gene_ptr, cell, val, sf, false);
     if (rc) return rc;
     std::vector<uint8_t> kept((size_t)n_cells, keep_cells ? 0 : 1);
     if (!keep_cells) n_keep = n_cells;
