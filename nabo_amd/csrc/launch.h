@@ -1,7 +1,8 @@
 // launch.h -- every function of libnabo_knn.so that one translation unit defines and another calls: the kernel launchers,
-// their geometry and plan helpers, the index accessors sharded.hip uses, and the error recorder.  The defining file and
+// their geometry and plan helpers, the index accessors sharded.hip uses, and the error recorder (what sharded.hip asks
+// of comm.hip is declared in comm.h).  The defining file and
 // every caller include it, so each definition is checked against the one declaration here; default arguments live here
-// and nowhere else.  Host types only: tests/host_shim compiles sharded.hip and its fakes of some of these with g++.
+// and nowhere else.  Host types only: tests/host_shim compiles comm.hip, sharded.hip and its fakes of some of these with g++.
 #pragma once
 #include <cstddef>
 #include <cstdint>

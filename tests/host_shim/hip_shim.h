@@ -1,5 +1,5 @@
-// hip_shim.h -- TEST INFRASTRUCTURE: just enough of the HIP runtime, on HOST memory, to compile nabo_amd/csrc/sharded.hip
-// with g++ (-DNABO_SHARDED_HOST) and run its control flow on a box without a GPU: communicators, the loopback
+// hip_shim.h -- TEST INFRASTRUCTURE: just enough of the HIP runtime, on HOST memory, to compile nabo_amd/csrc/comm.hip and
+// sharded.hip with g++ (-DNABO_SHARDED_HOST) and run its control flow on a box without a GPU: communicators, the loopback
 // rendezvous, status agreements, the exchange / merge / certificate / second round / gather sequence of
 // nabo_sharded_query, its failure semantics.  "Device" memory is malloc'ed, streams are synchronous, a kernel launch runs
 // its grid as nested host loops (blockIdx / threadIdx are thread-local variables), RCCL is absent (the loader fails, as on

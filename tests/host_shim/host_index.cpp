@@ -1,4 +1,4 @@
-// host_index.cpp -- TEST INFRASTRUCTURE: the part of libnabo_knn.so that sharded.hip calls into, restated for the host
+// host_index.cpp -- TEST INFRASTRUCTURE: the part of libnabo_knn.so that comm.hip and sharded.hip call into, restated for the host
 // build (hip_shim.h): a nabo_index is a record whose candidate query / certified query are CALLBACKS the test installs,
 // the merge and gather kernels are plain loops in the canonical (distance, index) order of refine.hip's merge_kernel.
 #include <algorithm>

@@ -1,9 +1,9 @@
 """The PRODUCT's sharded-query control flow, compiled, on a box without a GPU.
 
 tests/test_dist_gloo.py runs a torch.distributed *restatement* of the protocol (tests/_dist_spec.py): it pins the
-protocol, not the implementation.  Here nabo_amd/csrc/sharded.hip ITSELF is compiled with g++ against tests/host_shim
-(-DNABO_SHARDED_HOST: "device" memory is malloc'ed, streams are synchronous, a kernel launch is a host loop) and driven
-through its C entry points with the loopback transport, N ranks as host threads: communicator creation, the 2-D layout,
+protocol, not the implementation.  Here nabo_amd/csrc/comm.hip and sharded.hip THEMSELVES are compiled with g++ against
+tests/host_shim (-DNABO_SHARDED_HOST: "device" memory is malloc'ed, streams are synchronous, a kernel launch is a host loop) and driven
+through their C entry points with the loopback transport, N ranks as host threads: communicator creation, the 2-D layout,
 status agreements, the grouped exchange, merge_parts + certify_kernel, the second round (adopt_kernel), the ragged-slice
 fill, the final gather, and the failure semantics (a rank failing alone, mismatched arguments, an allocation failure, a
 peer that never arrives, nabo_comm_abort from another thread).  What a rank's nabo_index would compute on the GPU -- its
@@ -26,7 +26,7 @@ from nabo_amd._synth import pca_like
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(REPO, "tests", "host_shim")
 SO = os.path.join(SHIM, "build", "libnabo_sharded_host.so")
-E_INVALID, E_HIP, E_NOMEM, E_COMM = -1, -3, -4, -6
+E_INVALID, E_HIP, E_NOMEM, E_UNSUPPORTED, E_COMM = -1, -3, -4, -5, -6
 
 CAND_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
 QUERY_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
@@ -34,9 +34,10 @@ QUERY_CB = C.CFUNCTYPE(C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_v
 
 @pytest.fixture(scope="module")
 def host():
-    srcs = [os.path.join(REPO, "nabo_amd", "csrc", "sharded.hip"), os.path.join(SHIM, "host_index.cpp")]
-    deps = srcs + [os.path.join(SHIM, "hip_shim.h"), os.path.join(REPO, "include", "nabo_knn.h"),
-                   os.path.join(REPO, "nabo_amd", "csrc", "launch.h"), os.path.join(REPO, "nabo_amd", "csrc", "host_common.h")]
+    csrc = os.path.join(REPO, "nabo_amd", "csrc")
+    srcs = [os.path.join(csrc, "comm.hip"), os.path.join(csrc, "sharded.hip"), os.path.join(SHIM, "host_index.cpp")]
+    deps = srcs + [os.path.join(SHIM, "hip_shim.h"), os.path.join(REPO, "include", "nabo_knn.h"), os.path.join(csrc, "comm.h"),
+                   os.path.join(csrc, "launch.h"), os.path.join(csrc, "host_common.h")]
     os.makedirs(os.path.dirname(SO), exist_ok=True)
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-x", "c++", "-DNABO_SHARDED_HOST", "-I" + SHIM]
@@ -280,5 +281,95 @@ def test_a_missing_peer_times_out_and_abort_releases_the_waiting_ranks(host):
         assert time.time() - t0 < 20 and res[0][0] == E_COMM and res[2][0] == E_COMM
         assert host.nabo_comm_abort(grp.comms[0]) == 0 and host.nabo_comm_abort(grp.comms[2]) == 0      # idempotent, any thread
         assert host.nabo_comm_transport_ranks(grp.comms[0]) == E_COMM
+    finally:
+        grp.close()
+
+
+def _all_equal_the_oracle(res, oi, od):
+    for rc, msg, gi, gd in res:
+        assert rc == 0, msg
+        assert np.array_equal(gi, oi) and np.array_equal(gd, od)
+
+
+@pytest.mark.parametrize("N,R,metric,k,protocol,code,text", [
+    (3, 3, 0, 5, 7, E_INVALID, "protocol 7"),
+    (4, 2, 0, 5, 2, E_UNSUPPORTED, "2-D shard layout"),
+    (4, 2, 1, 5, 0, E_UNSUPPORTED, "2-D shard layout"),
+    (3, 1, 0, 5, 2, E_UNSUPPORTED, "pure target slicing"),
+    (3, 3, 1, 5, 1, E_UNSUPPORTED, "global certification needs"),
+    (4, 4, 0, 300, 2, E_UNSUPPORTED, "4 x 300 exceeds the merge width"),
+    (4, 4, 1, 300, 0, E_UNSUPPORTED, "4 x 300 exceeds the merge width")])
+def test_a_protocol_the_layout_cannot_run_is_refused_before_any_query(host, N, R, metric, k, protocol, code, text):
+    """Phase 0: the protocol choice and the merge-width checks refuse on every rank with the same code and text, agreed on
+    before any local query runs (no callback), and the same communicators answer a correct call afterwards.  (Modified
+    Canberra in the 2 x 2 layout has no protocol it can run: no follow-up call there.)"""
+    Y, X = _data()
+    grp = Group(host, N, R, Y, metric=metric)
+    try:
+        res = grp.query(X, k, protocol=protocol)
+        assert [r[0] for r in res] == [code] * N
+        assert all(text in r[1] for r in res), res[0][1]
+        assert grp.calls == {"cand": 0, "query": 0}
+        if not (R == 2 and metric == 1):
+            oi, od = oracle.knn(X, Y, 5, metric, nthreads=4)
+            _all_equal_the_oracle(grp.query(X, 5), oi, od)
+    finally:
+        grp.close()
+
+
+@pytest.mark.parametrize("N,R,m", [(4, 2, 2), (3, 3, 1), (4, 1, 3), (4, 2, 5)])
+def test_fewer_target_rows_than_ranks(host, N, R, m):
+    """Groups of the 2-D layout whose slice holds no row at all (no local query, lists of absent entries only) and owners
+    whose rows are all padding: every rank still takes part in every collective and ends with the oracle's rows."""
+    Y, X = _data()
+    X = X[:m]
+    grp = Group(host, N, R, Y)
+    try:
+        oi, od = oracle.knn(X, Y, 4, 0, nthreads=4)
+        _all_equal_the_oracle(grp.query(X, 4), oi, od)
+    finally:
+        grp.close()
+
+
+@pytest.mark.parametrize("N,R,k,protocol,n_cand,n_query", [(3, 3, 9, 2, 0, 3), (3, 3, 9, 0, 3, 0), (3, 1, 9, 0, 0, 3), (4, 2, 8, 1, 4, 0)])
+def test_shards_with_fewer_references_than_k(host, N, R, k, protocol, n_cand, n_query):
+    """20 references: a piece of 6 or 7 (10 in the 2 x 2 layout) holds fewer than k' of them and takes part with absent
+    entries -- local certification through local_topk's widen_kernel, global certification through candidate lists that
+    end early -- and one piece on every rank (R = 1) answers with its certified local query alone."""
+    Y, X = _data()
+    Y, X = Y[:20], X[:37]
+    grp = Group(host, N, R, Y)
+    try:
+        oi, od = oracle.knn(X, Y, k, 0, nthreads=4)
+        _all_equal_the_oracle(grp.query(X, k, protocol=protocol), oi, od)
+        assert grp.calls == {"cand": n_cand, "query": n_query}
+    finally:
+        grp.close()
+
+
+def test_second_round_on_short_shards(host):
+    """The exact re-solve of refused rows on pieces with fewer than k' references (local_topk widens them too)."""
+    Y, X = _data()
+    Y, X = Y[:20], X[:37]
+    grp = Group(host, 3, 3, Y)
+    try:
+        grp.refuse_rows = {0, 13, 36}
+        oi, od = oracle.knn(X, Y, 9, 0, nthreads=4)
+        _all_equal_the_oracle(grp.query(X, 9), oi, od)
+        assert [grp.stats(r)["uncertified"] for r in range(3)] == [3, 3, 3]
+    finally:
+        grp.close()
+
+
+def test_second_round_in_the_2d_layout(host):
+    """Rows refused in both target slices: every rank re-solves all of them on its piece, and an owner merges the parts of
+    ITS group of R = 2 ranks only (they cover every piece)."""
+    Y, X = _data()
+    grp = Group(host, 4, 2, Y)
+    try:
+        grp.refuse_rows = {0, 33, 66, 130}
+        oi, od = oracle.knn(X, Y, 6, 0, nthreads=4)
+        _all_equal_the_oracle(grp.query(X, 6), oi, od)
+        assert [grp.stats(r)["uncertified"] for r in range(4)] == [4, 4, 4, 4]
     finally:
         grp.close()
