@@ -47,6 +47,9 @@ PCA_SYMBOLS = ["nabo_pca_project", "nabo_gene_stats", "nabo_pca_last_device_ms"]
 # every symbol include/nabo_pca_fit.h declares (mean and covariance of the scaled cells: the exact PCA fit)
 PCA_FIT_SYMBOLS = ["nabo_pca_cov", "nabo_pca_cov_last_phase_ms"]
 
+# every symbol include/nabo_qc.h declares (per-cell quality-control sums)
+QC_SYMBOLS = ["nabo_cell_qc", "nabo_qc_last_device_ms"]
+
 
 class NaboError(RuntimeError):
     pass
@@ -122,7 +125,9 @@ def lib():
     L.nabo_pca_last_device_ms.argtypes = [C.POINTER(dbl), C.POINTER(i64)]
     L.nabo_pca_cov.argtypes = [i32, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, i64, vp, vp]
     L.nabo_pca_cov_last_phase_ms.argtypes = [C.POINTER(dbl)]
-    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS:
+    L.nabo_cell_qc.argtypes = [i32, i64, i64, vp, vp, vp, i32, vp, i64, vp, i64, vp, vp]
+    L.nabo_qc_last_device_ms.argtypes = [C.POINTER(dbl), C.POINTER(i64)]
+    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS:
         if name not in ("nabo_version", "nabo_last_error"):
             getattr(L, name).restype = C.c_int
     _lib = L

@@ -182,6 +182,11 @@ int pca_check_selection(int64_t n_raw_genes, const int32_t *gene_pos, int64_t G,
                         const int64_t *rows);
 void pca_set_device_ms(const double ms[3], int64_t n_chunks);
 
+// per-cell quality-control sums: one streaming pass over the cells (cell_qc.hip); table: the class bytes, padded with
+// zeros to a multiple of 16
+hipError_t cell_qc_launch(const int64_t *ptr, const int32_t *gene, const float *val, int64_t n_rows, const uint8_t *table,
+                          int64_t n_raw_genes, int n_classes, int64_t *out_n, double *out_sums, hipStream_t st);
+
 // device time of the last classification / set-levels call, read by nabo_cluster_last_device_ms (classify.hip)
 void cluster_set_device_ms(int which, double ms);
 
