@@ -263,6 +263,7 @@ hipError_t de_rank_launch(const uint64_t *keys, const int64_t *seg, int64_t n_se
 #include <vector>
 
 #include "../../include/nabo_de.h"
+#include "de_exact.h"
 #include "host_common.h"
 
 namespace {
@@ -283,35 +284,6 @@ struct Csc {
     const int32_t *cell;
     const float *val, *sf;
 };
-
-// 2 * P(U >= u_max) for samples of m and n values without ties, clipped to 1: the number of ways U takes the value k is
-// the coefficient of q^k in the Gaussian binomial C(m + n, m)_q = prod_{i=1..m} (1 - q^(n+i)) / (1 - q^i).  Unsigned
-// 128-bit arithmetic wraps, and a ring keeps the final coefficients exact as long as they are below 2^128 themselves.
-int exact_pvalue(int64_t n1, int64_t n2, int64_t u2, double *p)
-{
-    const int64_t m = n1 < n2 ? n1 : n2, n = n1 < n2 ? n2 : n1;      // the distribution is symmetric in (m, n)
-    unsigned __int128 total = 1;
-    for (int64_t i = 1; i <= m; ++i) {
-        // C(n + i, i) = C(n + i - 1, i - 1) * (n + i) / i, exact at every step
-        if (total > (((unsigned __int128)1 << 127) / (unsigned __int128)(n + i)))
-            return nabo::api_fail(NABO_E_UNSUPPORTED, "exact Mann-Whitney p for samples of %lld and %lld values without ties: "
-                                  "C(n1 + n2, n1) does not fit 127 bits", (long long)n1, (long long)n2);
-        total = total * (unsigned __int128)(n + i) / (unsigned __int128)i;
-    }
-    const int64_t mn = m * n, um2 = u2 > 2 * mn - u2 ? u2 : 2 * mn - u2;
-    const int64_t K = mn - um2 / 2;                                  // without ties U is an integer
-    std::vector<unsigned __int128> f((size_t)K + 1, 0);
-    f[0] = 1;
-    for (int64_t i = 1; i <= m; ++i) {
-        for (int64_t k = K; k >= n + i; --k) f[k] -= f[k - n - i];
-        for (int64_t k = i; k <= K; ++k) f[k] += f[k - i];
-    }
-    unsigned __int128 cum = 0;
-    for (int64_t k = 0; k <= K; ++k) cum += f[k];
-    const double v = 2.0 * ((double)cum / (double)total);
-    *p = v > 1.0 ? 1.0 : v;
-    return NABO_OK;
-}
 
 int check_csc(const char *which, int64_t n_genes, const Csc &m)
 {
@@ -597,7 +569,7 @@ int nabo_de_test(int32_t device, int64_t n_genes, int64_t n_cells, const int64_t
                 const double p = erfc(out_z[i] * 0.70710678118654752440);
                 out_pval[i] = p > 1.0 ? 1.0 : p;
             } else if (out_status[i] == NABO_DE_EXACT) {
-                if ((rc = exact_pvalue(out_n1[i], out_n2[i], out_u2[i], &out_pval[i]))) return rc;
+                if ((rc = nabo::de_exact_pvalue(out_n1[i], out_n2[i], out_u2[i], &out_pval[i]))) return rc;
             }
         }
     }

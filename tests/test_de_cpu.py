@@ -1,7 +1,11 @@
 """The Mann-Whitney DE test and cluster markers (include/nabo_de.h, nabo_amd/_de.py) without a GPU: the C header and its
 symbols, argument checks, the no-device failure, the tests' plain restatement against the reference's tables
 (tests/golden/de.npz, tools/gen_golden_de.py), and the host logic -- carry-over of an empty group, Benjamini-Hochberg,
-ordering, filtering, marker counting -- with the device step replaced by that restatement."""
+ordering, filtering, marker counting -- with the device step replaced by that restatement.  Then the edge cases of
+tests/_de_edges.py: the restatement against the dense reference (tests/_de_dense_ref.py), and the library's exact p
+(nabo_amd/csrc/de_exact.h, compiled for the host) against Python integers."""
+import ctypes as C
+import math
 import os
 import re
 import subprocess
@@ -12,6 +16,8 @@ import pytest
 import nabo_amd
 from nabo_amd import _de, _lib
 
+import _de_dense_ref as dense
+import _de_edges as edges
 import _de_ref as dref
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -186,3 +192,120 @@ def test_exact_p_of_the_restatement():
             want = min(1.0, 2.0 * sum(c for k, c in counts.items() if k >= max(u, m * n - u)) / total)
             assert abs(dref.exact_p(m, n, 2 * u) - want) < 1e-15, (m, n, u)
             assert abs(dref.exact_p(n, m, 2 * u) - want) < 1e-15
+
+
+# ---- the edge cases: restatement against the dense reference ----------------------------------------------------------
+def references(name, _cache={}):
+    """(dense reference, restatement's arrays) of an edge case, computed once"""
+    if name not in _cache:
+        a = edges.args(edges.case(name))
+        _cache[name] = (dense.dense_step(*a), dref.de_step(*a))
+    return _cache[name]
+
+
+def margins_hold(case, want, tol):
+    """every finite reference log2_fc is farther from the threshold than the tolerance, so a skip cannot flip"""
+    lfc = [w["log2_fc"] for row in want for w in row if w["status"] not in (dref.SKIP_GENE, dref.EMPTY)]
+    lfc = [x for x in lfc if math.isfinite(x)]
+    if case.get("exact_threshold"):
+        return bool(lfc) and all(x == case["log2_fc_thresh"] for x in lfc)
+    return all(abs(x - case["log2_fc_thresh"]) > tol for x in lfc)
+
+
+@pytest.mark.parametrize("name", edges.all_names())
+def test_dense_reference_and_restatement_agree_on_the_edge_cases(golden, name):
+    """two statements of the step written differently: integers and statuses exactly, z within its float64 bound, p and
+    log2_fc within theirs; and the margin that keeps the device's skip decisions unambiguous"""
+    tol, p_rel = tolerances(golden("de"))
+    want, step = references(name)
+    worst = dense.check_against_dense(step, want, tol, p_rel, name)
+    print("%s: largest z error %.3f of its bound" % (name, worst))
+    assert margins_hold(edges.case(name), want, tol), name
+
+
+def test_edge_cases_reach_their_edges():
+    """what each family is there for is really in its cases"""
+    def get(name, k):
+        return [[w.get(k) for w in row] for row in references(name)[0]]
+
+    def st(name):
+        return np.array(get(name, "status"))
+    assert (st("exact_sweep_to_8") == dref.EXACT).all() and (st("exact_large_n1") == dref.EXACT).all()
+    assert 1.0 in get("exact_sweep_to_8", "rbc")[0] and -1.0 in get("exact_sweep_to_8", "rbc")[1]          # U at both ends
+    z = get("runs_all_equal", "z")
+    assert z[0][0] is None and z[1][0] is not None                    # the zero-variance pair
+    assert sorted(np.unique(st("zeros_counted")).tolist()) == [dref.SKIP_GENE, dref.ASYMPTOTIC]
+    assert st("zeros_counted")[16, 0] == dref.ASYMPTOTIC and get("zeros_counted", "nonzero_test")[16][0] == 3
+    assert (st("thresh_frac_on_threshold")[:, 0] == [dref.ASYMPTOTIC, dref.SKIP_GENE, dref.SKIP_GENE, dref.SKIP_GENE, dref.ASYMPTOTIC]).all()
+    assert (st("thresh_all_zero_test_skipped")[2:4, 0] == [dref.SKIP_PAIR, dref.ASYMPTOTIC]).all()
+    assert (st("thresh_frac_above_one") == dref.SKIP_GENE).all()
+    assert (st("thresh_log2_fc_on_threshold") >= dref.ASYMPTOTIC).all()
+    assert dref.EMPTY in st("sets_memberships") and dref.EMPTY in st("two_matrices")
+    t0 = 2 * ((1 << 20) - 8)
+    tie = get("limit_just_below", "tie")[0]
+    assert 2 ** 63 - 2 ** 48 < t0 ** 3 < 2 ** 63 and all(t0 ** 3 - t0 <= t < 2 ** 63 for t in tie)
+    for k in (1, 2, 8, 9, 16, 17):
+        assert any(n.startswith("chunks_nseg_%d_" % k) for n in edges.FAMILIES["chunks"])
+
+
+# ---- the exact p of the library, compiled for the host ----------------------------------------------------------------
+@pytest.fixture(scope="module")
+def exact_lib():
+    shim = os.path.join(REPO, "tests", "host_shim")
+    so = os.path.join(shim, "build", "libnabo_de_exact_host.so")
+    deps = [os.path.join(shim, "de_exact_host.cpp"), os.path.join(REPO, "nabo_amd", "csrc", "de_exact.h"), os.path.join(REPO, "include", "nabo_knn.h")]
+    os.makedirs(os.path.dirname(so), exist_ok=True)
+    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-fPIC", "-shared", deps[0], "-o", so])
+    L = C.CDLL(so)
+    L.nabo_last_error.restype = C.c_char_p
+    L.nabo_host_de_exact_pvalue.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_double)]
+
+    def p_of(n1, n2, u2):
+        p = C.c_double(-1.0)
+        rc = L.nabo_host_de_exact_pvalue(n1, n2, u2, C.byref(p))
+        return rc, p.value, L.nabo_last_error().decode()
+    return p_of
+
+
+def test_exact_p_small_samples_every_u(exact_lib):
+    """every (n1, n2) up to 8 x 8, both orders, every U: Python integers within 4 * 2^-53 (two conversions, one division)"""
+    for n1 in range(1, 9):
+        for n2 in range(1, 9):
+            for u in range(n1 * n2 + 1):
+                rc, p, _ = exact_lib(n1, n2, 2 * u)
+                want = dref.exact_p(n1, n2, 2 * u)
+                assert rc == 0 and abs(p - want) <= dense.P_EXACT_REL * want, (n1, n2, u, p, want)
+    assert exact_lib(8, 8, 64)[1] == 1.0 and exact_lib(3, 2, 0)[1] == 2.0 / 10
+
+
+@pytest.mark.parametrize("n1,n2", [(9, 8), (1000, 8), (174439, 8), (174440, 8), (226220, 8), (300000, 7), (8, 226220), (1 << 21, 1)])
+def test_exact_p_large_samples(exact_lib, n1, n2):
+    """up to the last binomial below 2^127 (C(226228, 8) has 127 bits), at both ends of U and where the 128-bit ring has
+    wrapped on the way (K = 20000 coefficients)"""
+    mn = n1 * n2
+    assert math.comb(n1 + n2, n2) < 2 ** 127
+    for u in (mn, mn - 1, mn - 17, 3, 0, mn - min(mn // 2, 20000)):
+        rc, p, msg = exact_lib(n1, n2, 2 * u)
+        want = dref.exact_p(n1, n2, 2 * u)
+        assert rc == 0 and abs(p - want) <= dense.P_EXACT_REL * want, (n1, n2, u, p, want, msg)
+
+
+def test_exact_p_limit_is_the_header_s(exact_lib):
+    """include/nabo_de.h: NABO_E_UNSUPPORTED when C(n1 + n2, n1) >= 2^127, not before"""
+    hdr = open(os.path.join(REPO, "include", "nabo_de.h")).read()
+    assert "NABO_E_UNSUPPORTED when C(n1 + n2, n1) >= 2^127" in hdr
+    assert math.comb(226220 + 8, 8) < 2 ** 127 <= math.comb(226221 + 8, 8)
+    for n1, n2 in ((226221, 8), (8, 226221), (400000, 8), ((1 << 21) - 9, 8), (3000000, 7)):
+        assert math.comb(n1 + n2, n2) >= 2 ** 127
+        rc, p, msg = exact_lib(n1, n2, 2 * n1 * n2 - 6)
+        assert rc == _lib.E_UNSUPPORTED and "%d and %d" % (n1, n2) in msg and p == -1.0, (n1, n2, rc, msg)
+    rc, p, _ = exact_lib(226220, 8, 2 * 226220 * 8 - 6)                   # the next call works
+    assert rc == 0 and abs(p - dref.exact_p(226220, 8, 2 * 226220 * 8 - 6)) <= dense.P_EXACT_REL * p
+    # the largest 7-sample binomial below the limit and the first beyond it, by bisection
+    lo, hi = 300000, 1 << 21
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if math.comb(mid + 7, 7) < 2 ** 127 else (lo, mid)
+    assert math.comb(lo + 7, 7) < 2 ** 127 <= math.comb(hi + 7, 7)
+    assert exact_lib(lo, 7, 2 * lo * 7)[0] == 0 and exact_lib(hi, 7, 2 * hi * 7)[0] == _lib.E_UNSUPPORTED
