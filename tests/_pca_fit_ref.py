@@ -41,6 +41,23 @@ def mean_cov(Y):
     return mean, cov
 
 
+def exact_mean_cov(Y):
+    """mean_cov for the exact-arithmetic cases at sizes where a Python fsum per entry takes too long, in integers: the
+    values y of n rows (a power of two) are multiples of 1 / K, K = 4 n, and every column sums to 0, so mean = 0 and
+    cov = ((Yi^T Yi) / K^2) / (n - 1) with Yi = K y.  Every partial sum of the product is an integer below 2^53, so the
+    float64 matrix product is exact in any order; the division by K^2 is by a power of two, the last one rounds once."""
+    n = Y.shape[0]
+    K = 4 * n
+    assert n & (n - 1) == 0
+    Yi = np.rint(Y * K)
+    assert np.array_equal(Yi, Y * K) and np.array_equal(Yi / K, Y)
+    assert not Yi.sum(axis=0).any()
+    assert n * float(np.abs(Yi).max()) ** 2 < 2.0 ** 53
+    P = Yi.T @ Yi
+    assert np.abs(P).max() < 2.0 ** 53
+    return np.zeros(Y.shape[1], dtype=np.float64), (P / float(K * K)) / (n - 1)
+
+
 def bounds(Y, mean):
     """(e[G], B[G, G]): |mean - exact| <= e_p = n eps A_p with A_p = sum_r |y[r][p]| / n, and
     |cov[p][q] - exact| <= B = (4 n eps s'_p s'_q + n e_p e_q) / (n - 1), s_p = sqrt(sum_r (y[r][p] - mean[p])^2),

@@ -45,6 +45,34 @@ def cell_qc(cell_ptr, gene, val, gene_class=None, n_classes=0, rows=None, exact=
     return n_ent, sums
 
 
+def cell_qc_many(cell_ptr, gene, val, gene_class=None, n_classes=0):
+    """cell_qc over all cells, for tests with very many short cells: a cell of at most 16 entries has one entry per
+    partial sum, so its sum is the butterfly over its values padded to 16 with +0.0 (0.0 + x first, as ordered_sum adds
+    the row to its zeros), taken for all such cells at once; a longer cell goes through ordered_sum"""
+    cell_ptr, gene = np.asarray(cell_ptr, dtype=np.int64), np.asarray(gene, dtype=np.int64)
+    val = np.asarray(val, dtype=np.float32)
+    n_ent = np.diff(cell_ptr)
+    sums = np.zeros((n_ent.shape[0], 1 + n_classes), dtype=np.float64)
+    short = np.nonzero(n_ent <= GROUP)[0]
+    at = cell_ptr[short][:, None] + _J[None, :]
+    inside = _J[None, :] < n_ent[short][:, None]
+    at = at[inside]                                              # the short cells' entries, cell by cell
+    cls = np.asarray(gene_class, dtype=np.int64)[gene] if n_classes else None
+    for k in range(1 + n_classes):
+        x = val.astype(np.float64)
+        if k > 0:
+            x = np.where(((cls >> (k - 1)) & 1).astype(bool), x, 0.0)     # an entry outside the class adds 0.0
+        pad = np.zeros((short.shape[0], GROUP), dtype=np.float64)
+        pad[inside] = x[at]
+        s = np.zeros_like(pad) + pad
+        for d in (8, 4, 2, 1):
+            s = s + s[:, _J ^ d]
+        sums[short, k] = s[:, 0]
+        for c in np.nonzero(n_ent > GROUP)[0].tolist():
+            sums[c, k] = ordered_sum(x[cell_ptr[c]:cell_ptr[c + 1]])
+    return n_ent.astype(np.int64), sums
+
+
 def step(cell_ptr, gene, val, gene_class, n_classes):
     """cell_qc with the signature of nabo_amd._qc's device step"""
     return cell_qc(cell_ptr, gene, val, gene_class, n_classes)

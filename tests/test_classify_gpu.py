@@ -1,7 +1,8 @@
 """Classification and DE groups on the MI355X (nabo_classify_targets, nabo_refgraph_set_levels, nabo_amd._classify):
 parity with the reference's Graph methods (tests/golden/classify.npz) for every option set of the resident graph, the
 quirk graph, real mapping files in both layouts, a 200k-cell SNN graph built by the product against the tests' plain
-restatement, set levels on awkward graphs against the tests' BFS, and the plain-C consumer."""
+restatement, rows at the boundaries of the kernel's stage, set levels on awkward graphs against the tests' BFS, and the
+plain-C consumer."""
 import json
 import os
 import subprocess
@@ -123,6 +124,78 @@ def test_synthetic_rows(gpu_lib):
     got = nabo_amd.classify_from_edges(rc2, ptr, nbr, w, 0.2, 1, 0.0, n_clusters=3000)
     lab, cnt = cref.classify(rc2, 3000, ptr, nbr, w, 0.2, 1, 0.0)
     assert np.array_equal(got["label"], lab) and np.array_equal(got["counts"], cnt)
+
+
+def _few(rng, n):
+    return rng.integers(0, 12, n).tolist()
+
+
+def _stage_cases():
+    """name -> rows as (length, pool) pairs: the row's neighbours are `length` draws from the first `pool` reference
+    nodes, all distinct when pool is None.  The kernel stages 64 rows at a time in pieces of at most 1 024 edges cut at
+    row boundaries; a single row of more than 1 024 edges is walked in the device scratch."""
+    rng = np.random.default_rng(21)
+    short = lambda lens: [(int(ln), 120) for ln in lens]
+    return {
+        # the last row length staged in LDS and the first that takes the scratch, each between short rows
+        "rows_of_1023_1024_1025": short([5]) + [(1023, None)] + short([0]) + [(1024, None)] + short([3]) + [(1025, None)] + short([2]),
+        # the longest row the ABI accepts, the first loop's repeat search never cut short
+        "row_of_4096_distinct": short([3]) + [(4096, None)] + short([7]),
+        # the same length with every neighbour repeated about twenty times
+        "row_of_4096_from_200_nodes": short([2, 0]) + [(4096, 200)] + short([9]),
+        # two scratch rows in a row: `done` advances by one twice, the empty rows before and after join the next stage
+        "two_long_rows_between_empty_ones": short([4, 0]) + [(1100, 3000), (1300, 3000)] + short([0, 6]),
+        # a whole batch is exactly one stage: one pass, run = 64
+        "64_rows_of_16": [(16, 300)] * 64,
+        # one edge more: the stage is cut after row 62, row 63 is a stage of its own
+        "64_rows_of_16_one_of_17": [(16, 300)] * 40 + [(17, 300)] + [(16, 300)] * 23,
+        # a scratch row in lane 63 of batch 0, in lane 0 of batch 1 and as the last row of a final batch of 3 rows
+        "long_rows_in_lane_0_and_63_and_last": short(_few(rng, 63)) + [(1200, 3000), (1500, 3000)] + short(_few(rng, 63)) + short([4, 0])
+                                               + [(1026, 3000)],
+        # a batch of one lane, a full batch, a full batch and a final batch of one row
+        "n_targets_1": [(30, 120)],
+        "n_targets_64": short(rng.integers(0, 40, 64)),
+        "n_targets_65": short(rng.integers(0, 40, 65)),
+    }
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("wf,md,mw", [(0.5, 2, 0.1), (0.05, 1, 0.1), (0.0, 0, -1.0), (0.5, 2, 5.0)])
+@pytest.mark.parametrize("name", sorted(_stage_cases()))
+def test_rows_at_the_stage_boundaries(gpu_lib, name, wf, md, mw):
+    """every case of _stage_cases (the comments there say which branch of classify_rows_kernel each one is the first to
+    run) with each of the four settings of test_synthetic_rows: labels and counts equal to the restatement, best and total
+    bit for bit.  Two rows of 4 096 edges in all, and a call for each setting: one lane walks such a row with O(len^2)
+    reads, more than a second for the row without repeats."""
+    import nabo_amd
+    rows_of = _stage_cases()[name]
+    rng = np.random.default_rng(len(name) + len(rows_of))
+    n_ref, ncl = 5000, 7
+    rc = rng.integers(-1, ncl, n_ref).astype(np.int32)
+    rows = [rng.permutation(n_ref)[:ln] if pool is None else rng.integers(0, pool, ln) for ln, pool in rows_of]
+    lens = [len(r) for r in rows]
+    ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    nbr = np.concatenate(rows).astype(np.int64)
+    w = rng.choice([0.05, 0.11, 0.25, 0.33, 1.0, 0.1], nbr.shape[0])
+    # what the names promise
+    if name == "64_rows_of_16":
+        assert len(lens) == 64 and ptr[-1] == 1024
+    if name == "64_rows_of_16_one_of_17":
+        assert len(lens) == 64 and ptr[-1] == 1025 and ptr[63] <= 1024
+    if name == "long_rows_in_lane_0_and_63_and_last":
+        assert len(lens) == 131 and min(lens[63], lens[64], lens[130]) > 1024 and max(lens[:63] + lens[65:130]) < 12
+    if name.startswith("row_of_4096"):
+        assert max(lens) == 4096
+        assert len(set(rows[lens.index(4096)].tolist())) == (4096 if "distinct" in name else 200)
+    if name.startswith("n_targets"):
+        assert len(lens) == int(name.split("_")[-1])
+    got = nabo_amd.classify_from_edges(rc, ptr, nbr, w, wf, md, mw, n_clusters=ncl)
+    lab, best, tot, cnt, _ = cref.classify(rc, ncl, ptr, nbr, w, wf, md, mw, details=True)
+    assert np.array_equal(got["label"], lab), np.nonzero(got["label"] != lab)[0][:5]
+    assert _bit_equal(got["best"], best) and _bit_equal(got["total"], tot)
+    assert np.array_equal(got["counts"], cnt) and int(cnt.sum()) == len(lens)
+    if (wf, md, mw) == (0.05, 1, 0.1):
+        assert (lab >= 0).any()
 
 
 def _sets(n, n_sets, rng):

@@ -232,3 +232,17 @@ def test_the_bound_holds_between_two_summation_orders():
     assert not (np.abs(bad - mean_w) <= e).all()
     Yc = Y - mean_w
     assert not (np.abs((Yc[1:].T @ Yc[1:]) / (n - 1) - cov_w) <= B).all()
+
+
+def test_integer_evaluation_of_the_exact_cases_equals_the_restatement():
+    """fref.exact_mean_cov, which the GPU tests use where an fsum per entry takes too long, against fref.mean_cov bit for
+    bit at 130 genes x 64 cells; and it refuses values that are not multiples of 1 / (4 n) or whose columns do not sum to 0"""
+    from test_pca_fit_gpu import exact_case
+    Y = fref.scaled_rows(**exact_case(130, 64))
+    mean_w, cov_w = fref.mean_cov(Y)
+    mean, cov = fref.exact_mean_cov(Y)
+    assert np.array_equal(mean.view(np.int64), mean_w.view(np.int64)) and np.array_equal(cov.view(np.int64), cov_w.view(np.int64))
+    assert np.count_nonzero(cov) > 0.95 * 128 * 128
+    for bad in (Y + np.where(np.arange(64) == 9, 1.0 / 512, 0.0)[:, None], Y + 0.25):
+        with pytest.raises(AssertionError):
+            fref.exact_mean_cov(bad)

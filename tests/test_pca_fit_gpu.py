@@ -1,7 +1,8 @@
 """The exact PCA fit on the MI355X (nabo_pca_cov, nabo_amd.pca_cov_csr / fit_pca_csr / fit_pca): bit-equal to the tests'
-restatement (tests/_pca_fit_ref.py) where every operation is exact, within a derived bound of it elsewhere, within the
-measured deviation of the reference's exact regime (tests/golden/pca_fit.npz), no worse than the reference's truncated
-fit, one sized case, the file-level function with `Mapping` on what it leads to, and the refusals.
+restatement (tests/_pca_fit_ref.py) where every operation is exact -- up to 2 049 genes, where the tile count sets the
+number of splits --, within a derived bound of it elsewhere, within the measured deviation of the reference's exact
+regime (tests/golden/pca_fit.npz), no worse than the reference's truncated fit, one sized case, the file-level function
+with `Mapping` on what it leads to, and the refusals.
 
 The bound against the restatement (exactly rounded sums), eps = 2^-53, n rows:  any order of n terms is within n eps of
 the exact sum relative to the sum of the terms' magnitudes, so |d mean[p]| <= e_p = n eps A_p with A_p = sum|y| / n; for
@@ -76,6 +77,65 @@ def test_exact_arithmetic_cases_are_bit_equal(gpu_lib, G, n):
         assert chunks == 1 if rows_per_chunk is None else (chunks > 4 if n >= 64 else chunks == 2), (budget, chunks)
         assert _same(mean, mean_w), (budget, mean[:5])
         assert _same(cov, cov_w), (budget, np.argwhere(_bits(cov) != _bits(cov_w))[:5].tolist())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("G,n,tiles,splits", [(1281, 256, 66, 16), (1409, 256, 78, 14), (2000, 256, 136, 8), (2049, 64, 153, 7)])
+def test_exact_arithmetic_cases_at_the_workload_gene_counts(gpu_lib, G, n, tiles, splits):
+    """the gene counts of a real selection, where the existing cases stop at 6 tiles: fit_tile_of's sqrt decode for tile
+    numbers up to 152, cov_finish's gather for tile rows up to 16, and the partial tiles' layout [split][tile] with
+    (1281, 256): 66 tiles, the last count with the constant 16 splits; (1409, 256): 78 tiles, 14 splits, the first where
+    the tile count sets them; (2000, 256): 136 tiles and 8 splits, the workload's; (2049, 64): 153 tiles, 7 splits by the
+    rule for the buffers but 4 launched over the 4 stages of 16 rows (one in the chunks of 8 rows).  In one chunk and in
+    forced chunks, whose budget comes from _pca.cov_resident_bytes: its restated split rule is wrong if the chunk count
+    is.  The mean is exactly 0, cov bit-equal to the integer evaluation and symmetric bit for bit."""
+    from nabo_amd import _pca
+    nt = -(-G // 128)
+    assert nt * (nt + 1) // 2 == tiles and min(16, -(-1024 // tiles)) == splits
+    kw = exact_case(G, n)
+    Y = fref.scaled_rows(**kw)
+    mean_w, cov_w = fref.exact_mean_cov(Y)
+    assert not Y[:, 3].any() and not Y[:, 5].any() and not cov_w[3].any() and np.count_nonzero(cov_w) > 0.99 * (G - 2) ** 2
+    resident, row = _pca.cov_resident_bytes(G)
+    assert resident == tiles * 128 * 128 * 8 * (1 + splits) + nt * 128 * 8 * 256
+    per_row = row + 8 * int(np.diff(kw["cell_ptr"]).max())
+    for rows_per_chunk in (None, n // 8):
+        budget = 0 if rows_per_chunk is None else resident + rows_per_chunk * per_row
+        mean, cov = gpu_lib.pca_cov_csr(mem_budget=budget, **kw)
+        chunks = _pca.last_device_ms()[1]
+        assert chunks == 1 if rows_per_chunk is None else chunks > 4, (budget, chunks)
+        assert _same(mean, mean_w), (budget, mean[:5])
+        differ = np.argwhere(_bits(cov) != _bits(cov_w))
+        assert _same(cov, cov_w), (budget, len(differ), differ[:5].tolist(), sorted(set(map(tuple, (differ // 128).tolist())))[:8])
+        assert _same(cov, np.ascontiguousarray(cov.T)), "cov is not symmetric bit for bit"
+
+
+@pytest.mark.gpu
+def test_general_case_of_78_tiles_against_numpy(gpu_lib):
+    """200 listed rows (permuted, repeated) x 1409 genes, the mean far from 0: 78 tiles and 14 splits with values that are
+    not exact, against a float64 numpy evaluation with the bound of the module docstring (numpy's own sums are within it
+    too), in one chunk and in three or more; two runs bit-equal, cov symmetric bit for bit"""
+    from nabo_amd import _pca
+    n, G = 200, 1409
+    kw = general_case(n, G, listed=True, far=True, seed=n + G)
+    Y = fref.scaled_rows(**kw)
+    mean_w = Y.sum(axis=0) / n
+    A = np.abs(Y).sum(axis=0) / n
+    Yc = Y - mean_w
+    cov_w = (Yc.T @ Yc) / (n - 1)
+    e = n * fref.EPS * A
+    s1 = np.sqrt((Yc * Yc).sum(axis=0)) + np.sqrt(n) * e
+    B = (4 * n * fref.EPS * np.outer(s1, s1) + n * np.outer(e, e)) / (n - 1)
+    assert (e > 0).all() and np.abs(mean_w).min() > 10
+    resident, row = _pca.cov_resident_bytes(G)
+    for budget in (0, resident + (n // 5) * (row + 8 * int(np.diff(kw["cell_ptr"]).max()))):
+        mean, cov = gpu_lib.pca_cov_csr(mem_budget=budget, **kw)
+        chunks = _pca.last_device_ms()[1]
+        assert chunks == 1 if budget == 0 else chunks >= 3, chunks
+        mean2, cov2 = gpu_lib.pca_cov_csr(mem_budget=budget, **kw)
+        assert _same(mean, mean2) and _same(cov, cov2), "two runs of the same call differ"
+        assert _same(cov, np.ascontiguousarray(cov.T)), "cov is not symmetric bit for bit"
+        check_against(mean, cov, mean_w, cov_w, e, B, "n %d, G %d, budget %d" % (n, G, budget))
 
 
 def general_case(n_cells, G, listed, far, seed):

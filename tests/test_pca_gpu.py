@@ -1,7 +1,7 @@
 """The PCA projection and the gene statistics on the MI355X (nabo_pca_project, nabo_gene_stats, nabo_amd._pca): through
 the C ABI bit-equal to the tests' plain restatement and within the measured deviation of the reference's vectors
-(tests/golden/pca.npz), in one chunk and in forced chunks; the edges; a 300k-cell case in a process of its own; the
-file-level functions with `Mapping` on what they write; and the plain-C consumer.
+(tests/golden/pca.npz), in one chunk and in forced chunks; the edges; float32 products that underflow; a 300k-cell case
+in a process of its own; the file-level functions with `Mapping` on what they write; and the plain-C consumer.
 
 Bounds of the statistics against the restatement (exactly rounded sums): any summation order of n non-negative terms is
 within (n - 1) 2^-53 of the exact sum, relatively, so m and nzm get n 2^-53; the variance's terms are non-negative too and
@@ -144,6 +144,56 @@ def test_statistics_edges(gpu_lib):
         assert got["m"][0] == got["nzm"][0]
         if n == 1:
             assert (got["variance"] == 0).all()
+
+
+@pytest.mark.gpu
+def test_float32_products_that_underflow(gpu_lib):
+    """"one float32 product" where it leaves the normal range: values of 1e-30f in cells with sf = 1e-10f (cells 3 and 11:
+    the product is a positive subnormal) and with sf = 1e-20f (cells 7 and 13: the product is exactly 0), among ordinary
+    cells.  pca_project_csr is the restatement bit for bit, also with mu = mean = 0, where the bias is 0 and the
+    subnormal products are all a row holds; gene_stats_csc counts the subnormal product as positive and the underflowed
+    one not: gene 0 (cells 3 and 11 only) is valid with ncells 2, gene 1 (cells 7 and 13 only) is not valid, gene 2 is
+    listed by all four and by ordinary cells"""
+    rng = np.random.default_rng(31)
+    n_cells, n_raw, G, C = 40, 50, 30, 5
+    tiny_cells, zero_cells = [3, 11], [7, 13]
+    X = np.where(rng.random((n_cells, n_raw)) < 0.4, 0.75 + 0.75 * rng.poisson(1.0, (n_cells, n_raw)), 0).astype(np.float32)
+    X[:, :2] = 0
+    X[tiny_cells + zero_cells, 2] = 1
+    X[tiny_cells, 0] = 1
+    X[zero_cells, 1] = 1
+    X[rng.random((n_cells, n_raw)) < 0.05] = np.float32(1e-30)         # and a few among the ordinary cells' values
+    X[tiny_cells + zero_cells] = np.where(X[tiny_cells + zero_cells] > 0, np.float32(1e-30), 0)
+    X[:, 0] = np.where(np.isin(np.arange(n_cells), tiny_cells), X[:, 0], 0)
+    X[:, 1] = np.where(np.isin(np.arange(n_cells), zero_cells), X[:, 1], 0)
+    sf = (0.5 + rng.random(n_cells)).astype(np.float32)
+    sf[tiny_cells], sf[zero_cells] = np.float32(1e-10), np.float32(1e-20)
+    P = X * sf[:, None]
+    assert P.dtype == np.float32 and ((P[tiny_cells] > 0) == (X[tiny_cells] > 0)).all() and (P[tiny_cells] < np.finfo(np.float32).tiny).all()
+    assert (X[zero_cells] > 0).sum() > 20 and not P[zero_cells].any() and (X[tiny_cells] > 0).sum() > 20
+    ci, gi = np.nonzero(X)
+    cell_ptr = np.concatenate([[0], np.cumsum(np.bincount(ci, minlength=n_cells))]).astype(np.int64)
+    gene_pos = np.full(n_raw, -1, dtype=np.int32)
+    gene_pos[np.sort(rng.permutation(n_raw - 3)[:G - 3] + 3)] = rng.permutation(G - 3) + 3
+    gene_pos[:3] = [0, 1, 2]
+    kw = dict(cell_ptr=cell_ptr, gene=gi.astype(np.int32), val=X[ci, gi], sf=sf, gene_pos=gene_pos, mu=rng.random(G), sigma=0.5 + rng.random(G),
+              mean=rng.normal(size=G), components=rng.normal(size=(C, G)))
+    Z, want = gpu_lib.pca_project_csr(**kw), pref.project(**kw)
+    assert _same(Z, want), np.argwhere(_bits(Z) != _bits(want))[:5].tolist()
+    kw0 = dict(kw, mu=np.zeros(G), mean=np.zeros(G))
+    Z, want = gpu_lib.pca_project_csr(**kw0), pref.project(**kw0)
+    assert (want[tiny_cells] != 0).all() and (np.abs(want[tiny_cells]) < 1e-36).all() and not want[zero_cells].any()
+    assert _same(Z, want), np.argwhere(_bits(Z) != _bits(want))[:5].tolist()
+    # the same entries by gene
+    gj, cj = np.nonzero(X.T)
+    m = (np.concatenate([[0], np.cumsum(np.bincount(gj, minlength=n_raw))]).astype(np.int64), cj.astype(np.int32), X[cj, gj], sf)
+    for keep_cells in (None, np.array(tiny_cells + zero_cells + [0, 1, 2, 20])):
+        got = gpu_lib.gene_stats_csc(*m, keep_cells=keep_cells)
+        want = pref.gene_stats(*m, keep_cells=keep_cells)
+        kept = np.arange(n_cells) if keep_cells is None else keep_cells
+        assert want["ncells"][:2].tolist() == [2, 0] and want["valid"][:2].tolist() == [1, 0] and 0 < want["m"][0] < 1e-39
+        assert want["ncells"][2] == 2 + (P[np.setdiff1d(kept, tiny_cells + zero_cells), 2] > 0).sum()
+        _check_stats(got, want, len(kept), "underflow, keep %s" % (None if keep_cells is None else len(keep_cells)))
 
 
 @pytest.mark.gpu

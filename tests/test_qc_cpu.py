@@ -126,6 +126,23 @@ def test_restatement_orders_and_float32_trap():
     assert a[0, 0] == 0 and a[1, 0] == float(x[0]) and (np.abs(a - b) <= 1000 * 2.0 ** -53 * b).all()
 
 
+@pytest.mark.parametrize("n_classes", [0, 3, 8])
+def test_restatement_for_many_cells_equals_the_plain_one(n_classes):
+    """qref.cell_qc_many (short cells all at once) against qref.cell_qc bit for bit: cells of 0 .. 17 entries, the
+    lengths of the geometry tests and an empty last cell, with no class, three and eight"""
+    from test_qc_gpu import EDGE_LENGTHS, edge_cells            # (that module imports this one)
+    lengths = EDGE_LENGTHS + list(range(18)) + [16, 1, 16, 0]
+    cell_ptr, gene, val, cls = edge_cells(5000, lengths, seed=50 + n_classes)
+    val[cell_ptr[18]:cell_ptr[19]] = 0                          # a cell of five stored zeros only
+    want = qref.cell_qc(cell_ptr, gene, val, cls if n_classes else None, n_classes)
+    got = qref.cell_qc_many(cell_ptr, gene, val, cls if n_classes else None, n_classes)
+    assert got[0].dtype == np.int64 and np.array_equal(got[0], want[0]) and got[0].tolist() == lengths
+    assert got[1].shape == (len(lengths), 1 + n_classes) and np.array_equal(got[1].view(np.int64), want[1].view(np.int64))
+    assert (got[1][:, 0] > 0).sum() > 25 and got[1][18, 0] == 0 and lengths[18] == 5
+    for k in range(n_classes):                                  # every class holds some of a cell's sum, never all of every cell's
+        assert (got[1][:, 1 + k] > 0).any() and (got[1][:, 1 + k] < got[1][:, 0]).any()
+
+
 @pytest.mark.parametrize("s", ["A", "B"])
 @pytest.mark.parametrize("pre", ["", "_pre"])
 def test_filter_reproduces_the_reference(gold, s, pre):

@@ -1,7 +1,8 @@
 """The per-cell quality-control sums on the MI355X (nabo_cell_qc, nabo_amd._qc): through the C ABI bit-equal to the
 tests' plain restatement, which sums in the header's order (tests/_qc_ref.py), on both golden samples
 (tests/golden/qc.npz) in one chunk and in forced chunks; the edges of the kernel's geometry -- groups of 16 lanes, 32
-cells per workgroup, the class table in LDS and through L2; the argument checks of the C entry point; the file-level
+cells per workgroup, the class table in LDS and through L2; 100 001 cells, where every workgroup walks its tile loop
+several times; subnormal values; the argument checks of the C entry point; the file-level
 functions on files written from the golden; and the plain-C consumer."""
 import json
 import os
@@ -120,6 +121,106 @@ def test_edges_of_the_geometry(gpu_lib, n_raw, n_classes, n_cells):
         assert _qc.last_device_ms()[1] >= 3
     empty = gpu_lib.cell_qc_csr(cell_ptr, gene, val, rows=np.zeros(0, np.int64), **kw)
     assert empty[0].shape == (0,) and empty[1].shape == (0, 1 + n_classes)
+
+
+MANY_CELLS = 100001                     # 3 126 tiles of 32 cells, the last one of a single cell
+
+
+def cu_count():
+    """the number cell_qc.hip's launcher reads: hipDeviceGetAttribute(hipDeviceAttributeMultiprocessorCount, which is 63 in
+    hip_runtime_api.h) of device 0, asked of the HIP runtime the library has loaded into this process (torch brings a
+    runtime of its own, which sees no device once another one is in use)"""
+    import ctypes
+    with open("/proc/self/maps") as f:
+        loaded = sorted(set(ln.split()[-1] for ln in f if "libamdhip64" in ln and "/torch/" not in ln))
+    assert len(loaded) == 1, loaded
+    n = ctypes.c_int(0)
+    assert ctypes.CDLL(loaded[0]).hipDeviceGetAttribute(ctypes.byref(n), 63, 0) == 0
+    assert 8 <= n.value <= 4096, n.value
+    return n.value
+
+
+def many_cells(n_raw, long_at, seed):
+    """MANY_CELLS cells over n_raw genes: 0 .. 5 entries each (strictly increasing genes from the lower five eighths of
+    the table), every 307th cell 17 .. 200 entries drawn from all genes with gene 0 and gene n_raw - 1 among them, cell
+    `long_at` 3 000 entries (n_raw when there are fewer genes), the last cell empty; values with fractions and stored
+    zeros as in edge_cells; a random class byte per gene"""
+    rng = np.random.default_rng(seed)
+    n = MANY_CELLS
+    lens = rng.integers(0, 6, n)
+    long_cells = np.arange(150, n - 1, 307)
+    lens[long_cells] = rng.integers(17, 201, long_cells.shape[0])
+    lens[long_at] = min(3000, n_raw)
+    lens[n - 1] = 0
+    cell_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    gene = np.zeros(int(cell_ptr[-1]), dtype=np.int32)
+    few = np.nonzero(lens <= 5)[0]
+    g5 = np.cumsum(rng.integers(1, n_raw // 8 + 1, (few.shape[0], 5)), axis=1) - 1       # at most 5 (n_raw // 8) - 1
+    inside = np.arange(5)[None, :] < lens[few][:, None]
+    gene[(cell_ptr[few][:, None] + np.arange(5)[None, :])[inside]] = g5[inside]
+    for c in np.nonzero(lens > 5)[0].tolist():
+        g = np.sort(rng.permutation(n_raw)[:lens[c]])
+        g[0], g[-1] = 0, n_raw - 1
+        gene[cell_ptr[c]:cell_ptr[c + 1]] = g
+    val = (rng.poisson(1.5, gene.shape[0]) * rng.random(gene.shape[0])).astype(np.float32)
+    return cell_ptr, gene, val, rng.integers(0, 256, n_raw).astype(np.uint8)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_classes,n_raw", [(0, 5000), (3, 5000), (2, 65537), (8, 65536), (5, 70000), (7, 600)])
+def test_more_tiles_than_workgroups(gpu_lib, n_classes, n_raw):
+    """100 001 cells: every workgroup walks its tile loop several times, and not all the same number of times.
+    (0, 5000): the kernel without classes; (3, 5000): <3, true>, the table in LDS; (2, 65537): <3, false>, the table
+    through L2; (8, 65536): <8, true> with the 64 KiB table, two workgroups per CU and the attribute call, so twice the
+    trips; (5, 70000): <8, false> and (7, 600): <8, true>, both with fewer output columns than the nine accumulators
+    (the store guard and the bit mask below 8).  The 3 000-entry cell sits in a tile of the second trip.  Bit-equal to
+    the header's order (n_entries too), two runs alike, and alike in three or more chunks."""
+    from nabo_amd import _qc
+    cus = cu_count()
+    n_tiles = -(-MANY_CELLS // 32)
+    assert n_tiles > 2 * 4 * cus, "a device of %d CUs walks %d tiles in two trips or fewer: this test needs more cells" % (cus, n_tiles)
+    # cell_qc.hip's grid: CUs x min(4, 160 KiB / the table's bytes in LDS) workgroups
+    table = -(-n_raw // 16) * 16 if 0 < n_classes and n_raw <= _qc.LDS_TABLE_GENES else 0
+    grid = cus * (min(4, 160 * 1024 // table) if table else 4)
+    print("%d CUs, %d workgroups, %d tiles: %d or %d trips per workgroup" % (cus, grid, n_tiles, n_tiles // grid, -(-n_tiles // grid)))
+    assert n_tiles // grid >= 2 and n_tiles % grid != 0        # every workgroup loops, and not all equally often
+    long_at = (grid + 5) * 32 + 9
+    cell_ptr, gene, val, cls = many_cells(n_raw, long_at, seed=n_raw + n_classes)
+    lens = np.diff(cell_ptr)
+    assert lens[long_at] == min(3000, n_raw) and lens[-1] == 0 and gene.min() == 0 and gene.max() == n_raw - 1
+    assert ((lens > 16) & (lens <= 200)).sum() > 300 and (lens <= 5).sum() > 99000
+    want = qref.cell_qc_many(cell_ptr, gene, val, cls, n_classes)
+    assert np.array_equal(want[0], lens)
+    kw = dict(gene_class=cls, n_classes=n_classes)
+    got = gpu_lib.cell_qc_csr(cell_ptr, gene, val, **kw)
+    assert _qc.last_device_ms()[1] == 1
+    differ = np.nonzero((_bits(got[1]) != _bits(want[1])).any(axis=1) | (got[0] != want[0]))[0]
+    assert got[1].shape == (MANY_CELLS, 1 + n_classes) and _same(got, want), (differ[:8].tolist(), (differ[:8] // 32).tolist())
+    assert _same(gpu_lib.cell_qc_csr(cell_ptr, gene, val, **kw), got)
+    budget = int(8 * gene.shape[0] + (16 + 8 * (1 + n_classes)) * MANY_CELLS) // 3
+    chunked = gpu_lib.cell_qc_csr(cell_ptr, gene, val, mem_budget=budget, **kw)
+    assert _qc.last_device_ms()[1] >= 3 and _same(chunked, got)
+
+
+@pytest.mark.gpu
+def test_subnormal_values_are_summed_not_flushed(gpu_lib):
+    """float32 values below 2^-126 (1e-40, the smallest subnormal, some around ordinary values): the float64 sums are
+    the restatement's bit for bit, so the conversion to float64 keeps them"""
+    tiny = np.float32(1e-40)
+    assert 0 < tiny < np.finfo(np.float32).tiny
+    rng = np.random.default_rng(11)
+    lengths = [3, 16, 17, 70, 0, 5]
+    cell_ptr, gene, val, cls = edge_cells(300, lengths, seed=12)
+    val[:] = (tiny * rng.integers(1, 100, val.shape[0])).astype(np.float32)
+    val[cell_ptr[1]] = np.float32(1.401298464324817e-45)         # the smallest subnormal
+    val[cell_ptr[3]:cell_ptr[4]:3] = np.float32(0.375)           # cell 3: ordinary values among them
+    val[cell_ptr[5]:cell_ptr[6]] = [1e-38, 1e-39, 0.0, 2e-45, 1.17549435e-38]
+    assert ((val > 0) & (val < np.finfo(np.float32).tiny)).sum() > 80
+    for n_classes in (0, 3, 8):
+        want = qref.cell_qc(cell_ptr, gene, val, cls if n_classes else None, n_classes)
+        got = gpu_lib.cell_qc_csr(cell_ptr, gene, val, gene_class=cls, n_classes=n_classes)
+        assert _same(got, want), n_classes
+        assert (want[1][[0, 1, 2, 5], 0] > 0).all() and (want[1][[0, 1, 2], 0] < 1e-34).all()
 
 
 @pytest.mark.gpu
