@@ -50,6 +50,11 @@ PCA_FIT_SYMBOLS = ["nabo_pca_cov", "nabo_pca_cov_last_phase_ms"]
 # every symbol include/nabo_qc.h declares (per-cell quality-control sums)
 QC_SYMBOLS = ["nabo_cell_qc", "nabo_qc_last_device_ms"]
 
+# every symbol include/nabo_layout.h declares (ForceAtlas2 layout of the reference graph, exact repulsion)
+LAYOUT_SYMBOLS = ["nabo_layout_create", "nabo_layout_destroy", "nabo_layout_set_params", "nabo_layout_set_state",
+                  "nabo_layout_get_state", "nabo_layout_run", "nabo_layout_last_forces", "nabo_layout_last_ms",
+                  "nabo_layout_geometry"]
+
 
 class NaboError(RuntimeError):
     pass
@@ -127,8 +132,17 @@ def lib():
     L.nabo_pca_cov_last_phase_ms.argtypes = [C.POINTER(dbl)]
     L.nabo_cell_qc.argtypes = [i32, i64, i64, vp, vp, vp, i32, vp, i64, vp, i64, vp, vp]
     L.nabo_qc_last_device_ms.argtypes = [C.POINTER(dbl), C.POINTER(i64)]
-    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS:
-        if name not in ("nabo_version", "nabo_last_error"):
+    L.nabo_layout_create.argtypes = [C.POINTER(vp), i32, i64, vp, vp, vp]
+    L.nabo_layout_destroy.argtypes = [vp]
+    L.nabo_layout_set_params.argtypes = [vp, i32, dbl, dbl, dbl, i32, dbl, dbl]
+    L.nabo_layout_set_state.argtypes = [vp, vp, vp, vp, vp, dbl, dbl]
+    L.nabo_layout_get_state.argtypes = [vp, vp, vp, vp, vp, C.POINTER(dbl), C.POINTER(dbl)]
+    L.nabo_layout_run.argtypes = [vp, i64, C.POINTER(i64)]
+    L.nabo_layout_last_forces.argtypes = [vp, vp, vp, vp, C.POINTER(dbl)]
+    L.nabo_layout_last_ms.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
+    L.nabo_layout_geometry.argtypes = [i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS:
+        if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy"):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L

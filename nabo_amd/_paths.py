@@ -242,7 +242,7 @@ class RefGraph:
     def __init__(self, mapping_h5_fn, ref_name, device=0, options=None):
         import h5py
         from ._mapping import read_graph_csr
-        self.fn, self.ref_name = mapping_h5_fn, ref_name
+        self.fn, self.ref_name, self.device, self.layout = mapping_h5_fn, ref_name, device, None
         with h5py.File(mapping_h5_fn, "r") as h5:
             self.names, self.pos, ref_uid = _open_ref(h5, ref_name)
             rows, ptr, nbr, _ = read_graph_csr(h5[ref_uid + "_graph"], self.pos)
@@ -323,6 +323,15 @@ class RefGraph:
         The reference returns each ring in set order; here a ring is sorted by reference position."""
         from ._classify import _k_path_neighbours
         return _k_path_neighbours(self, nodes, k_dist, full_trail, trail_start)
+
+    def set_ref_layout(self, niter=500, init_pos=None, seed=0, disable_rescaling=False, verbose=True, **params):
+        """Graph.set_ref_layout (nabo/_graph.py:179-237): {reference node: (x, y)}, the ForceAtlas2 layout of the
+        reference graph with the repulsion summed over every pair; `params` and everything else as in
+        nabo_amd.set_ref_layout, which this calls on the object's file and device (the weighted graph is read again
+        through read_graph_csr: the resident graph keeps no weights).  The result is also kept as `self.layout`."""
+        from ._layout import _set_ref_layout
+        self.layout = _set_ref_layout(self.fn, self.ref_name, niter, init_pos, seed, disable_rescaling, verbose, self.device, params)
+        return self.layout
 
     def set_de_groups(self, target, min_score, node_dist, from_clusters=None, full_trail=False, trail_start=1,
                       stringent_control=False, clusters=None):

@@ -190,4 +190,29 @@ hipError_t cell_qc_launch(const int64_t *ptr, const int32_t *gene, const float *
 // device time of the last classification / set-levels call, read by nabo_cluster_last_device_ms (classify.hip)
 void cluster_set_device_ms(int which, double ms);
 
+// ForceAtlas2 layout, one iteration = these five in this order (layout.hip; include/nabo_layout.h has the definition).
+// LayoutScalars lives on the device: the speed kernel's single thread writes it, every later kernel reads it, and once
+// `stop` is set (S == 0 or T == 0) every kernel but pack returns at once.
+struct LayoutScalars {
+    double speed, eff, S, T;
+    long long done;   // iterations that moved the nodes
+    int stop, pad_;
+};
+struct LayoutParams {
+    double scaling_ratio, gravity, comp;   // comp: mean(mass) with outbound attraction distribution, else 1
+    int oad, strong;
+};
+int layout_iblock();   // nodes i per workgroup of the repulsion kernel; pk holds a multiple of it
+int layout_jtile();    // nodes j per staged tile
+hipError_t layout_pack_launch(const double *x, const double *y, const double *mass, int64_t n, int64_t npad, void *pk, hipStream_t st);
+// part: [n_splits][2][n] (nabo_layout_geometry gives n_splits)
+hipError_t layout_repulse_launch(const void *pk, int64_t n, double *part, const LayoutScalars *sc, hipStream_t st);
+hipError_t layout_node_launch(int64_t n, const double *x, const double *y, const double *mass, double *dx, double *dy,
+                              const int64_t *ptr, const int32_t *nbr, const double *ew, const double *part, const LayoutParams &P,
+                              double *f_rep, double *f_grav, double *f_attr, double *swing, double *block_st,
+                              const LayoutScalars *sc, hipStream_t st);
+hipError_t layout_speed_launch(int64_t n, const double *block_st, double jitter_tolerance, LayoutScalars *sc, hipStream_t st);
+hipError_t layout_move_launch(int64_t n, double *x, double *y, const double *dx, const double *dy, const double *swing,
+                              LayoutScalars *sc, hipStream_t st);
+
 }  // namespace nabo
