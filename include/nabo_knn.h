@@ -97,7 +97,10 @@ int nabo_index_destroy(nabo_index *ix);
  * workgroups), "pieces" (accepted, no effect: the launch cut into equal chunks was removed), "l2c_geo" (0 = A, 1 = B,
  * 2 = C), "l2_r1", "split_refs_max", "cosine_centre" (takes effect at the next set_ref), "coarse_kernel_q" (the one-product
  * operands through the l2q kernel instead of l2c), "order_flags" (locality-ordered streaming, removed: refused with
- * NABO_E_UNSUPPORTED).  Unknown names: NABO_E_INVALID.
+ * NABO_E_UNSUPPORTED), "local_seeds" (tournament seeds of a one-split launch of the one-product pass from each row's own
+ * bucket of the references, the nearest of "local_anchors" reference cells: 0 = off, 1 = where a gain was measured (long one-split launches on the 23-entry lists),
+ * 2 = on every such launch), "local_anchors" (buckets, 0 = 64, at most 256) and "local_cap" (references kept per bucket,
+ * 0 = 16384, at most 32768).  Unknown names: NABO_E_INVALID.
  * The library reads TWO environment variables, once, in nabo_index_create: NABO_L2_MODE = f32 | f16x3 (which Euclidean /
  * cosine filter runs first; default: the one-product pass) and NABO_CANBERRA_MODE = exact | swar | bits; the sharded
  * transport reads NABO_COMM_TIMEOUT_S and NABO_RCCL_LIB. */
@@ -180,8 +183,8 @@ int nabo_index_last_row_pass(const nabo_index *ix, uint8_t *out, int64_t m);
  * (-1: another kernel), [2] target rows per workgroup, [3] / [4] workgroups (x) of the main / tail launch, [5] / [6] their
  * reference splits, [7] kept list entries, [8] emitted list length, [9] reference tiles per split, [10] / [11] tournament
  * tiles and tiles per group (0: no tournament), [12] workgroups resident at once, [13] workgroups launched in all,
- * [14] padded target rows, [15] operand steps of 16 slots, [16] / [17] always 0 (they described the launch cut into
- * pieces, which was removed).  kernel (optional): the kernel's name as nabo_index_last_kernel reports it. */
+ * [14] padded target rows, [15] operand steps of 16 slots, [16] always 0 (it described the launch cut into pieces, which
+ * was removed), [17] buckets of the local tournament seeds when the main launch takes them (option "local_seeds"), else 0.  kernel (optional): the kernel's name as nabo_index_last_kernel reports it. */
 #define NABO_PLAN_FIELDS 18
 int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t k, int32_t drop_first, int32_t n_cand,
                     int32_t n_cu, const char *l2_mode, const char *options, int64_t out[NABO_PLAN_FIELDS], char *kernel,

@@ -37,6 +37,9 @@ struct Options {
     int cosine_centre = 1;     // cosine: centre the unit rows before packing (takes effect at the next set_ref)
     int coarse_kernel_q = 0;   // the one-product operands through the l2q kernel instead of l2c
     int order_flags = 0;       // refused by nabo_index_set_option (locality-ordered streaming was removed)
+    // local tournament seeds (local_seeds.hip): 0 off, 1 where the planner expects a gain (lseed_applies), 2 on every
+    // one-split launch of the one-product pass; anchors (0: 64) and references kept per bucket (0: 16384) pinned for A/B runs
+    int local_seeds = 1, local_anchors = 0, local_cap = 0;
 };
 bool option_set(Options &o, const char *name, int64_t value);
 
@@ -112,6 +115,10 @@ struct L2Plan {
 // entries per lane of the emitted candidate lists (they hold 32 epl entries): 64-entry lists for k' > 24 and the wide retry
 inline int list_epl(const PassCtx &ctx, int kk, bool cand_mode) { return ((kk <= 24 && !ctx.wide_retry) || cand_mode) ? 1 : 2; }
 int plan_l2(const IndexShape &sh, const PassCtx &ctx, int64_t m, int k, int drop, bool cand_mode, L2Plan *P);
+// local tournament seeds (local_seeds.hip): anchors and references kept per bucket of an index of this shape (*C = 0: none),
+// and whether a launch of `rows` target rows over S reference splits takes its seeds from them
+void lseed_params(const IndexShape &sh, int *C, int *cap);
+bool lseed_applies(const IndexShape &sh, const L2Plan &P, int S, int64_t rows);
 
 struct CbPlan {
     int64_t gx_exact = 0;            // exact kernel: workgroups (64 rows each) and reference splits
@@ -159,6 +166,13 @@ struct nabo_index {
             double fscale = 1.0;           // power-of-two input scale of the fp32 path: max |y~| * fscale in (1/2, 1]
             nabo::DevBuf centre, ypk, ycpk, ycpk1, normmax;
             bool packed_f32 = false, packed_c16 = false, packed_c1 = false;
+            // local tournament seeds (local_seeds.hip): the buckets' runs live BEHIND the one-product operands in ycpk1, from
+            // tile ref_tiles_alloc on (local_room tiles: one address space for l2c_pre_kernel's tile ranges); anchors and the
+            // unmasked references per bucket; built by ensure_local_seeds for (local_C, local_cap), stale after every repack
+            nabo::DevBuf lanchors, lrefcnt;
+            int64_t local_room = 0;
+            int local_C = 0, local_cap = 0;
+            bool local_built = false;
             double ymax_sqrt = 0.0, ymax_sqrt_c = 0.0;
             // the largest reference norm of the last pack, on its way to the host (ensure_packed / ymax_resolve): pinned word,
             // the event behind its copy, which of the two values it becomes and the scale it was packed with
@@ -188,6 +202,9 @@ struct nabo_index {
         nabo::DevBuf cand_key, cand_key2, cand_mi, cand_mt, cand_mi2, cand_mt2;   // filter keys of the lists; merged lists (merge_lists_kernel)
         nabo::DevBuf xbuf, xnbuf, xpk, xnorm, cand_idx, cand_tau, cand_idx2, cand_tau2, cand_d, fails, failcnt, oidx, odist, nfound;
         nabo::DevBuf xh, cbrow;                   // modified Canberra: 7-bit target operands; target row numbers of the bitmap pass
+        // local tournament seeds: the counting sort's keys, block counts, bucket totals and layout (shared by the reference
+        // build and the queries: one stream); the bucket-ordered target tiles, their row map and the columns' ranges
+        nabo::DevBuf lkey, lblk, ltot, llay, xpre, lmap, lranges;
     } ws;
 
     // ---- the last query's record (the nabo_index_last_* getters) ----
@@ -219,6 +236,7 @@ int index_idle(const nabo_index *ix);
 // set_ref.hip
 int ensure_packed(nabo_index *ix, int want);
 int ymax_resolve(nabo_index *ix);
+int ensure_local_seeds(nabo_index *ix);
 // query.hip
 int query_impl(nabo_index *ix, const PassCtx &ctx, const double *X, int32_t x_on_device, int64_t m, int32_t k, int32_t drop_first,
                int64_t *out_idx, double *out_dist, int32_t out_on_device, bool cand_mode, double *out_bound, PassResult *res);

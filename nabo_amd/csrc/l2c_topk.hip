@@ -496,7 +496,8 @@ template <int KS, int NB, int QM>
 __global__ __launch_bounds__(256) void l2c_pre_kernel(const unsigned char *__restrict__ Xpk, const unsigned char *__restrict__ Ypk,
                                                       int tiles_per_split, int64_t tile_off, int64_t rows, int pre_tiles, int gt,
                                                       int q, int64_t pad_tile, int64_t rows_valid, float *__restrict__ tau_out,
-                                                      const int4 *__restrict__ ranges, int rows_per_col)
+                                                      const int4 *__restrict__ ranges, int rows_per_col,
+                                                      const uint32_t *__restrict__ row_map)
 {
     constexpr int NP = NB / 2;
     constexpr int TB = 2 * KS * 1024;
@@ -507,7 +508,9 @@ __global__ __launch_bounds__(256) void l2c_pre_kernel(const unsigned char *__res
     const int64_t ttile0 = tile_off + ltile0;
     // (wave-uniform: a wave beyond the launch's rows -- the filter's workgroups are whole multiples of a wave's rows -- or
     // with nothing but padding rows)
-    if (ltile0 * 32 >= rows || ttile0 * 32 >= rows_valid) return;
+    // (row_map: the rows are a bucket-ordered copy of the launch's, local_seeds.hip -- position p holds the launch's row
+    // row_map[p], 0xFFFFFFFF a padding position; which rows are valid is the map's business)
+    if (ltile0 * 32 >= rows || (!row_map && ttile0 * 32 >= rows_valid)) return;
     f16x8 xb[NB][KS];
 #pragma unroll
     for (int rb = 0; rb < NB; ++rb) {
@@ -581,20 +584,23 @@ __global__ __launch_bounds__(256) void l2c_pre_kernel(const unsigned char *__res
         v = fmaxf(v, __shfl_xor(v, 16, 64));
         v = fmaxf(v, __shfl_xor(v, 32, 64));
         const int64_t lrow = ltile0 * 32 + rb * 16 + (lane & 15);
-        if (lane < 16 && tile_off * 32 + lrow < rows_valid) tau_out[lrow * S + split] = v;
+        if (row_map) {
+            const uint32_t r = row_map[lrow];
+            if (lane < 16 && r != 0xFFFFFFFFu) tau_out[(int64_t)r * S + split] = v;
+        } else if (lane < 16 && tile_off * 32 + lrow < rows_valid) tau_out[lrow * S + split] = v;
     }
 }
 
 template <int KS, int NB, int QM>
 static hipError_t cpre_launch(const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S, int64_t rows,
                               int64_t tile_off, int pre_tiles, int gt, int q, int64_t pad_tile, hipStream_t st,
-                              int64_t rows_valid, float *tau_out, const int *ranges, int rows_per_col)
+                              int64_t rows_valid, float *tau_out, const int *ranges, int rows_per_col, const uint32_t *row_map)
 {
     const int64_t gx = (rows + 4 * NB * 16 - 1) / (4 * NB * 16);
     if (ranges && (rows_per_col <= 0 || rows_per_col % (NB * 16) != 0)) return hipErrorInvalidValue;
     hipLaunchKernelGGL((l2c_pre_kernel<KS, NB, QM>), dim3((unsigned)gx, (unsigned)S), dim3(256), 0, st, Xpk, Ypk, tiles_per_split,
                        tile_off, rows, pre_tiles, gt, q, pad_tile, rows_valid, tau_out, reinterpret_cast<const int4 *>(ranges),
-                       rows_per_col);
+                       rows_per_col, row_map);
     return hipGetLastError();
 }
 
@@ -621,7 +627,7 @@ void l2c_pre_plan(int kc, int lkeep, int tiles_per_split, int scale_pct, int *pr
 // tau_out [rows][S] (rows local to this launch: row tile_off * 32 of the query is row 0), rows_valid as in l2c_topk_launch
 hipError_t l2c_pre_launch(int kc, int lkeep, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
                           int64_t rows, int64_t tile_off, int pre_tiles, int gt, int64_t pad_tile, hipStream_t st,
-                          int64_t rows_valid, float *tau_out, const int *ranges, int rows_per_col)
+                          int64_t rows_valid, float *tau_out, const int *ranges, int rows_per_col, const uint32_t *row_map)
 {
     const int q = (lkeep + 3) / 4;
     // (ranges: every (column, slot) brings its own tournament length -- l2c_pre_plan's, checked by the planner)
@@ -630,9 +636,9 @@ hipError_t l2c_pre_launch(int kc, int lkeep, const unsigned char *Xpk, const uns
 #define NABO_PRE(KSV)                                                                                                               \
     case 2 * KSV:                                                                                                                   \
         return q <= 8 ? cpre_launch<KSV, (KSV <= 2 ? 8 : 4), 8>(Xpk, Ypk, tiles_per_split, S, rows, tile_off, pre_tiles, gt, q, pad_tile, \
-                                                              st, rows_valid, tau_out, ranges, rows_per_col)                       \
+                                                              st, rows_valid, tau_out, ranges, rows_per_col, row_map)              \
                       : cpre_launch<KSV, 4, 16>(Xpk, Ypk, tiles_per_split, S, rows, tile_off, pre_tiles, gt, q, pad_tile, st,     \
-                                                rows_valid, tau_out, ranges, rows_per_col);
+                                                rows_valid, tau_out, ranges, rows_per_col, row_map);
     switch (kc) {
         NABO_PRE(1) NABO_PRE(2) NABO_PRE(3) NABO_PRE(4)
     default: return hipErrorInvalidValue;

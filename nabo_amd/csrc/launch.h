@@ -65,7 +65,20 @@ hipError_t l2c_topk_launch(int kc, int geo, const unsigned char *Xpk, const unsi
 void l2c_pre_plan(int kc, int lkeep, int tiles_per_split, int scale_pct, int *pre_tiles, int *gt);
 hipError_t l2c_pre_launch(int kc, int lkeep, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
                           int64_t rows, int64_t tile_off, int pre_tiles, int gt, int64_t pad_tile, hipStream_t st,
-                          int64_t rows_valid, float *tau_out, const int *ranges = nullptr, int rows_per_col = 0);
+                          int64_t rows_valid, float *tau_out, const int *ranges = nullptr, int rows_per_col = 0,
+                          const uint32_t *row_map = nullptr);
+// local tournament seeds (local_seeds.hip; the layout rules: local_seeds.h)
+size_t lseed_key_bytes(int64_t ncell);
+size_t lseed_blockcnt_bytes(int64_t ncell, int C);
+size_t lseed_layout_bytes(int C);
+size_t lseed_anchor_bytes(int kc, int C);
+hipError_t lseed_anchors_launch(int kc, const unsigned char *Ypk, int64_t n, int g, int C, void *anchors, hipStream_t st);
+hipError_t lseed_sort_launch(int kc, bool is_ref, const unsigned char *pk, int64_t ncell, int g, const void *anchors, int C,
+                             uint32_t *key, uint32_t *blockcnt, uint32_t *tot, hipStream_t st);
+hipError_t lseed_layout_launch(int C, const uint32_t *ref_cnt, const uint32_t *row_cnt, int cap, int lkeep, int tile0,
+                               const int rest[4], int64_t *lay, int *ranges, int64_t ncol, hipStream_t st);
+hipError_t lseed_move_launch(int kc, const unsigned char *src, int64_t ncell, const uint32_t *key, const uint32_t *blockoff, int C,
+                             const int64_t *lay, int cap, int64_t pad_cell, unsigned char *dst, uint32_t *row_map, hipStream_t st);
 
 // list merges, float64 re-evaluation, exact kernels and row helpers (refine.hip)
 hipError_t merge_lists_launch(const uint32_t *cand_idx, const float *cand_key, const float *cand_tau, int64_t rows, int S, int L,

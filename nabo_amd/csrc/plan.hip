@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "index.h"
+#include "local_seeds.h"
 
 namespace nabo {
 
@@ -29,6 +30,12 @@ static const OptionName OPTION_NAMES[] = {
     {"coarse_kernel_q", &Options::coarse_kernel_q}, {"order_flags", &Options::order_flags},
 };
 
+// The local tournament seeds' options (local_seeds.hip).  A table of their own: tests/test_local_seeds_gpu.py runs them
+// on and off against the oracle, the randomised option sweep draws from OPTION_NAMES above.
+static const OptionName LOCAL_SEED_OPTION_NAMES[] = {
+    {"local_seeds", &Options::local_seeds}, {"local_anchors", &Options::local_anchors}, {"local_cap", &Options::local_cap},
+};
+
 bool option_set(Options &o, const char *name, int64_t value)
 {
     for (const OptionName &e : OPTION_NAMES)
@@ -36,7 +43,42 @@ bool option_set(Options &o, const char *name, int64_t value)
             o.*(e.field) = (int)value;
             return true;
         }
+    for (const OptionName &e : LOCAL_SEED_OPTION_NAMES)
+        if (strcmp(e.name, name) == 0) {
+            o.*(e.field) = (int)value;
+            return true;
+        }
     return false;
+}
+
+void lseed_params(const IndexShape &sh, int *C, int *cap)
+{
+    int c = sh.opt.local_anchors > 0 ? sh.opt.local_anchors : 64;
+    if (c > LSEED_MAX_ANCHORS) c = LSEED_MAX_ANCHORS;
+    int k = sh.opt.local_cap > 0 ? sh.opt.local_cap : 16384;
+    k = (k + 31) / 32 * 32;
+    if (k > LSEED_MAX_CAP) k = LSEED_MAX_CAP;
+    // no one-product operands, switched off, or fewer references than anchors
+    if (!sh.coarse || sh.opt.local_seeds == 0 || sh.n < c) c = 0;
+    // by default only where a launch can take them (lseed_applies): the runs cost C * cap cells of memory
+    if (sh.opt.local_seeds == 1 && sh.n < LSEED_MIN_REFS) c = 0;
+    *C = c;
+    *cap = k;
+}
+
+// Local seeds serve a launch of the first one-product pass with ONE reference split (a seed bounds the lkeep-th smallest
+// score over a split's own references only if the sample lies inside it: every bucket does for S = 1), where the tournament
+// is on at all.  By default from 2^18 references and 2^16 rows on: below that the launch is cut into reference splits
+// anyway, and the sort of the rows (assignment, two gathers) is no longer small against the list updates it saves.
+// And by default in geometry B only (two operand steps, up to 23 kept entries: 1M x 1M, d = 50, k = 15: 95.5 -> 93.8 ms
+// per step): on the 64-entry lists of geometry C the filter kernel itself ran twice as long behind local seeds (cosine
+// 1M x 1M, d = 100, k = 50: 274 -> 522 ms, same rows per pass; not understood), geometry A has not been measured.
+bool lseed_applies(const IndexShape &sh, const L2Plan &P, int S, int64_t rows)
+{
+    int C = 0, cap = 0;
+    lseed_params(sh, &C, &cap);
+    if (C == 0 || !P.on_l2c || S != 1 || rows < 1 || sh.opt.prepass <= 0) return false;
+    return sh.opt.local_seeds >= 2 || (P.geo == 1 && rows >= LSEED_MIN_ROWS);
 }
 
 // Which filter kernels serve an index of this shape, and its reference tiles (IndexShape, index.h)
@@ -369,11 +411,17 @@ int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t
     if (rc) return rc;
     int pt = 0, gt = 0;
     if (P.on_l2c && sh.opt.prepass > 0) l2c_pre_plan(P.kcq, P.lkeep, (int)P.tps, sh.opt.prepass, &pt, &gt);
-    // (out[16], out[17]: the launch cut into pieces, removed -- always 0)
+    // (out[16]: the launch cut into pieces, removed -- always 0)
     const int64_t fields[16] = {P.use_1 ? NABO_PASS_ONE_PRODUCT : NABO_PASS_SECOND, P.geo, P.rows_per_wg, P.gx_main, P.gx_tail, P.S, P.S2,
                                 P.lkeep, P.L, P.tps, pt, gt, (int64_t)n_cu * P.wg_per_cu, P.gx_main * P.S + P.gx_tail * P.S2,
                                 P.rows_pad, P.kcq};
     memcpy(out, fields, sizeof(fields));
+    {   // out[17]: the buckets of the local tournament seeds where the main launch takes them (local_seeds.hip), else 0
+        int lc = 0, lcap = 0;
+        lseed_params(sh, &lc, &lcap);
+        const int64_t rows_main = P.gx_main * P.rows_per_wg < m ? P.gx_main * P.rows_per_wg : m;
+        out[17] = lseed_applies(sh, P, P.S, rows_main) ? lc : 0;
+    }
     if (kernel && kernel_len) snprintf(kernel, kernel_len, "%s", P.kernel);
     return NABO_OK;
 }

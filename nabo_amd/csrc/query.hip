@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "index.h"
+#include "local_seeds.h"
 
 namespace nabo {
 
@@ -100,6 +101,44 @@ struct L2Part {
     int64_t end(int64_t m) const { return row0 + rows < m ? row0 + rows : m; }
 };
 
+// LOCAL tournament seeds of a one-split launch (local_seeds.hip): the launch's rows sorted by bucket -- assignment on the
+// packed operands, counting sort, a bucket-ordered copy of their tiles for the tournament alone -- and ONE tournament launch
+// whose columns each run over their bucket's references; rows of buckets too small for one keep the stream's first tiles
+// (pt, gt: l2c_pre_plan's; pt = 0: no tournament there, those rows start from +inf).  No host wait: counts, layout and
+// ranges stay on the device.
+static int local_seeds(nabo_index *ix, const Query &q, const L2Plan &P, L2Part &p, int pt, int gt)
+{
+    const IndexShape &sh = ix->shape;
+    auto &l2 = ix->ref.l2;
+    auto &ws = ix->ws;
+    hipStream_t st = ix->stream;
+    int rc;
+    const int C = l2.local_C, cap = l2.local_cap, kc = P.kcq;
+    const int64_t nrows = p.end(q.m) - p.row0;
+    const int64_t ncol = lseed_columns(nrows, C), prow = ncol * LSEED_COL_ROWS;
+    const size_t tile_bytes = (size_t)kc * 1024;
+    if ((rc = p.pre->reserve((size_t)p.rows * sizeof(float))) || (rc = ws.lkey.reserve(lseed_key_bytes(nrows))) ||
+        (rc = ws.lblk.reserve(lseed_blockcnt_bytes(nrows, C))) || (rc = ws.ltot.reserve((size_t)C * sizeof(uint32_t))) ||
+        (rc = ws.llay.reserve(lseed_layout_bytes(C))) || (rc = ws.xpre.reserve((size_t)(prow / 32) * tile_bytes)) ||
+        (rc = ws.lmap.reserve((size_t)prow * sizeof(uint32_t))) || (rc = ws.lranges.reserve((size_t)ncol * 4 * sizeof(int))))
+        return rc;
+    const unsigned char *xh = ws.xpk.as<unsigned char>() + (size_t)(p.row0 / 32) * tile_bytes;
+    const int rest[4] = {0, (int)p.tps, pt, pt > 0 ? gt : 0};
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.pre->p), 0x7F800000, (size_t)p.rows, st));      // +inf: rows without a tournament
+    HIP_TRY(hipMemsetAsync(ws.lmap.p, 0xFF, (size_t)prow * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(ws.lranges.p, 0, (size_t)ncol * 4 * sizeof(int), st));
+    HIP_TRY(lseed_sort_launch(kc, false, xh, nrows, sh.g, l2.lanchors.p, C, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(),
+                              ws.ltot.as<uint32_t>(), st));
+    HIP_TRY(lseed_layout_launch(C, l2.lrefcnt.as<uint32_t>(), ws.ltot.as<uint32_t>(), cap, P.lkeep, (int)sh.ref_tiles_alloc, rest,
+                                ws.llay.as<int64_t>(), ws.lranges.as<int>(), ncol, st));
+    HIP_TRY(lseed_move_launch(kc, xh, nrows, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), 0, 0,
+                              ws.xpre.as<unsigned char>(), ws.lmap.as<uint32_t>(), st));
+    HIP_TRY(l2c_pre_launch(kc, P.lkeep, ws.xpre.as<unsigned char>(), l2.ycpk1.as<unsigned char>(), (int)p.tps, 1, prow, 0, 0, 2,
+                           sh.ref_tiles_alloc - 1, st, prow, p.pre->as<float>(), ws.lranges.as<int>(), LSEED_COL_ROWS,
+                           ws.lmap.as<uint32_t>()));
+    return NABO_OK;
+}
+
 // The filter kernels of a pass, main launch then tail: the one-product kernel behind its tournament seeds (l2c_topk.hip),
 // or the f16x3 (l2q_topk.hip) / fp32 (l2_topk.hip) filter.  *beside: ev_main was recorded between the two launches -- the
 // refine of the main launch's rows runs on the second stream beside the tail launch.
@@ -139,6 +178,13 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
         L2Part &p = part[i];
         int pt = 0, gt = 2;
         l2c_pre_plan(P.kcq, P.lkeep, (int)p.tps, pre_pct, &pt, &gt);
+        if (first && p.gx > 0 && lseed_applies(sh, P, p.S, p.end(q.m) - p.row0)) {
+            if ((rc = local_seeds(ix, q, P, p, pt, gt))) return rc;
+            seed[i] = p.pre->as<float>();
+            stride[i] = p.S;
+            if (i == 0 && first) ix->last.pre_tiles_last = pt;
+            continue;
+        }
         if (pt <= 0 || p.gx == 0) continue;
         if ((rc = p.pre->reserve((size_t)p.rows * p.S * sizeof(float)))) return rc;
         HIP_TRY(l2c_pre_launch(P.kcq, P.lkeep, xh, yh, (int)p.tps, p.S, p.rows, p.row0 / 32, pt, gt, pad_tile, st, q.m,
@@ -289,6 +335,11 @@ static int query_l2(nabo_index *ix, const PassCtx &ctx, Query &q)
         snprintf(ix->last.kernel, sizeof(ix->last.kernel), "%s", P.kernel);
     }
     if ((rc = ensure_packed(ix, P.use_1 ? 2 : P.use_h ? 1 : 0))) return rc;
+    // (before anything takes the operands' address: a change of options since the pack moves them)
+    if (ctx.first() && (lseed_applies(sh, P, P.S, P.gx_main * P.rows_per_wg < m ? P.gx_main * P.rows_per_wg : m) ||
+                          (P.gx_tail > 0 && lseed_applies(sh, P, P.S2, m - P.gx_main * P.rows_per_wg))) &&
+        (rc = ensure_local_seeds(ix)))
+        return rc;
     if (q.top) ix->last.row_pass.assign((size_t)m, (uint8_t)(P.use_1 ? NABO_PASS_ONE_PRODUCT : NABO_PASS_SECOND));
     const int64_t rows_main = P.gx_main * P.rows_per_wg;
     L2Part part[2] = {

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "index.h"
+#include "local_seeds.h"
 
 namespace nabo {
 
@@ -38,7 +39,12 @@ int ensure_packed(nabo_index *ix, int want)
     if (e2 < -480) e2 = -480;
     double scale;
     if (want == 2) {
-        if ((rc = l2.ycpk1.reserve((size_t)sh.ref_tiles_alloc * sh.kc1 * 1024 + 128))) return rc;
+        // (behind the stream: the runs of the local tournament seeds, ensure_local_seeds)
+        int lc = 0, lcap = 0;
+        lseed_params(sh, &lc, &lcap);
+        l2.local_room = (int64_t)lc * (lcap / 32);
+        l2.local_built = false;
+        if ((rc = l2.ycpk1.reserve((size_t)(sh.ref_tiles_alloc + l2.local_room) * sh.kc1 * 1024 + 128))) return rc;
         l2.hscale = scale = std::ldexp(1.0, e2 + 12);
         HIP_TRY(pack_cref_launch(l2.dYp, sh.n, sh.g, l2.centre.as<double>(), l2.hscale, sh.kc1,
                                  sh.ref_tiles_alloc, ref.dmask, l2.ycpk1.as<unsigned char>(),
@@ -69,6 +75,44 @@ int ensure_packed(nabo_index *ix, int want)
     if (want == 2) l2.packed_c1 = true;
     else if (want_h) l2.packed_c16 = true;
     else l2.packed_f32 = true;
+    return NABO_OK;
+}
+
+// The runs of the local tournament seeds (local_seeds.hip) for the index's current options: anchors, the references sorted
+// by bucket, the first `cap` unmasked cells of every bucket copied behind the one-product operands.  Enqueued on the
+// stream behind the pack; a query that takes local seeds calls this first (the runs are stale after every repack, and an
+// option may have changed C or the cap since).
+int ensure_local_seeds(nabo_index *ix)
+{
+    const IndexShape &sh = ix->shape;
+    auto &l2 = ix->ref.l2;
+    auto &ws = ix->ws;
+    hipStream_t st = ix->stream;
+    int rc, C = 0, cap = 0;
+    lseed_params(sh, &C, &cap);
+    if (C == 0) return NABO_OK;
+    if (l2.local_built && l2.local_C == C && l2.local_cap == cap && l2.packed_c1) return NABO_OK;
+    if (!l2.packed_c1 || l2.local_room < (int64_t)C * (cap / 32)) {           // (options changed since the pack: room for the runs)
+        l2.packed_c1 = false;
+        if ((rc = ensure_packed(ix, 2))) return rc;
+    }
+    const int64_t nblk_bytes = (int64_t)lseed_blockcnt_bytes(sh.n, C);
+    if ((rc = l2.lanchors.reserve(lseed_anchor_bytes(sh.kc1, C))) || (rc = l2.lrefcnt.reserve((size_t)C * sizeof(uint32_t))) ||
+        (rc = ws.lkey.reserve(lseed_key_bytes(sh.n))) || (rc = ws.lblk.reserve((size_t)nblk_bytes)) ||
+        (rc = ws.llay.reserve(lseed_layout_bytes(C))))
+        return rc;
+    unsigned char *ypk = l2.ycpk1.as<unsigned char>();
+    const int rest[4] = {0, 0, 0, 0};
+    HIP_TRY(lseed_anchors_launch(sh.kc1, ypk, sh.n, sh.g, C, l2.lanchors.p, st));
+    HIP_TRY(lseed_sort_launch(sh.kc1, true, ypk, sh.n, sh.g, l2.lanchors.p, C, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(),
+                              l2.lrefcnt.as<uint32_t>(), st));
+    HIP_TRY(lseed_layout_launch(C, l2.lrefcnt.as<uint32_t>(), nullptr, cap, 1, 0, rest, ws.llay.as<int64_t>(), nullptr, 0, st));
+    // (padding positions: a cell of the stream's last tile, which lies beyond the references -- +inf norm)
+    HIP_TRY(lseed_move_launch(sh.kc1, ypk, sh.n, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), cap,
+                              (sh.ref_tiles_alloc - 1) * 32, ypk + (size_t)sh.ref_tiles_alloc * sh.kc1 * 1024, nullptr, st));
+    l2.local_C = C;
+    l2.local_cap = cap;
+    l2.local_built = true;
     return NABO_OK;
 }
 
