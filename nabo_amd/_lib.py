@@ -55,6 +55,11 @@ LAYOUT_SYMBOLS = ["nabo_layout_create", "nabo_layout_destroy", "nabo_layout_set_
                   "nabo_layout_get_state", "nabo_layout_run", "nabo_layout_last_forces", "nabo_layout_last_ms",
                   "nabo_layout_geometry"]
 
+# every symbol include/nabo_umap.h declares (UMAP embedding: fuzzy k-NN graph, synchronous epochs)
+UMAP_SYMBOLS = ["nabo_umap_create", "nabo_umap_destroy", "nabo_umap_set_params", "nabo_umap_set_knn", "nabo_umap_fit_knn", "nabo_umap_set_graph",
+                "nabo_umap_graph_size", "nabo_umap_get_graph", "nabo_umap_set_embedding", "nabo_umap_get_embedding",
+                "nabo_umap_run", "nabo_umap_rewind", "nabo_umap_last_epoch_counts", "nabo_umap_last_ms", "nabo_umap_geometry"]
+
 
 class NaboError(RuntimeError):
     pass
@@ -141,8 +146,23 @@ def lib():
     L.nabo_layout_last_forces.argtypes = [vp, vp, vp, vp, C.POINTER(dbl)]
     L.nabo_layout_last_ms.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
     L.nabo_layout_geometry.argtypes = [i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS:
-        if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy"):
+    L.nabo_umap_create.argtypes = [C.POINTER(vp), i32, i64, i32]
+    L.nabo_umap_destroy.argtypes = [vp]
+    L.nabo_umap_set_params.argtypes = [vp, i64, i32, dbl, dbl, dbl, C.c_uint64]
+    L.nabo_umap_set_knn.argtypes = [vp, vp, vp, i32]
+    L.nabo_umap_fit_knn.argtypes = [vp, vp, i32, i32, i32, dbl]
+    L.nabo_umap_set_graph.argtypes = [vp, vp, vp, vp]
+    L.nabo_umap_graph_size.argtypes = [vp, C.POINTER(i64), C.POINTER(dbl)]
+    L.nabo_umap_get_graph.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.nabo_umap_set_embedding.argtypes = [vp, vp]
+    L.nabo_umap_get_embedding.argtypes = [vp, vp]
+    L.nabo_umap_run.argtypes = [vp, i64, C.POINTER(i64)]
+    L.nabo_umap_rewind.argtypes = [vp]
+    L.nabo_umap_last_epoch_counts.argtypes = [vp, vp, vp, vp]
+    L.nabo_umap_last_ms.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
+    L.nabo_umap_geometry.argtypes = [C.POINTER(i32)]
+    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS + UMAP_SYMBOLS:
+        if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy", "nabo_umap_destroy"):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L

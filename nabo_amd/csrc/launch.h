@@ -228,4 +228,26 @@ hipError_t layout_speed_launch(int64_t n, const double *block_st, double jitter_
 hipError_t layout_move_launch(int64_t n, double *x, double *y, const double *dx, const double *dy, const double *swing,
                               LayoutScalars *sc, hipStream_t st);
 
+// UMAP embedding (umap.hip; include/nabo_umap.h has the definition).  The graph build is smooth -> graph -> arcs; one
+// epoch is one launch of the epoch kernel, which reads y and writes ynew.
+struct UmapEpoch {
+    double a, b, ca, cr;      // the curve; ca = (-2 a) b, cr = (2 gamma) b
+    double alpha, t;          // this epoch's step length and number
+    uint64_t s_t;             // mix(seed + G (t + 1)): the epoch's part of the negative-sample hash
+};
+int umap_group();             // lanes per node of the epoch kernel
+hipError_t umap_smooth_launch(const double *dist, int64_t n, int k, double target, double *rowsum, double *rho, double *total,
+                              double *sigma, hipStream_t st);
+hipError_t umap_sort_temp_bytes(int64_t n_slots, int64_t n, size_t *bytes);
+// keys_*, w_*: [2 n k] slots; on return keys_b, w_b hold the pruned arcs in CSR order and ptr[n] their number
+hipError_t umap_graph_launch(const int64_t *idx, const double *dist, int64_t n, int k, const double *rho, const double *sigma,
+                             double n_epochs, double *a, uint64_t *keys_a, double *w_a, uint64_t *keys_b, double *w_b, void *temp,
+                             size_t temp_bytes, double *wmax, int64_t *ptr, hipStream_t st);
+// nbr may be NULL (the schedule alone is set back to its first state)
+hipError_t umap_arcs_launch(const uint64_t *keys, const double *w, int64_t n_arcs, const double *wmax, double nsr, int32_t *nbr,
+                            double *eps, double *epn, double *next, double *nneg, hipStream_t st);
+hipError_t umap_epoch_launch(int dims, int64_t n, const int64_t *ptr, const int32_t *nbr, const double *eps, const double *epn,
+                             double *next, double *nneg, const double *y, double *ynew, const UmapEpoch &P, int32_t *n_attr,
+                             int32_t *n_neg, uint64_t *idx_sum, hipStream_t st);
+
 }  // namespace nabo
