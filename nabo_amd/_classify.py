@@ -73,7 +73,7 @@ def _imported_clusters(ref_nodes, clusters):
 def _validate_clusters(cluster_dict):
     nclusts = len(set(cluster_dict.values()))
     if nclusts == 0:
-        raise ValueError('ERROR: Calculate clusters first using "make_clusters" or import clusters using '
+        raise ValueError('ERROR: Calculate clusters first using "make_leiden_clusters" or import clusters using '
                          '"import_clusters"')
     elif nclusts == 1:
         raise ValueError("ERROR: Cannot classify targets when only one cluster is present in the graph")

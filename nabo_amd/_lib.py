@@ -60,6 +60,13 @@ UMAP_SYMBOLS = ["nabo_umap_create", "nabo_umap_destroy", "nabo_umap_set_params",
                 "nabo_umap_graph_size", "nabo_umap_get_graph", "nabo_umap_set_embedding", "nabo_umap_get_embedding",
                 "nabo_umap_run", "nabo_umap_rewind", "nabo_umap_last_epoch_counts", "nabo_umap_last_ms", "nabo_umap_geometry"]
 
+# every symbol include/nabo_community.h declares (communities of the reference graph: seeded synchronous Louvain)
+COMMUNITY_SYMBOLS = ["nabo_community_create", "nabo_community_destroy", "nabo_community_set_params", "nabo_community_run",
+                     "nabo_community_labels", "nabo_community_history", "nabo_community_modularity", "nabo_community_split",
+                     "nabo_community_level_size", "nabo_community_get_level", "nabo_community_set_comm", "nabo_community_get_comm",
+                     "nabo_community_sweep", "nabo_community_aggregate", "nabo_community_rewind", "nabo_community_last_ms",
+                     "nabo_community_geometry"]
+
 
 class NaboError(RuntimeError):
     pass
@@ -161,8 +168,25 @@ def lib():
     L.nabo_umap_last_epoch_counts.argtypes = [vp, vp, vp, vp]
     L.nabo_umap_last_ms.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
     L.nabo_umap_geometry.argtypes = [C.POINTER(i32)]
-    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS + UMAP_SYMBOLS:
-        if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy", "nabo_umap_destroy"):
+    L.nabo_community_create.argtypes = [C.POINTER(vp), i32, i64, vp, vp, vp, dbl]
+    L.nabo_community_destroy.argtypes = [vp]
+    L.nabo_community_set_params.argtypes = [vp, dbl, C.c_uint64, i32, i32, i32]
+    L.nabo_community_run.argtypes = [vp]
+    L.nabo_community_labels.argtypes = [vp, vp, C.POINTER(i32), C.POINTER(dbl)]
+    L.nabo_community_history.argtypes = [vp, C.POINTER(i64), i64, vp, vp]
+    L.nabo_community_modularity.argtypes = [vp, vp, dbl, C.POINTER(dbl)]
+    L.nabo_community_split.argtypes = [vp, vp, i32, vp, C.POINTER(i32)]
+    L.nabo_community_level_size.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.nabo_community_get_level.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.nabo_community_set_comm.argtypes = [vp, vp]
+    L.nabo_community_get_comm.argtypes = [vp, vp]
+    L.nabo_community_sweep.argtypes = [vp, i64, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.nabo_community_aggregate.argtypes = [vp]
+    L.nabo_community_rewind.argtypes = [vp]
+    L.nabo_community_last_ms.argtypes = [vp, C.POINTER(dbl)]
+    L.nabo_community_geometry.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    for name in SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS + UMAP_SYMBOLS + COMMUNITY_SYMBOLS:
+        if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy", "nabo_umap_destroy", "nabo_community_destroy"):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L

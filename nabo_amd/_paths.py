@@ -333,6 +333,21 @@ class RefGraph:
         self.layout = _set_ref_layout(self.fn, self.ref_name, niter, init_pos, seed, disable_rescaling, verbose, self.device, params)
         return self.layout
 
+    def make_leiden_clusters(self, resolution=1.0, random_seed=4466):
+        """Graph.make_leiden_clusters (nabo/_graph.py:266-292): {reference node: str(cluster)}, as
+        nabo_amd.make_leiden_clusters, which this calls on the object's file and device (the weighted graph is read again
+        through read_graph_csr: the resident graph keeps no weights).  The result is also kept as `self.clusters`."""
+        from ._community import make_leiden_clusters
+        self.clusters = make_leiden_clusters(self.fn, self.ref_name, resolution, random_seed, self.device)
+        return self.clusters
+
+    def calc_modularity(self, clusters=None):
+        """Graph.calc_modularity (nabo/_graph.py:415-442) of `clusters`, by default those make_leiden_clusters kept; as
+        nabo_amd.calc_modularity."""
+        from ._community import calc_modularity
+        clusters = getattr(self, "clusters", None) if clusters is None else clusters
+        return calc_modularity(self.fn, self.ref_name, {} if clusters is None else clusters, self.device)
+
     def set_de_groups(self, target, min_score, node_dist, from_clusters=None, full_trail=False, trail_start=1,
                       stringent_control=False, clusters=None):
         """Graph.set_de_groups (nabo/_graph.py:989-1055): 'Test' = reference nodes whose mapping score for `target` is

@@ -55,7 +55,7 @@ def get_mapping_score(mapping_h5_fn, ref_name, target, min_weight=0, min_score=0
       * `remove_suffix=True` returns a LIST of cell names in both the sorted and the dict form -- the
         reference iterates the dict there (:693-694), kept as is;
       * `by_cluster=True` returns {cluster: [scores of its reference nodes]} (:655-671).  The Graph object keeps the
-        clusters as node attributes, set by `make_clusters` (out of scope: SURVEY.md section 2) or `import_clusters`;
+        clusters as node attributes, set by `make_leiden_clusters` (here: nabo_amd.make_leiden_clusters returns the dict) or `import_clusters`;
         here they arrive as `clusters` = the dict `import_clusters` takes ({reference node: cluster}, :334-356: values
         become strings, reference nodes the dict does not name get 'NA').  Without `clusters` no node has one and
         every score lands in 'NA' -- what the reference returns on a fresh Graph (its guard at :603 compares a set

@@ -250,4 +250,38 @@ hipError_t umap_epoch_launch(int dims, int64_t n, const int64_t *ptr, const int3
                              double *next, double *nneg, const double *y, double *ynew, const UmapEpoch &P, int32_t *n_attr,
                              int32_t *n_neg, uint64_t *idx_sum, hipStream_t st);
 
+// Communities of the reference graph (community.hip; include/nabo_community.h has the definition).  One sweep is
+// totsize then sweep, which reads comm and writes comm_new; an aggregation is totsize, renumber, part_sums with keys,
+// coarse_sort, coarse_ptr, coarse_arcs and compose.
+struct CommunitySweep {
+    double gamma, two_m;      // the resolution and 2m as a double
+    uint64_t h2;              // mix(mix(seed + G (L + 1)) + G (s + 1)): the gate's part of (level, sweep)
+};
+int community_huge_blocks();       // dense tables of the global-memory path; scratch holds this many times n entries, zeroed
+hipError_t community_totsize_launch(int64_t n, const int32_t *comm, const int64_t *k, int64_t *tot, int32_t *size, hipStream_t st);
+// counters: {moved, want}, added to; long_rows, ovf [n_long], ovf_count, scratch: unused when n_long == 0
+hipError_t community_sweep_launch(int64_t n, const int64_t *ptr, const int32_t *nbr, const int64_t *a, const int64_t *k, const int32_t *comm,
+                                  const int64_t *tot, const int32_t *size, const CommunitySweep &P, const int32_t *long_rows, int64_t n_long,
+                                  int32_t *ovf, unsigned int *ovf_count, int64_t *scratch, int32_t *comm_new, uint64_t *counters,
+                                  hipStream_t st);
+hipError_t community_renumber_temp_bytes(int64_t n, size_t *bytes);
+// flag[c] = community c is used, newid = its exclusive prefix sum, lab[i] = newid[comm[i]]
+hipError_t community_renumber_launch(int64_t n, const int32_t *size, const int32_t *comm, int32_t *flag, int32_t *newid, int32_t *lab, void *temp,
+                                     size_t temp_bytes, hipStream_t st);
+// d[c] = sum of k, in2[c] = sum of in plus the inner arcs, c = lab[i] in [0, n_next); keys, vals (may be NULL): [A]
+hipError_t community_part_sums_launch(int64_t n, int64_t A, const int32_t *src, const int32_t *nbr, const int64_t *a, const int64_t *k,
+                                      const int64_t *inn, const int32_t *lab, int64_t n_next, int64_t *d, int64_t *in2, uint64_t *keys,
+                                      int64_t *vals, hipStream_t st);
+hipError_t community_coarse_temp_bytes(int64_t A, int64_t n_next, size_t *bytes);
+hipError_t community_coarse_sort_launch(int64_t A, int64_t n_next, const uint64_t *keys_a, const int64_t *vals_a, uint64_t *keys_b,
+                                        int64_t *vals_b, uint64_t *ukeys, int64_t *usums, int64_t *n_unique, void *temp, size_t temp_bytes,
+                                        hipStream_t st);
+// the row pointer [n_next + 1] off the n_unique >= 1 sorted keys (ptr[n_next] = the coarse arcs, A); then src, nbr of these A >= 1
+hipError_t community_coarse_ptr_launch(const uint64_t *ukeys, int64_t n_unique, int64_t n_next, int64_t *ptr, hipStream_t st);
+hipError_t community_coarse_arcs_launch(const uint64_t *ukeys, int64_t A, int32_t *src, int32_t *nbr, hipStream_t st);
+hipError_t community_compose_launch(int64_t n, int32_t *map, const int32_t *lab, hipStream_t st);
+// one round of the component split: hook, then pointer jumping; *changed != 0 if a label fell
+hipError_t community_hook_launch(int64_t n, int64_t A, const int32_t *src, const int32_t *nbr, const int32_t *part, int32_t *lab,
+                                 int32_t *changed, hipStream_t st);
+
 }  // namespace nabo
