@@ -348,6 +348,13 @@ class RefGraph:
         clusters = getattr(self, "clusters", None) if clusters is None else clusters
         return calc_modularity(self.fn, self.ref_name, {} if clusters is None else clusters, self.device)
 
+    def calc_diff_potential(self, r=None, tol=1e-10, max_iter=10000):
+        """Graph.calc_diff_potential (nabo/_graph.py:918-954): {reference node: V}, the population-balance potential
+        pinv(I - A/D) r of the unweighted reference graph, as nabo_amd.calc_diff_potential, which this calls on the
+        object's file and device."""
+        from ._potential import calc_diff_potential
+        return calc_diff_potential(self.fn, self.ref_name, r, tol, max_iter, self.device)
+
     def set_de_groups(self, target, min_score, node_dist, from_clusters=None, full_trail=False, trail_start=1,
                       stringent_control=False, clusters=None):
         """Graph.set_de_groups (nabo/_graph.py:989-1055): 'Test' = reference nodes whose mapping score for `target` is
