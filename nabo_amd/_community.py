@@ -13,7 +13,7 @@ import json
 import numpy as np
 
 from . import _lib
-from ._layout import _check_graph
+from ._graphio import Handle, check_csr as _check_graph, read_ref_graph as _ref_graph_csr
 
 PHASES = ("sweeps", "aggregate", "finish", "run")
 
@@ -75,13 +75,13 @@ def _labels(labels, n):
     return np.ascontiguousarray(lab, dtype=np.int32)
 
 
-class Community:
+class Community(Handle):
     """A graph resident on one device and the state of its clustering (nabo_community_create): the handle the tests and
     tools/bench_community.py step through; `louvain_csr` and `modularity_csr` are the one-call forms."""
+    _destroy = "nabo_community_destroy"
 
     def __init__(self, ptr, nbr, w, resolution=1.0, seed=4466, weight_scale=10000, max_sweeps=128, max_levels=32, split=True,
                  device=0):
-        self._h = None
         self.n, ptr, nbr, w = _check_graph(ptr, nbr, w)
         p = _check_params(resolution, seed, weight_scale, max_sweeps, max_levels)
         _check_weights(w, p[2])
@@ -168,23 +168,6 @@ class Community:
         _lib.check(_lib.lib().nabo_community_last_ms(self._h, ms))
         return dict(zip(PHASES, ms[:4]))
 
-    def close(self):
-        if self._h is not None:
-            _lib.lib().nabo_community_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def louvain_csr(ptr, nbr, w, resolution=1.0, seed=4466, weight_scale=10000, max_sweeps=128, max_levels=32, split=True, device=0):
     """Clusters of the weighted graph a CSR (ptr, nbr, w) describes -- rows in either arc direction; a pair listed more
@@ -204,21 +187,6 @@ def modularity_csr(ptr, nbr, w, labels, resolution=1.0, weight_scale=10000, devi
     labels = _labels(labels, n)
     with Community(ptr, nbr, w, resolution, 0, weight_scale, device=device) as H:
         return H.modularity(labels)
-
-
-def _ref_graph_csr(mapping_h5_fn, ref_name):
-    """(refNodes, node -> id, n_ref, a CSR by node id with the file's weights): the graph as _layout._set_ref_layout reads it"""
-    import h5py
-    from ._mapping import read_graph_csr
-    from ._paths import _open_ref
-    with h5py.File(mapping_h5_fn, "r") as h5:
-        names, pos, ref_uid = _open_ref(h5, ref_name)
-        rows, ptr, nbr, w = read_graph_csr(h5[ref_uid + "_graph"], pos)
-    src = np.repeat(np.array([pos[r] for r in rows], dtype=np.int64), np.diff(ptr))
-    order = np.argsort(src, kind="stable")
-    cptr = np.zeros(len(names) + 1, dtype=np.int64)
-    np.cumsum(np.bincount(src, minlength=len(names)), out=cptr[1:])
-    return list(rows), pos, len(names), cptr, nbr[order], w[order]
 
 
 def _leiden_of_graph(ref_nodes, pos, ptr, nbr, w, resolution, random_seed, device):

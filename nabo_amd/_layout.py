@@ -12,6 +12,7 @@ import json
 import numpy as np
 
 from . import _lib
+from ._graphio import Handle, _f64, check_csr as _check_graph, csr_by_node_id, open_ref
 
 PARAMS = {"outbound_attraction_distribution": True, "edge_weight_influence": 1.0, "jitter_tolerance": 1.0,
           "barnes_hut_optimize": True, "barnes_hut_theta": 1.2, "scaling_ratio": 1.0, "strong_gravity_mode": False,
@@ -24,18 +25,6 @@ def geometry(n=1):
     a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
     _lib.check(_lib.lib().nabo_layout_geometry(int(n), C.byref(a), C.byref(b), C.byref(c)))
     return int(a.value), int(b.value), int(c.value)
-
-
-def _f64(a, name, n=None):
-    try:
-        a = np.ascontiguousarray(a, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("ERROR: %s must be numeric" % name)
-    if a.ndim != 1 or (n is not None and a.shape[0] != n):
-        raise ValueError("ERROR: %s must be 1-D%s" % (name, "" if n is None else " with %d entries" % n))
-    if not np.isfinite(a).all():
-        raise ValueError("ERROR: %s holds a value that is not finite" % name)
-    return a
 
 
 def _check_params(params):
@@ -53,30 +42,12 @@ def _check_params(params):
     return p
 
 
-def _check_graph(ptr, nbr, w):
-    try:
-        ptr, nbr = np.ascontiguousarray(ptr, dtype=np.int64), np.ascontiguousarray(nbr, dtype=np.int64)
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError("ERROR: ptr and nbr must be integers")
-    if ptr.ndim != 1 or nbr.ndim != 1:
-        raise ValueError("ERROR: ptr and nbr must be 1-D")
-    w = _f64(w, "w", nbr.shape[0])
-    n = ptr.shape[0] - 1
-    if n < 1:
-        raise ValueError("ERROR: ptr needs n_nodes + 1 entries and the graph at least one node")
-    if ptr[0] != 0 or (np.diff(ptr) < 0).any() or int(ptr[-1]) != nbr.shape[0]:
-        raise ValueError("ERROR: ptr must start at 0, be monotone and end at len(nbr) = %d" % nbr.shape[0])
-    if nbr.size and (nbr.min() < 0 or nbr.max() >= n):
-        raise ValueError("ERROR: nbr holds an entry that is not a node in [0, %d)" % n)
-    return n, ptr, nbr, w
-
-
-class Layout:
+class Layout(Handle):
     """A graph and its layout state resident on one device (nabo_layout_create): the handle the tests and
     tools/bench_layout.py step through; `layout_fa2` is the one-call form."""
+    _destroy = "nabo_layout_destroy"
 
     def __init__(self, ptr, nbr, w, device=0, **params):
-        self._h = None
         self.n, ptr, nbr, w = _check_graph(ptr, nbr, w)
         p = _check_params(params)
         h = C.c_void_p()
@@ -126,23 +97,6 @@ class Layout:
         out.update(run=ms[5], n_timed=int(nt.value))
         return out
 
-    def close(self):
-        if self._h is not None:
-            _lib.lib().nabo_layout_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def layout_fa2(ptr, nbr, w, pos0, niter=500, device=0, **params):
     """ForceAtlas2 on the weighted graph a CSR (ptr, nbr, w) describes -- rows in either arc direction; a pair listed more
@@ -183,15 +137,11 @@ def _layout_of_graph(ref_nodes, pos, n_ref, rows, ptr, nbr, w, niter, init_pos, 
             p0 = np.array([[float(init_pos[x][0]), float(init_pos[x][1])] for x in ref_nodes], dtype=np.float64)
         except (TypeError, ValueError, IndexError):
             raise ValueError("ERROR: every value of init_pos must be an (x, y) pair of numbers")
-    # node ids are positions in ref_cells; the rows of the file become a CSR by node id (either arc direction will do)
-    src = np.repeat(np.array([pos[r] for r in rows], dtype=np.int64), np.diff(ptr))
-    order = np.argsort(src, kind="stable")
-    cptr = np.zeros(n_ref + 1, dtype=np.int64)
-    np.cumsum(np.bincount(src, minlength=n_ref), out=cptr[1:])
+    cptr, cnbr, cw = csr_by_node_id(rows, pos, n_ref, ptr, nbr, w)
     ids = np.array([pos[x] for x in ref_nodes], dtype=np.int64)
     full = np.zeros((n_ref, 2), dtype=np.float64)
     full[ids] = p0
-    out = layout_fa2(cptr, nbr[order], w[order], full, niter, device, **params)[ids]
+    out = layout_fa2(cptr, cnbr, cw, full, niter, device, **params)[ids]
     if not disable_rescaling:
         out = out - out.min(axis=0)
     return {x: (float(out[i, 0]), float(out[i, 1])) for i, x in enumerate(ref_nodes)}
@@ -200,10 +150,9 @@ def _layout_of_graph(ref_nodes, pos, n_ref, rows, ptr, nbr, w, niter, init_pos, 
 def _set_ref_layout(mapping_h5_fn, ref_name, niter, init_pos, seed, disable_rescaling, verbose, device, params):
     import h5py
     from ._mapping import read_graph_csr
-    from ._paths import _open_ref
     params = _check_params(params)
     with h5py.File(mapping_h5_fn, "r") as h5:
-        names, pos, ref_uid = _open_ref(h5, ref_name)
+        names, pos, ref_uid = open_ref(h5, ref_name)
         rows, ptr, nbr, w = read_graph_csr(h5[ref_uid + "_graph"], pos)
     out = _layout_of_graph(list(rows), pos, len(names), rows, ptr, nbr, w, niter, init_pos, seed, disable_rescaling, device, params)
     if verbose:

@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._graphio import csr_by_node_id, open_ref as _open_ref
 
 
 def _i64(a, name):
@@ -114,15 +115,6 @@ def group_hops(ptr, nbr, grp_ptr, members, pair_hops=False, device=0, options=No
 
 
 # ---- the mapping file ---------------------------------------------------------------------------------------------
-def _open_ref(h5, ref_name):
-    if h5["name_stash/ref_name"][0].decode("UTF-8") != ref_name:
-        raise KeyError("ERROR: The reference is named %s in the mapping file and not %s. Please verify that you are "
-                       "trying to load right reference." % (h5["name_stash/ref_name"][0].decode("UTF-8"), ref_name))
-    cells = [x.decode("UTF-8") for x in h5["ref_cells/ref_cells"][:]]
-    names = [c + "_" + ref_name for c in cells]
-    return names, {n: i for i, n in enumerate(names)}, h5["name_stash/ref_name"][1].decode("UTF-8")
-
-
 def _ref_nodes_in_file_order(h5, ref_uid):
     """Graph.refNodes: the reference's nodes as load_from_h5 meets them (HDF5 name order of its graph group; the
     columnar layout lists them in that order too, see read_graph_csr)"""
@@ -247,15 +239,12 @@ class RefGraph:
             self.names, self.pos, ref_uid = _open_ref(h5, ref_name)
             rows, ptr, nbr, _ = read_graph_csr(h5[ref_uid + "_graph"], self.pos)
         # rows in the group's order -> a CSR by reference position (arc direction does not matter to the device)
-        src = np.repeat(np.array([self.pos[r] for r in rows], dtype=np.int64), np.diff(ptr))
+        cptr, cnbr, _ = csr_by_node_id(rows, self.pos, len(self.names), ptr, nbr)
         self.ref_nodes = list(rows)      # Graph.refNodes: read_graph_csr lists rows in the file's node order (either layout)
         self.selfloop = np.zeros(len(self.names), dtype=bool)
-        self.selfloop[src[src == nbr]] = True
+        self.selfloop[cnbr[cnbr == np.repeat(np.arange(len(self.names)), np.diff(cptr))]] = True
         self.deTestCells, self.deCtrlCells = None, None
-        order = np.argsort(src, kind="stable")
-        cptr = np.zeros(len(self.names) + 1, dtype=np.int64)
-        np.cumsum(np.bincount(src, minlength=len(self.names)), out=cptr[1:])
-        self._g = _DeviceGraph(cptr, nbr[order], device, options)
+        self._g = _DeviceGraph(cptr, cnbr, device, options)
 
     def __enter__(self):
         return self

@@ -13,7 +13,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from ._layout import _f64
+from ._graphio import Handle, _f64, check_csr, read_ref_graph
 
 PHASES = ("prepare", "iterate", "finish", "run")
 STATUS = ("running", "converged", "max_iter", "breakdown")
@@ -29,19 +29,7 @@ def geometry():
 
 
 def _check_graph(ptr, nbr):
-    try:
-        ptr, nbr = np.ascontiguousarray(ptr, dtype=np.int64), np.ascontiguousarray(nbr, dtype=np.int64)
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError("ERROR: ptr and nbr must be integers")
-    if ptr.ndim != 1 or nbr.ndim != 1:
-        raise ValueError("ERROR: ptr and nbr must be 1-D")
-    n = ptr.shape[0] - 1
-    if n < 1:
-        raise ValueError("ERROR: ptr needs n_nodes + 1 entries and the graph at least one node")
-    if ptr[0] != 0 or (np.diff(ptr) < 0).any() or int(ptr[-1]) != nbr.shape[0]:
-        raise ValueError("ERROR: ptr must start at 0, be monotone and end at len(nbr) = %d" % nbr.shape[0])
-    if nbr.size and (nbr.min() < 0 or nbr.max() >= n):
-        raise ValueError("ERROR: nbr holds an entry that is not a node in [0, %d)" % n)
+    n, ptr, nbr = check_csr(ptr, nbr)
     seen = np.zeros(n, dtype=bool)
     seen[nbr] = True
     seen[np.diff(ptr) > 0] = True
@@ -64,12 +52,12 @@ def _check_params(tol, max_iter):
     return tol, int(max_iter)
 
 
-class Potential:
+class Potential(Handle):
     """A graph resident on one device and the state of its solve (nabo_potential_create): the handle the tests and
     tools/bench_potential.py step through; `diff_potential_csr` is the one-call form."""
+    _destroy = "nabo_potential_destroy"
 
     def __init__(self, ptr, nbr, tol=1e-10, max_iter=10000, device=0):
-        self._h = None
         self.n, ptr, nbr = _check_graph(ptr, nbr)
         p = _check_params(tol, max_iter)
         h = C.c_void_p()
@@ -145,23 +133,6 @@ class Potential:
         _lib.check(_lib.lib().nabo_potential_last_ms(self._h, ms))
         return dict(zip(PHASES, ms[:4]))
 
-    def close(self):
-        if self._h is not None:
-            _lib.lib().nabo_potential_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def diff_potential_csr(ptr, nbr, r=None, tol=1e-10, max_iter=10000, device=0):
     """V = pinv(I - D^-1 A) r on the unweighted graph a CSR (ptr, nbr) describes -- rows in either arc direction, a pair
@@ -211,6 +182,5 @@ def calc_diff_potential(mapping_h5_fn, ref_name, r=None, tol=1e-10, max_iter=100
     What differs from the reference: no dense matrix.  The same vector solves one sparse symmetric system per connected
     component, taken by conjugate gradients to `tol` (relative residual) in at most `max_iter` iterations; a run that
     does not converge returns its iterate and issues a RuntimeWarning with the true residual."""
-    from ._community import _ref_graph_csr
-    ref_nodes, pos, _, ptr, nbr, _ = _ref_graph_csr(mapping_h5_fn, ref_name)
+    ref_nodes, pos, _, ptr, nbr, _ = read_ref_graph(mapping_h5_fn, ref_name)
     return _potential_of_graph(ref_nodes, pos, ptr, nbr, r, tol, max_iter, device)

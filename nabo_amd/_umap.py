@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._graphio import Handle
 from ._lib import EUCLIDEAN
 
 KERNEL_MS = ("graph", "knn", "epoch", "run")
@@ -157,13 +158,13 @@ def _check_lists(idx, dist):
     return idx, dist
 
 
-class Umap:
+class Umap(Handle):
     """An embedding resident on one device (nabo_umap_create): the handle the tests and tools/bench_umap.py step
     through; `umap_fit` is the one-call form."""
+    _destroy = "nabo_umap_destroy"
 
     def __init__(self, n, dims=2, device=0, n_epochs=None, negative_sample_rate=5, repulsion_strength=1.0, a=None, b=None,
                  seed=0):
-        self._h = None
         self.n, self.dims = _count(n, "n", 3), _count(dims, "dims", 2)
         if self.dims > 3:
             raise ValueError("ERROR: dims must be 2 or 3")
@@ -275,23 +276,6 @@ class Umap:
         out = dict(zip(KERNEL_MS, ms[:4]))
         out["n_timed"] = int(nt.value)
         return out
-
-    def close(self):
-        if self._h is not None:
-            _lib.lib().nabo_umap_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _cells(X, n=None):

@@ -171,10 +171,8 @@ int nabo_cell_qc(int32_t device, int64_t n_cells, int64_t n_raw_genes, const int
     if (!rows) n_rows = n_cells;
     if (n_rows < 0) return nabo::api_fail(NABO_E_INVALID, "n_rows=%lld is negative", (long long)n_rows);
     if (n_rows > 0 && (!out_n_entries || !out_sums)) return nabo::api_fail(NABO_E_INVALID, "an output array is NULL");
-    if (!cell_ptr) return nabo::api_fail(NABO_E_INVALID, "cell_ptr is NULL");
-    if (cell_ptr[0] != 0) return nabo::api_fail(NABO_E_INVALID, "cell_ptr[0] = %lld, must be 0", (long long)cell_ptr[0]);
-    for (int64_t i = 0; i < n_cells; ++i)
-        if (cell_ptr[i + 1] < cell_ptr[i]) return nabo::api_fail(NABO_E_INVALID, "cell_ptr is not monotone at cell %lld", (long long)i);
+    int rc = nabo::check_csr_ptr("cell_ptr", "cell", n_cells, cell_ptr);
+    if (rc) return rc;
     if (cell_ptr[n_cells] > 0 && (!gene || !val)) return nabo::api_fail(NABO_E_INVALID, "gene or val is NULL");
     for (int64_t i = 0; i < n_cells; ++i) {
         int64_t last = -1;
@@ -222,8 +220,7 @@ int nabo_cell_qc(int32_t device, int64_t n_cells, int64_t n_raw_genes, const int
     }
     g_qc_ms[0] = g_qc_ms[1] = g_qc_ms[2] = 0;
     g_qc_chunks = 0;
-    int rc = nabo::use_device(device);
-    if (rc) return rc;
+    if ((rc = nabo::use_device(device))) return rc;
     if (n_rows == 0) return NABO_OK;
 
     hipStream_t st = nullptr;

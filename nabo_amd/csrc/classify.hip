@@ -232,14 +232,11 @@ int nabo_classify_targets(int32_t device, int64_t n_ref, const int32_t *ref_clus
     if (n_clusters < 1) return nabo::api_fail(NABO_E_INVALID, "n_clusters=%d: at least one cluster is needed", (int)n_clusters);
     if (n_targets < 0 || n_targets >= ((int64_t)1 << 37)) return nabo::api_fail(NABO_E_INVALID, "n_targets=%lld out of range", (long long)n_targets);
     if (n_ref > 0 && !ref_cluster) return nabo::api_fail(NABO_E_INVALID, "ref_cluster is NULL");
-    if (!ptr) return nabo::api_fail(NABO_E_INVALID, "ptr is NULL");
-    if (n_targets > 0 && !out_label) return nabo::api_fail(NABO_E_INVALID, "out_label is NULL");
-    if (ptr[0] != 0) return nabo::api_fail(NABO_E_INVALID, "ptr[0] = %lld, must be 0", (long long)ptr[0]);
+    if (ptr && n_targets > 0 && !out_label) return nabo::api_fail(NABO_E_INVALID, "out_label is NULL");
+    int rc = nabo::check_csr_ptr("ptr", "row", n_targets, ptr);
+    if (rc) return rc;
     int64_t longest = 0;
-    for (int64_t i = 0; i < n_targets; ++i) {
-        if (ptr[i + 1] < ptr[i]) return nabo::api_fail(NABO_E_INVALID, "ptr is not monotone at row %lld", (long long)i);
-        longest = ptr[i + 1] - ptr[i] > longest ? ptr[i + 1] - ptr[i] : longest;
-    }
+    for (int64_t i = 0; i < n_targets; ++i) longest = ptr[i + 1] - ptr[i] > longest ? ptr[i + 1] - ptr[i] : longest;
     if (longest > nabo::classify_max_row())
         return nabo::api_fail(NABO_E_UNSUPPORTED, "a row of %lld edges: at most %d per target node", (long long)longest, nabo::classify_max_row());
     const int64_t E = ptr[n_targets];
@@ -250,8 +247,7 @@ int nabo_classify_targets(int32_t device, int64_t n_ref, const int32_t *ref_clus
     for (int64_t i = 0; i < n_ref; ++i)
         if (ref_cluster[i] < -1 || ref_cluster[i] >= n_clusters)
             return nabo::api_fail(NABO_E_INVALID, "ref_cluster[%lld] = %d is not -1 or a cluster in [0, %d)", (long long)i, (int)ref_cluster[i], (int)n_clusters);
-    int rc = nabo::use_device(device);
-    if (rc) return rc;
+    if ((rc = nabo::use_device(device))) return rc;
 
     const bool scratch = longest > nabo::classify_stage_edges();
     DevBuf d_cl, d_ptr, d_nbr, d_w, d_lab, d_best, d_tot, d_cnt, l_nb, l_wt, l_cl;

@@ -32,6 +32,7 @@
 
 #include "../../include/nabo_community.h"
 #include "host_common.h"
+#include "simple_graph.h"
 
 namespace nabo {
 
@@ -332,18 +333,6 @@ __global__ __launch_bounds__(CM_THREADS) void cm_part_arc_kernel(int64_t A, cons
     }
 }
 
-// ptr[r] = the first key whose row is >= r, r = 0 .. n; the keys of inner arcs carry row n
-__global__ __launch_bounds__(CM_THREADS) void cm_rowptr_kernel(const uint64_t *__restrict__ keys, int64_t n_keys, int64_t n, int64_t *__restrict__ ptr)
-{
-    const int64_t q = (int64_t)blockIdx.x * CM_THREADS + threadIdx.x;
-    if (q >= n_keys) return;
-    const int64_t r = (int64_t)(keys[q] >> 32);
-    const int64_t prev = q == 0 ? -1 : (int64_t)(keys[q - 1] >> 32);
-    for (int64_t x = prev + 1; x <= r; ++x) ptr[x] = q;
-    if (q == n_keys - 1)
-        for (int64_t x = r + 1; x <= n; ++x) ptr[x] = n_keys;
-}
-
 __global__ __launch_bounds__(CM_THREADS) void cm_unpack_kernel(const uint64_t *__restrict__ keys, int64_t A, int32_t *__restrict__ src,
                                                                int32_t *__restrict__ nbr)
 {
@@ -459,18 +448,11 @@ hipError_t community_part_sums_launch(int64_t n, int64_t A, const int32_t *src, 
     return hipGetLastError();
 }
 
-static unsigned cm_key_bits(int64_t n_next)
-{
-    unsigned b = 1;
-    while (b < 32 && ((int64_t)1 << b) <= n_next) ++b;   // rows 0 .. n_next, n_next the row of an inner arc
-    return 32 + b;
-}
-
 hipError_t community_coarse_temp_bytes(int64_t A, int64_t n_next, size_t *bytes)
 {
     size_t s1 = 0, s2 = 0;
     hipError_t e = rocprim::radix_sort_pairs(nullptr, s1, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const int64_t *)nullptr,
-                                             (int64_t *)nullptr, (size_t)A, 0u, cm_key_bits(n_next), (hipStream_t) nullptr);
+                                             (int64_t *)nullptr, (size_t)A, 0u, key_sort_bits(n_next), (hipStream_t) nullptr);
     if (e != hipSuccess) return e;
     e = rocprim::reduce_by_key(nullptr, s2, (const uint64_t *)nullptr, (const int64_t *)nullptr, (size_t)A, (uint64_t *)nullptr,
                                (int64_t *)nullptr, (int64_t *)nullptr, rocprim::plus<int64_t>(), rocprim::equal_to<uint64_t>(),
@@ -483,16 +465,10 @@ hipError_t community_coarse_sort_launch(int64_t A, int64_t n_next, const uint64_
                                         int64_t *vals_b, uint64_t *ukeys, int64_t *usums, int64_t *n_unique, void *temp, size_t temp_bytes,
                                         hipStream_t st)
 {
-    hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, keys_a, keys_b, vals_a, vals_b, (size_t)A, 0u, cm_key_bits(n_next), st);
+    hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, keys_a, keys_b, vals_a, vals_b, (size_t)A, 0u, key_sort_bits(n_next), st);
     if (e != hipSuccess) return e;
     return rocprim::reduce_by_key(temp, temp_bytes, (const uint64_t *)keys_b, (const int64_t *)vals_b, (size_t)A, ukeys, usums, n_unique,
                                   rocprim::plus<int64_t>(), rocprim::equal_to<uint64_t>(), st);
-}
-
-hipError_t community_coarse_ptr_launch(const uint64_t *ukeys, int64_t n_unique, int64_t n_next, int64_t *ptr, hipStream_t st)
-{
-    hipLaunchKernelGGL(cm_rowptr_kernel, dim3(cm_grid(n_unique)), dim3(CM_THREADS), 0, st, ukeys, n_unique, n_next, ptr);
-    return hipGetLastError();
 }
 
 hipError_t community_coarse_arcs_launch(const uint64_t *ukeys, int64_t A, int32_t *src, int32_t *nbr, hipStream_t st)
@@ -577,17 +553,10 @@ struct nabo_community {
 
 namespace {
 
-struct Arc {
-    int64_t a, b, ord;
-    double w;
-};
-
 // the list of long rows of a level and what the huge path needs for them
 int level_long_rows(Level &lv, const std::vector<int64_t> &ptr)
 {
-    std::vector<int32_t> rows;
-    for (int64_t i = 0; i < lv.n; ++i)
-        if (ptr[(size_t)i + 1] - ptr[(size_t)i] > nabo::CM_LONG) rows.push_back((int32_t)i);
+    const std::vector<int32_t> rows = nabo::long_rows(ptr, nabo::CM_LONG);
     lv.n_long = (int64_t)rows.size();
     if (rows.empty()) return NABO_OK;
     HIP_TRY(lv.long_rows.alloc(rows.size() * 4));
@@ -617,69 +586,35 @@ int community_rewind(nabo_community *H)
 
 int community_create(nabo_community *H, int64_t n, const int64_t *ptr, const int64_t *nbr, const double *w, double scale)
 {
-    // the simple graph: a pair keeps its last weight
-    const int64_t E = ptr[n];
-    std::vector<Arc> arcs((size_t)E);
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) arcs[(size_t)e] = Arc{std::min(i, nbr[e]), std::max(i, nbr[e]), e, w[e]};
-    std::sort(arcs.begin(), arcs.end(), [](const Arc &p, const Arc &q) {
-        if (p.a != q.a) return p.a < q.a;
-        if (p.b != q.b) return p.b < q.b;
-        return p.ord < q.ord;
-    });
-    size_t m = 0;
-    for (size_t e = 0; e < arcs.size(); ++e)
-        if (e + 1 == arcs.size() || arcs[e + 1].a != arcs[e].a || arcs[e + 1].b != arcs[e].b) arcs[m++] = arcs[e];
-    arcs.resize(m);
-    // quantise; pairs of weight 0 go
-    std::vector<int64_t> qw(arcs.size());
-    m = 0;
-    for (size_t e = 0; e < arcs.size(); ++e) {
-        const double q = std::rint(arcs[e].w * scale);
+    // the simple graph (simple_graph.h) of the pairs whose weight does not quantise to 0
+    nabo::SimpleGraph g;
+    nabo::simple_pairs(g, n, ptr, nbr, true);
+    std::vector<int64_t> qw(g.pairs.size());
+    for (size_t p = 0; p < qw.size(); ++p) {
+        const double wp = w[g.last[p]], q = std::rint(wp * scale);
         if (!(q <= 2147483648.0))
-            return nabo::api_fail(NABO_E_INVALID, "w[%lld] = %g quantises to %g, above 2^31", (long long)arcs[e].ord, arcs[e].w, q);
-        if (q == 0.0) continue;
-        arcs[m] = arcs[e];
-        qw[m++] = (int64_t)q;
+            return nabo::api_fail(NABO_E_INVALID, "w[%lld] = %g quantises to %g, above 2^31", (long long)g.last[p], wp, q);
+        qw[p] = (int64_t)q;
     }
-    arcs.resize(m);
-    qw.resize(m);
-    std::vector<int64_t> k((size_t)n, 0), inn((size_t)n, 0), rptr((size_t)n + 1, 0);
+    std::vector<int64_t> k((size_t)n, 0), inn((size_t)n, 0);
     u128 two_m = 0;
-    for (size_t e = 0; e < arcs.size(); ++e) {
-        const Arc &p = arcs[e];
-        two_m += 2 * (u128)qw[e];
-        if (p.a == p.b) {
-            k[(size_t)p.a] += 2 * qw[e];
-            inn[(size_t)p.a] = qw[e];
-        } else {
-            k[(size_t)p.a] += qw[e];
-            k[(size_t)p.b] += qw[e];
-            ++rptr[(size_t)p.a + 1];
-            ++rptr[(size_t)p.b + 1];
-        }
-    }
+    nabo::simple_rows(g, n, [&](size_t p) { return qw[p] != 0; }, [&](size_t p, int64_t a, int64_t b) {
+        two_m += 2 * (u128)qw[p];
+        k[(size_t)a] += qw[p];
+        k[(size_t)b] += qw[p];
+        if (a == b) inn[(size_t)a] = qw[p];
+    });
     if (two_m >= ((u128)1 << 53)) return nabo::api_fail(NABO_E_INVALID, "the quantised weights add up to 2m >= 2^53: lower weight_scale");
-    for (int64_t i = 0; i < n; ++i) rptr[(size_t)i + 1] += rptr[(size_t)i];
+    const std::vector<int64_t> &rptr = g.rptr;
+    const std::vector<int32_t> &rnbr = g.rnbr;
     const int64_t A = rptr[(size_t)n];
-    std::vector<int32_t> rnbr((size_t)A), rsrc((size_t)A);
+    std::vector<int32_t> rsrc((size_t)A);
     std::vector<int64_t> ra((size_t)A);
-    std::vector<int64_t> fill(rptr.begin(), rptr.end() - 1);
-    // rows in ascending neighbour: first the lower-numbered partners (pairs sorted by (a, b)), then the higher-numbered
-    for (size_t e = 0; e < arcs.size(); ++e)
-        if (arcs[e].a != arcs[e].b) {
-            const size_t at = (size_t)fill[(size_t)arcs[e].b]++;
-            rnbr[at] = (int32_t)arcs[e].a;
-            ra[at] = qw[e];
-        }
-    for (size_t e = 0; e < arcs.size(); ++e)
-        if (arcs[e].a != arcs[e].b) {
-            const size_t at = (size_t)fill[(size_t)arcs[e].a]++;
-            rnbr[at] = (int32_t)arcs[e].b;
-            ra[at] = qw[e];
-        }
     for (int64_t i = 0; i < n; ++i)
-        for (int64_t e = rptr[(size_t)i]; e < rptr[(size_t)i + 1]; ++e) rsrc[(size_t)e] = (int32_t)i;
+        for (int64_t e = rptr[(size_t)i]; e < rptr[(size_t)i + 1]; ++e) {
+            rsrc[(size_t)e] = (int32_t)i;
+            ra[(size_t)e] = qw[(size_t)g.slot_pair[(size_t)e]];
+        }
     H->n0 = n;
     H->two_m = (int64_t)two_m;
     H->h_k0 = k;
@@ -799,7 +734,7 @@ int community_aggregate(nabo_community *H, u128 *out_in, u128 *out_d2)
         int64_t nu = 0;
         HIP_TRY(hipMemcpy(&nu, H->n_unique.p, 8, hipMemcpyDeviceToHost));
         if (nu < 1 || nu > A) return nabo::api_fail(NABO_E_HIP, "the coarse graph has %lld keys for %lld arcs", (long long)nu, (long long)A);
-        HIP_TRY(nabo::community_coarse_ptr_launch(H->ukeys.as<uint64_t>(), nu, n2, nx->ptr.as<int64_t>(), st));
+        HIP_TRY(nabo::key_rowptr_launch(H->ukeys.as<uint64_t>(), nu, n2, nx->ptr.as<int64_t>(), st));
         HIP_TRY(hipMemcpy(&A2, nx->ptr.as<int64_t>() + n2, 8, hipMemcpyDeviceToHost));
         if (A2 < 0 || A2 > nu) return nabo::api_fail(NABO_E_HIP, "the coarse graph has %lld arcs for %lld keys", (long long)A2, (long long)nu);
     } else
@@ -911,21 +846,6 @@ int community_modularity(nabo_community *H, const int32_t *labels, double gamma,
     return NABO_OK;
 }
 
-struct Timer {
-    nabo_community *H;
-    int start() { HIP_TRY(hipEventRecord(H->ev[0], nullptr)); return NABO_OK; }
-    int stop(int which)
-    {
-        HIP_TRY(hipEventRecord(H->ev[1], nullptr));
-        HIP_TRY(hipEventSynchronize(H->ev[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, H->ev[0], H->ev[1]));
-        H->ms[which] += ms;
-        H->ms[3] += ms;
-        return NABO_OK;
-    }
-};
-
 int community_run(nabo_community *H)
 {
     H->ran = false;
@@ -933,7 +853,7 @@ int community_run(nabo_community *H)
     for (double &m : H->ms) m = 0;
     int rc = community_rewind(H);
     if (rc) return rc;
-    Timer T{H};
+    nabo::PhaseTimer T{H->ev, H->ms, 3};
     const int64_t n = H->n0;
     u128 si = 0, sd = 0;
     for (int64_t i = 0; i < n; ++i) {
@@ -991,27 +911,11 @@ int nabo_community_create(nabo_community **out, int32_t device, int64_t n, const
     if (n < 1) return nabo::api_fail(NABO_E_INVALID, "n=%lld must be at least 1", (long long)n);
     if (n >= ((int64_t)1 << 31)) return nabo::api_fail(NABO_E_UNSUPPORTED, "n=%lld: the clustering takes fewer than 2^31 nodes", (long long)n);
     if (!std::isfinite(weight_scale) || !(weight_scale > 0.0)) return nabo::api_fail(NABO_E_INVALID, "weight_scale must be finite and positive");
-    if (!ptr) return nabo::api_fail(NABO_E_INVALID, "ptr is NULL");
-    if (ptr[0] != 0) return nabo::api_fail(NABO_E_INVALID, "ptr[0] = %lld, must be 0", (long long)ptr[0]);
-    for (int64_t i = 0; i < n; ++i)
-        if (ptr[i + 1] < ptr[i]) return nabo::api_fail(NABO_E_INVALID, "ptr is not monotone at node %lld", (long long)i);
-    if (ptr[n] > 0 && (!nbr || !w)) return nabo::api_fail(NABO_E_INVALID, "nbr or w is NULL");
-    for (int64_t e = 0; e < ptr[n]; ++e) {
-        if (nbr[e] < 0 || nbr[e] >= n)
-            return nabo::api_fail(NABO_E_INVALID, "nbr[%lld] = %lld is not a node in [0, %lld)", (long long)e, (long long)nbr[e], (long long)n);
-        if (!std::isfinite(w[e]) || w[e] < 0.0) return nabo::api_fail(NABO_E_INVALID, "w[%lld] is negative or not finite", (long long)e);
-    }
-    int rc = nabo::use_device(device);
+    int rc = nabo::check_csr_graph(n, ptr, nbr, w, nabo::CSR_FINITE_NOT_NEGATIVE);
     if (rc) return rc;
-    nabo_community *H = new nabo_community;
-    H->device = device;
-    rc = community_create(H, n, ptr, nbr, w, weight_scale);
-    if (rc) {
-        delete H;
-        return rc;
-    }
-    *out = H;
-    return NABO_OK;
+    if ((rc = nabo::use_device(device))) return rc;
+    return nabo::create_handle(out, device, "nabo_community_create",
+                               [&](nabo_community *H) { return community_create(H, n, ptr, nbr, w, weight_scale); });
 }
 
 void nabo_community_destroy(nabo_community *H)

@@ -95,4 +95,32 @@ hipError_t csr_build_launch(const int64_t *edge_r, const int64_t *edge_t, const 
     return hipGetLastError();
 }
 
+// Sorted 64-bit keys (row << 32 | column) -> their row pointer: ptr[r] = the first key whose row is >= r, r = 0 .. n.  Keys
+// that stand for no arc carry row n and sort to the end, so ptr[n] counts the arcs.  For the UMAP graph (umap.hip) and the
+// coarse graphs of the clustering (community.hip); n_keys >= 1.
+__global__ __launch_bounds__(256) void key_rowptr_kernel(const uint64_t *__restrict__ keys, int64_t n_keys, int64_t n, int64_t *__restrict__ ptr)
+{
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n_keys) return;
+    const int64_t r = (int64_t)(keys[q] >> 32);
+    const int64_t prev = q == 0 ? -1 : (int64_t)(keys[q - 1] >> 32);
+    for (int64_t x = prev + 1; x <= r; ++x) ptr[x] = q;
+    if (q == n_keys - 1)
+        for (int64_t x = r + 1; x <= n; ++x) ptr[x] = n_keys;
+}
+
+hipError_t key_rowptr_launch(const uint64_t *keys, int64_t n_keys, int64_t n, int64_t *ptr, hipStream_t st)
+{
+    hipLaunchKernelGGL(key_rowptr_kernel, dim3((unsigned)((n_keys + 255) / 256)), dim3(256), 0, st, keys, n_keys, n, ptr);
+    return hipGetLastError();
+}
+
+// the bits of such a key a radix sort has to look at: 32 of the column and those of the rows 0 .. n
+unsigned key_sort_bits(int64_t n)
+{
+    unsigned b = 1;
+    while (b < 32 && ((int64_t)1 << b) <= n) ++b;
+    return 32 + b;
+}
+
 }  // namespace nabo

@@ -362,10 +362,8 @@ int nabo_de_test(int32_t device, int64_t n_genes, int64_t n_cells, const int64_t
 {
     if (n_genes < 0 || n_genes >= ((int64_t)1 << 31)) return nabo::api_fail(NABO_E_INVALID, "n_genes=%lld out of range", (long long)n_genes);
     if (n_sets < 1 || n_sets >= ((int64_t)1 << 24)) return nabo::api_fail(NABO_E_INVALID, "n_sets=%lld out of range [1, 2^24)", (long long)n_sets);
-    if (!set_ptr) return nabo::api_fail(NABO_E_INVALID, "set_ptr is NULL");
-    if (set_ptr[0] != 0) return nabo::api_fail(NABO_E_INVALID, "set_ptr[0] = %lld, must be 0", (long long)set_ptr[0]);
-    for (int64_t s = 0; s < n_sets; ++s)
-        if (set_ptr[s + 1] < set_ptr[s]) return nabo::api_fail(NABO_E_INVALID, "set_ptr is not monotone at set %lld", (long long)s);
+    int rc = nabo::check_csr_ptr("set_ptr", "set", n_sets, set_ptr);
+    if (rc) return rc;
     if (set_ptr[n_sets] > 0 && !members) return nabo::api_fail(NABO_E_INVALID, "members is NULL");
     if (std::isnan(exp_frac_thresh) || std::isnan(log2_fc_thresh)) return nabo::api_fail(NABO_E_INVALID, "a threshold is NaN");
     if (!pair_test) n_pairs = n_sets - 1;
@@ -385,8 +383,7 @@ int nabo_de_test(int32_t device, int64_t n_genes, int64_t n_cells, const int64_t
     Side A, B;
     A.m = Csc{n_cells, gene_ptr, cell, val, sf};
     B.m = two ? Csc{n_cells2, gene_ptr2, cell2, val2, sf2} : A.m;
-    int rc = check_csc("matrix 1", n_genes, A.m);
-    if (rc) return rc;
+    if ((rc = check_csc("matrix 1", n_genes, A.m))) return rc;
     if (two && (rc = check_csc("matrix 2", n_genes, B.m))) return rc;
     // roles: 1 = test in some pair (reads matrix 1), 2 = control in some pair (reads matrix 2 when there is one)
     std::vector<uint8_t> role((size_t)n_sets, 0);

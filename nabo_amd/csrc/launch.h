@@ -157,6 +157,9 @@ hipError_t csr_build_launch(const int64_t *edge_r, const int64_t *edge_t, const 
                             int64_t n_t, uint32_t *keys_a, uint32_t *pos_a, uint32_t *keys_b, uint32_t *pos_b, void *temp,
                             size_t temp_bytes, int64_t *row_ptr, int64_t *out_t, double *out_w, unsigned int *flag,
                             hipStream_t st);
+// sorted (row << 32 | column) keys, row n for a key that is no arc -> ptr [n + 1]; and the bits their radix sort needs (csr_build.hip)
+hipError_t key_rowptr_launch(const uint64_t *keys, int64_t n_keys, int64_t n, int64_t *ptr, hipStream_t st);
+unsigned key_sort_bits(int64_t n);
 
 // differential expression: keys of a gene chunk, their sort and the rank kernel (de_rank.hip)
 hipError_t de_temp_bytes(int64_t nnz_max, int64_t keys_max, int64_t n_seg, size_t *bytes);
@@ -252,7 +255,7 @@ hipError_t umap_epoch_launch(int dims, int64_t n, const int64_t *ptr, const int3
 
 // Communities of the reference graph (community.hip; include/nabo_community.h has the definition).  One sweep is
 // totsize then sweep, which reads comm and writes comm_new; an aggregation is totsize, renumber, part_sums with keys,
-// coarse_sort, coarse_ptr, coarse_arcs and compose.
+// coarse_sort, key_rowptr, coarse_arcs and compose.
 struct CommunitySweep {
     double gamma, two_m;      // the resolution and 2m as a double
     uint64_t h2;              // mix(mix(seed + G (L + 1)) + G (s + 1)): the gate's part of (level, sweep)
@@ -276,8 +279,7 @@ hipError_t community_coarse_temp_bytes(int64_t A, int64_t n_next, size_t *bytes)
 hipError_t community_coarse_sort_launch(int64_t A, int64_t n_next, const uint64_t *keys_a, const int64_t *vals_a, uint64_t *keys_b,
                                         int64_t *vals_b, uint64_t *ukeys, int64_t *usums, int64_t *n_unique, void *temp, size_t temp_bytes,
                                         hipStream_t st);
-// the row pointer [n_next + 1] off the n_unique >= 1 sorted keys (ptr[n_next] = the coarse arcs, A); then src, nbr of these A >= 1
-hipError_t community_coarse_ptr_launch(const uint64_t *ukeys, int64_t n_unique, int64_t n_next, int64_t *ptr, hipStream_t st);
+// src, nbr of the A >= 1 coarse arcs, the first A of the sorted keys (A = ptr[n_next] of key_rowptr_launch)
 hipError_t community_coarse_arcs_launch(const uint64_t *ukeys, int64_t A, int32_t *src, int32_t *nbr, hipStream_t st);
 hipError_t community_compose_launch(int64_t n, int32_t *map, const int32_t *lab, hipStream_t st);
 // one round of the component split: hook, then pointer jumping; *changed != 0 if a label fell

@@ -22,6 +22,7 @@
 
 #include "../../include/nabo_layout.h"
 #include "host_common.h"
+#include "simple_graph.h"
 
 namespace nabo {
 
@@ -315,11 +316,6 @@ struct nabo_layout {
 
 namespace {
 
-struct Arc {
-    int64_t a, b, ord;
-    double w;
-};
-
 int layout_upload_scalars(nabo_layout *L, double speed, double eff)
 {
     nabo::LayoutScalars h;
@@ -332,52 +328,21 @@ int layout_upload_scalars(nabo_layout *L, double speed, double eff)
 
 int layout_create(nabo_layout *L, int64_t n, const int64_t *ptr, const int64_t *nbr, const double *w)
 {
-    // the simple graph: a pair keeps its last weight
-    const int64_t E = ptr[n];
-    std::vector<Arc> arcs((size_t)E);
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) arcs[(size_t)e] = Arc{std::min(i, nbr[e]), std::max(i, nbr[e]), e, w[e]};
-    std::sort(arcs.begin(), arcs.end(), [](const Arc &p, const Arc &q) {
-        if (p.a != q.a) return p.a < q.a;
-        if (p.b != q.b) return p.b < q.b;
-        return p.ord < q.ord;
-    });
-    size_t m = 0;
-    for (size_t e = 0; e < arcs.size(); ++e)
-        if (e + 1 == arcs.size() || arcs[e + 1].a != arcs[e].a || arcs[e + 1].b != arcs[e].b) arcs[m++] = arcs[e];
-    arcs.resize(m);
+    // the simple graph (simple_graph.h); a node's mass is 1 + its pairs, a self-loop counting once
+    nabo::SimpleGraph g;
     std::vector<double> mass((size_t)n, 1.0);
-    std::vector<int64_t> rptr((size_t)n + 1, 0);
-    for (const Arc &p : arcs) {
-        mass[(size_t)p.a] += 1.0;
-        if (p.a != p.b) {
-            mass[(size_t)p.b] += 1.0;
-            ++rptr[(size_t)p.a + 1];
-            ++rptr[(size_t)p.b + 1];
-        }
-    }
+    nabo::simple_graph(g, n, ptr, nbr, true, [&](size_t, int64_t a, int64_t b) {
+        mass[(size_t)a] += 1.0;
+        if (a != b) mass[(size_t)b] += 1.0;
+    });
     double msum = 0.0;
-    for (int64_t i = 0; i < n; ++i) {
-        msum += mass[(size_t)i];
-        rptr[(size_t)i + 1] += rptr[(size_t)i];
-    }
+    for (int64_t i = 0; i < n; ++i) msum += mass[(size_t)i];
     L->mean_mass = msum / (double)n;
+    const std::vector<int64_t> &rptr = g.rptr;
+    const std::vector<int32_t> &rnbr = g.rnbr;
     const int64_t A = rptr[(size_t)n];
-    std::vector<int32_t> rnbr((size_t)A);
     L->h_w.resize((size_t)A);
-    std::vector<int64_t> fill(rptr.begin(), rptr.end() - 1);
-    // rows in ascending neighbour: first the lower-numbered partners (pairs sorted by (a, b): ascending a for a fixed b),
-    // then the higher-numbered ones
-    for (const Arc &p : arcs)
-        if (p.a != p.b) {
-            rnbr[(size_t)fill[(size_t)p.b]] = (int32_t)p.a;
-            L->h_w[(size_t)fill[(size_t)p.b]++] = p.w;
-        }
-    for (const Arc &p : arcs)
-        if (p.a != p.b) {
-            rnbr[(size_t)fill[(size_t)p.a]] = (int32_t)p.b;
-            L->h_w[(size_t)fill[(size_t)p.a]++] = p.w;
-        }
+    for (size_t s = 0; s < (size_t)A; ++s) L->h_w[s] = w[g.last[(size_t)g.slot_pair[s]]];
     L->n = n;
     L->n_arcs = A;
     L->npad = (n + nabo::LAY_IBLOCK - 1) / nabo::LAY_IBLOCK * nabo::LAY_IBLOCK;
@@ -422,27 +387,10 @@ int nabo_layout_create(nabo_layout **out, int32_t device, int64_t n, const int64
     *out = nullptr;
     if (n < 1) return nabo::api_fail(NABO_E_INVALID, "n=%lld must be at least 1", (long long)n);
     if (n >= ((int64_t)1 << 24)) return nabo::api_fail(NABO_E_UNSUPPORTED, "n=%lld: the layout takes fewer than 2^24 nodes", (long long)n);
-    if (!ptr) return nabo::api_fail(NABO_E_INVALID, "ptr is NULL");
-    if (ptr[0] != 0) return nabo::api_fail(NABO_E_INVALID, "ptr[0] = %lld, must be 0", (long long)ptr[0]);
-    for (int64_t i = 0; i < n; ++i)
-        if (ptr[i + 1] < ptr[i]) return nabo::api_fail(NABO_E_INVALID, "ptr is not monotone at node %lld", (long long)i);
-    if (ptr[n] > 0 && (!nbr || !w)) return nabo::api_fail(NABO_E_INVALID, "nbr or w is NULL");
-    for (int64_t e = 0; e < ptr[n]; ++e) {
-        if (nbr[e] < 0 || nbr[e] >= n)
-            return nabo::api_fail(NABO_E_INVALID, "nbr[%lld] = %lld is not a node in [0, %lld)", (long long)e, (long long)nbr[e], (long long)n);
-        if (!std::isfinite(w[e])) return nabo::api_fail(NABO_E_INVALID, "w[%lld] is not finite", (long long)e);
-    }
-    int rc = nabo::use_device(device);
+    int rc = nabo::check_csr_graph(n, ptr, nbr, w, nabo::CSR_FINITE);
     if (rc) return rc;
-    nabo_layout *L = new nabo_layout;
-    L->device = device;
-    rc = layout_create(L, n, ptr, nbr, w);
-    if (rc) {
-        delete L;
-        return rc;
-    }
-    *out = L;
-    return NABO_OK;
+    if ((rc = nabo::use_device(device))) return rc;
+    return nabo::create_handle(out, device, "nabo_layout_create", [&](nabo_layout *L) { return layout_create(L, n, ptr, nbr, w); });
 }
 
 void nabo_layout_destroy(nabo_layout *L)

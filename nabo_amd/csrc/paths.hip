@@ -641,18 +641,15 @@ int nabo_refgraph_create(nabo_refgraph **out, int32_t device, int64_t n_nodes, c
     if (!out) return nabo::api_fail(NABO_E_INVALID, "out is NULL");
     *out = nullptr;
     if (n_nodes < 0 || n_nodes >= ((int64_t)1 << 31) - 1) return nabo::api_fail(NABO_E_INVALID, "n_nodes=%lld out of range [0, 2^31 - 1)", (long long)n_nodes);
-    if (!ptr) return nabo::api_fail(NABO_E_INVALID, "ptr is NULL");
-    if (ptr[0] != 0) return nabo::api_fail(NABO_E_INVALID, "ptr[0] = %lld, must be 0", (long long)ptr[0]);
-    for (int64_t i = 0; i < n_nodes; ++i)
-        if (ptr[i + 1] < ptr[i]) return nabo::api_fail(NABO_E_INVALID, "ptr is not monotone at row %lld", (long long)i);
+    int rc = nabo::check_csr_ptr("ptr", "row", n_nodes, ptr);
+    if (rc) return rc;
     const int64_t E = ptr[n_nodes];
     if (E >= ((int64_t)1 << 30)) return nabo::api_fail(NABO_E_UNSUPPORTED, "%lld arcs: fewer than 2^30 per graph", (long long)E);
     if (E > 0 && !nbr) return nabo::api_fail(NABO_E_INVALID, "nbr is NULL");
     for (int64_t e = 0; e < E; ++e)
         if (nbr[e] < 0 || nbr[e] >= n_nodes)
             return nabo::api_fail(NABO_E_INVALID, "nbr[%lld] = %lld is not a node index in [0, %lld)", (long long)e, (long long)nbr[e], (long long)n_nodes);
-    int rc = use_device(device);
-    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
     nabo_refgraph *g = new (std::nothrow) nabo_refgraph();
     if (!g) return nabo::api_fail(NABO_E_NOMEM, "host allocation failed");
     g->device = device;
@@ -863,10 +860,8 @@ int nabo_refgraph_set_levels(nabo_refgraph *g, int64_t n_sets, const int64_t *se
 {
     if (!g) return nabo::api_fail(NABO_E_INVALID, "NULL graph");
     if (n_sets < 0 || n_sets >= ((int64_t)1 << 31)) return nabo::api_fail(NABO_E_INVALID, "n_sets=%lld out of range", (long long)n_sets);
-    if (!set_ptr) return nabo::api_fail(NABO_E_INVALID, "set_ptr is NULL");
-    if (set_ptr[0] != 0) return nabo::api_fail(NABO_E_INVALID, "set_ptr[0] = %lld, must be 0", (long long)set_ptr[0]);
-    for (int64_t i = 0; i < n_sets; ++i)
-        if (set_ptr[i + 1] < set_ptr[i]) return nabo::api_fail(NABO_E_INVALID, "set_ptr is not monotone at set %lld", (long long)i);
+    int rc = nabo::check_csr_ptr("set_ptr", "set", n_sets, set_ptr);
+    if (rc) return rc;
     const int64_t M = set_ptr[n_sets], n = g->n;
     if (M > 0 && !members) return nabo::api_fail(NABO_E_INVALID, "members is NULL");
     if (M >= ((int64_t)1 << 31)) return nabo::api_fail(NABO_E_UNSUPPORTED, "%lld members: fewer than 2^31 per call", (long long)M);
@@ -880,8 +875,7 @@ int nabo_refgraph_set_levels(nabo_refgraph *g, int64_t n_sets, const int64_t *se
             node[i] = (int32_t)members[i];
             bit[i] = (uint8_t)(s % 64);
         }
-    int rc = use_device(g->device);
-    if (rc) return rc;
+    if ((rc = use_device(g->device))) return rc;
     nabo::cluster_set_device_ms(1, 0.0);
     if (n_sets == 0 || n == 0) return NABO_OK;
     rc = ensure_global_state(g);

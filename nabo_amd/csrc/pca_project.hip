@@ -192,11 +192,8 @@ hipError_t gene_stats_launch(const int64_t *gptr, const int32_t *cell, const flo
 int pca_check_sparse(const char *major, const char *minor, int64_t n_major, int64_t n_minor, const int64_t *ptr, const int32_t *idx,
                      const float *val, const float *sf, bool sf_by_major)
 {
-    const char *pn = sf_by_major ? "cell_ptr" : "gene_ptr";
-    if (!ptr) return api_fail(NABO_E_INVALID, "%s is NULL", pn);
-    if (ptr[0] != 0) return api_fail(NABO_E_INVALID, "%s[0] = %lld, must be 0", pn, (long long)ptr[0]);
-    for (int64_t i = 0; i < n_major; ++i)
-        if (ptr[i + 1] < ptr[i]) return api_fail(NABO_E_INVALID, "%s is not monotone at %s %lld", pn, major, (long long)i);
+    const int rc = check_csr_ptr(sf_by_major ? "cell_ptr" : "gene_ptr", major, n_major, ptr);
+    if (rc) return rc;
     if (ptr[n_major] > 0 && (!idx || !val)) return api_fail(NABO_E_INVALID, "%s or val is NULL", minor);
     if ((sf_by_major ? n_major : n_minor) > 0 && !sf) return api_fail(NABO_E_INVALID, "sf is NULL");
     for (int64_t i = 0; i < n_major; ++i) {

@@ -28,6 +28,7 @@
 
 #include "../../include/nabo_potential.h"
 #include "host_common.h"
+#include "simple_graph.h"
 
 namespace nabo {
 
@@ -234,21 +235,6 @@ struct nabo_potential {
 
 namespace {
 
-struct Timer {
-    nabo_potential *H;
-    int start() { HIP_TRY(hipEventRecord(H->ev[0], nullptr)); return NABO_OK; }
-    int stop(int which)
-    {
-        HIP_TRY(hipEventRecord(H->ev[1], nullptr));
-        HIP_TRY(hipEventSynchronize(H->ev[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, H->ev[0], H->ev[1]));
-        H->ms[which] += ms;
-        H->ms[3] += ms;
-        return NABO_OK;
-    }
-};
-
 int32_t uf_find(std::vector<int32_t> &parent, int32_t i)
 {
     while (parent[(size_t)i] != i) {
@@ -260,35 +246,24 @@ int32_t uf_find(std::vector<int32_t> &parent, int32_t i)
 
 int potential_create(nabo_potential *H, int64_t n, const int64_t *ptr, const int64_t *nbr)
 {
-    // the simple graph: every pair once, as (lower << 32 | higher)
-    const int64_t E = ptr[n];
-    std::vector<uint64_t> pairs((size_t)E);
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e)
-            pairs[(size_t)e] = ((uint64_t)std::min(i, nbr[e]) << 32) | (uint64_t)std::max(i, nbr[e]);
-    std::sort(pairs.begin(), pairs.end());
-    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    // the simple graph (simple_graph.h); d counts a self-loop once, c is the row's length, the components are those of the pairs
+    nabo::SimpleGraph g;
     H->n = n;
     H->d.assign((size_t)n, 0);
-    H->c.assign((size_t)n, 0);
-    std::vector<int64_t> rptr((size_t)n + 1, 0);
     std::vector<int32_t> parent((size_t)n);
     for (int64_t i = 0; i < n; ++i) parent[(size_t)i] = (int32_t)i;
-    for (uint64_t k : pairs) {
-        const int64_t a = (int64_t)(k >> 32), b = (int64_t)(k & 0xFFFFFFFFull);
-        if (a == b) {
-            ++H->d[(size_t)a];
-            continue;
-        }
+    nabo::simple_graph(g, n, ptr, nbr, false, [&](size_t, int64_t a, int64_t b) {
         ++H->d[(size_t)a];
+        if (a == b) return;
         ++H->d[(size_t)b];
-        ++H->c[(size_t)a];
-        ++H->c[(size_t)b];
-        ++rptr[(size_t)a + 1];
-        ++rptr[(size_t)b + 1];
         const int32_t ra = uf_find(parent, (int32_t)a), rb = uf_find(parent, (int32_t)b);
         if (ra != rb) parent[(size_t)std::max(ra, rb)] = std::min(ra, rb);   // the smaller root stays: a root is its component's smallest node
-    }
+    });
+    const std::vector<int64_t> &rptr = g.rptr;
+    const std::vector<int32_t> &rnbr = g.rnbr;
+    const int64_t A = rptr[(size_t)n];
+    H->c.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) H->c[(size_t)i] = rptr[(size_t)i + 1] - rptr[(size_t)i];
     H->label.resize((size_t)n);
     H->comp.resize((size_t)n);
     H->comp_size.clear();
@@ -303,23 +278,9 @@ int potential_create(nabo_potential *H, int64_t n, const int64_t *ptr, const int
         ++H->comp_size[(size_t)H->comp[(size_t)i]];
     }
     H->n_comp = (int64_t)H->comp_size.size();
-    // rows in ascending neighbour: first the lower-numbered partners (pairs sorted by (a, b)), then the higher-numbered
-    for (int64_t i = 0; i < n; ++i) rptr[(size_t)i + 1] += rptr[(size_t)i];
-    const int64_t A = rptr[(size_t)n];
-    std::vector<int32_t> rnbr((size_t)A);
-    std::vector<int64_t> fill(rptr.begin(), rptr.end() - 1);
-    for (uint64_t k : pairs) {
-        const int64_t a = (int64_t)(k >> 32), b = (int64_t)(k & 0xFFFFFFFFull);
-        if (a != b) rnbr[(size_t)fill[(size_t)b]++] = (int32_t)a;
-    }
-    for (uint64_t k : pairs) {
-        const int64_t a = (int64_t)(k >> 32), b = (int64_t)(k & 0xFFFFFFFFull);
-        if (a != b) rnbr[(size_t)fill[(size_t)a]++] = (int32_t)b;
-    }
-    std::vector<int32_t> long_rows;
+    const std::vector<int32_t> long_rows = nabo::long_rows(rptr, nabo::PT_LONG);
     std::vector<double> cd((size_t)n), invc((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
-        if (rptr[(size_t)i + 1] - rptr[(size_t)i] > nabo::PT_LONG) long_rows.push_back((int32_t)i);
         cd[(size_t)i] = (double)H->c[(size_t)i];
         invc[(size_t)i] = H->c[(size_t)i] ? 1.0 / (double)H->c[(size_t)i] : 0.0;
     }
@@ -420,7 +381,7 @@ int potential_prepare(nabo_potential *H, const double *r)
     }
     H->bnorm = std::sqrt(bb);
     if (!std::isfinite(H->bnorm)) return nabo::api_fail(NABO_E_INVALID, "the right-hand side overflows: ||b|| is not finite");
-    Timer T{H};
+    nabo::PhaseTimer T{H->ev, H->ms, 3};
     int rc;
     if ((rc = T.start())) return rc;
     HIP_TRY(hipMemsetAsync(H->x.p, 0, nb, nullptr));
@@ -446,7 +407,7 @@ int potential_prepare(nabo_potential *H, const double *r)
 
 int potential_iterate(nabo_potential *H, int64_t count)
 {
-    Timer T{H};
+    nabo::PhaseTimer T{H->ev, H->ms, 3};
     int rc;
     if ((rc = T.start())) return rc;
     while (count > 0 && !H->hs.done) {
@@ -463,7 +424,7 @@ int potential_finish(nabo_potential *H, double *V)
 {
     const int64_t n = H->n;
     const size_t nb = (size_t)n * 8;
-    Timer T{H};
+    nabo::PhaseTimer T{H->ev, H->ms, 3};
     int rc;
     if ((rc = T.start())) return rc;
     if ((rc = product_enqueue(H, H->x.as<double>(), 1))) return rc;
@@ -509,14 +470,8 @@ int nabo_potential_create(nabo_potential **out, int32_t device, int64_t n, const
     *out = nullptr;
     if (n < 1) return nabo::api_fail(NABO_E_INVALID, "n=%lld must be at least 1", (long long)n);
     if (n >= ((int64_t)1 << 31)) return nabo::api_fail(NABO_E_UNSUPPORTED, "n=%lld: the potential takes fewer than 2^31 nodes", (long long)n);
-    if (!ptr) return nabo::api_fail(NABO_E_INVALID, "ptr is NULL");
-    if (ptr[0] != 0) return nabo::api_fail(NABO_E_INVALID, "ptr[0] = %lld, must be 0", (long long)ptr[0]);
-    for (int64_t i = 0; i < n; ++i)
-        if (ptr[i + 1] < ptr[i]) return nabo::api_fail(NABO_E_INVALID, "ptr is not monotone at node %lld", (long long)i);
-    if (ptr[n] > 0 && !nbr) return nabo::api_fail(NABO_E_INVALID, "nbr is NULL");
-    for (int64_t e = 0; e < ptr[n]; ++e)
-        if (nbr[e] < 0 || nbr[e] >= n)
-            return nabo::api_fail(NABO_E_INVALID, "nbr[%lld] = %lld is not a node in [0, %lld)", (long long)e, (long long)nbr[e], (long long)n);
+    int rc = nabo::check_csr_graph(n, ptr, nbr, nullptr, nabo::CSR_NO_WEIGHTS);
+    if (rc) return rc;
     // a node without an edge is an error of the input: found before any device is asked for
     {
         std::vector<uint8_t> seen((size_t)n, 0);
@@ -526,17 +481,8 @@ int nabo_potential_create(nabo_potential **out, int32_t device, int64_t n, const
             if (!seen[(size_t)i])
                 return nabo::api_fail(NABO_E_INVALID, "node %lld has no edge: its row of I - A/D is a division by zero", (long long)i);
     }
-    int rc = nabo::use_device(device);
-    if (rc) return rc;
-    nabo_potential *H = new nabo_potential;
-    H->device = device;
-    rc = potential_create(H, n, ptr, nbr);
-    if (rc) {
-        delete H;
-        return rc;
-    }
-    *out = H;
-    return NABO_OK;
+    if ((rc = nabo::use_device(device))) return rc;
+    return nabo::create_handle(out, device, "nabo_potential_create", [&](nabo_potential *H) { return potential_create(H, n, ptr, nbr); });
 }
 
 void nabo_potential_destroy(nabo_potential *H)

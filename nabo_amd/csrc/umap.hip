@@ -175,19 +175,6 @@ __global__ __launch_bounds__(UM_THREADS) void umap_prune_kernel(uint64_t *__rest
     if (w[q] < wmax[0] / n_epochs) keys[q] = (uint64_t)n << 32;
 }
 
-// ptr[r] = the first sorted slot whose row is >= r, r = 0 .. n; unused slots carry row n
-__global__ __launch_bounds__(UM_THREADS) void umap_rowptr_kernel(const uint64_t *__restrict__ keys, int64_t n_slots, int64_t n,
-                                                                 int64_t *__restrict__ ptr)
-{
-    const int64_t q = (int64_t)blockIdx.x * UM_THREADS + threadIdx.x;
-    if (q >= n_slots) return;
-    const int64_t r = (int64_t)(keys[q] >> 32);
-    const int64_t prev = q == 0 ? -1 : (int64_t)(keys[q - 1] >> 32);
-    for (int64_t x = prev + 1; x <= r; ++x) ptr[x] = q;
-    if (q == n_slots - 1)
-        for (int64_t x = r + 1; x <= n; ++x) ptr[x] = n_slots;
-}
-
 // the arcs of the pruned CSR and the first state of their schedule
 __global__ __launch_bounds__(UM_THREADS) void umap_arcs_kernel(const uint64_t *__restrict__ keys, const double *__restrict__ w, int64_t n_arcs,
                                                                const double *__restrict__ wmax, double nsr, int32_t *__restrict__ nbr,
@@ -319,18 +306,11 @@ hipError_t umap_smooth_launch(const double *dist, int64_t n, int k, double targe
     return hipGetLastError();
 }
 
-static int umap_key_bits(int64_t n)
-{
-    int b = 1;
-    while (b < 32 && ((int64_t)1 << b) <= n) ++b;   // rows 0 .. n, n the row of an unused slot
-    return 32 + b;
-}
-
 hipError_t umap_sort_temp_bytes(int64_t n_slots, int64_t n, size_t *bytes)
 {
     *bytes = 0;
     return rocprim::radix_sort_pairs(nullptr, *bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const double *)nullptr,
-                                     (double *)nullptr, (size_t)n_slots, 0u, (unsigned)umap_key_bits(n), (hipStream_t) nullptr);
+                                     (double *)nullptr, (size_t)n_slots, 0u, key_sort_bits(n), (hipStream_t) nullptr);
 }
 
 hipError_t umap_graph_launch(const int64_t *idx, const double *dist, int64_t n, int k, const double *rho, const double *sigma,
@@ -346,10 +326,9 @@ hipError_t umap_graph_launch(const int64_t *idx, const double *dist, int64_t n, 
                        reinterpret_cast<unsigned long long *>(wmax));
     hipLaunchKernelGGL(umap_prune_kernel, dim3(g2), dim3(UM_THREADS), 0, st, keys_a, w_a, n_slots, n, wmax, n_epochs);
     e = rocprim::radix_sort_pairs(temp, temp_bytes, (const uint64_t *)keys_a, keys_b, (const double *)w_a, w_b, (size_t)n_slots, 0u,
-                                  (unsigned)umap_key_bits(n), st);
+                                  key_sort_bits(n), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(umap_rowptr_kernel, dim3(g2), dim3(UM_THREADS), 0, st, keys_b, n_slots, n, ptr);
-    return hipGetLastError();
+    return key_rowptr_launch(keys_b, n_slots, n, ptr, st);   // unused slots carry row n
 }
 
 hipError_t umap_arcs_launch(const uint64_t *keys, const double *w, int64_t n_arcs, const double *wmax, double nsr, int32_t *nbr,
@@ -620,9 +599,8 @@ int nabo_umap_set_graph(nabo_umap *U, const int64_t *ptr, const int64_t *nbr, co
 {
     if (!U || !ptr) return nabo::api_fail(NABO_E_INVALID, "NULL argument");
     const int64_t n = U->n;
-    if (ptr[0] != 0) return nabo::api_fail(NABO_E_INVALID, "ptr[0] = %lld, must be 0", (long long)ptr[0]);
-    for (int64_t i = 0; i < n; ++i)
-        if (ptr[i + 1] < ptr[i]) return nabo::api_fail(NABO_E_INVALID, "ptr is not monotone at node %lld", (long long)i);
+    int rc = nabo::check_csr_ptr("ptr", "node", n, ptr);
+    if (rc) return rc;
     const int64_t E = ptr[n];
     if (E < 1 || !nbr || !w) return nabo::api_fail(NABO_E_INVALID, "the graph has no arc, or nbr or w is NULL");
     std::vector<uint64_t> keys((size_t)E);
@@ -635,8 +613,7 @@ int nabo_umap_set_graph(nabo_umap *U, const int64_t *ptr, const int64_t *nbr, co
             keys[(size_t)e] = ((uint64_t)i << 32) | (uint64_t)nbr[e];
             wmax = std::max(wmax, w[e]);
         }
-    int rc = nabo::use_device(U->device);
-    if (rc) return rc;
+    if ((rc = nabo::use_device(U->device))) return rc;
     U->have_graph = false;
     U->k = 0;
     for (DevBuf *b : {&U->rho, &U->sigma}) {
