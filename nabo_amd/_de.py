@@ -13,6 +13,7 @@ from collections import Counter
 import numpy as np
 
 from . import _lib
+from ._matrixio import DatasetFile as _DatasetFile, csc as _csc
 
 SKIP_GENE, SKIP_PAIR, ASYMPTOTIC, EXACT, EMPTY = 0, 1, 2, 3, 4
 COLUMNS = ["gene", "exp_frac", "test_group", "versus_group", "rbc", "log2_fc", "pval", "qval"]
@@ -21,22 +22,6 @@ _FIELDS = (("status", np.int32), ("nonzero_test", np.int64), ("n1", np.int64), (
 
 
 # ---- arrays -------------------------------------------------------------------------------------------------------
-def _csc(m, what):
-    """(n_cells, gene_ptr int64, cell int32, val float32, sf float32) from (gene_ptr, cell, val, sf)"""
-    gene_ptr, cell, val, sf = m
-    gene_ptr = np.ascontiguousarray(gene_ptr, dtype=np.int64)
-    cell_in = np.asarray(cell)
-    if cell_in.size and (cell_in.min() < -2 ** 31 or cell_in.max() >= 2 ** 31):
-        raise ValueError("ERROR: %s: a cell index does not fit 32 bits" % what)
-    cell = np.ascontiguousarray(cell_in, dtype=np.int32)
-    val, sf = np.ascontiguousarray(val, dtype=np.float32), np.ascontiguousarray(sf, dtype=np.float32)
-    if gene_ptr.ndim != 1 or cell.ndim != 1 or val.ndim != 1 or sf.ndim != 1 or gene_ptr.shape[0] < 1:
-        raise ValueError("ERROR: %s: gene_ptr, cell, val and sf must be 1-D, gene_ptr with n_genes + 1 entries" % what)
-    if cell.shape != val.shape or int(gene_ptr[-1]) != cell.shape[0]:
-        raise ValueError("ERROR: %s: gene_ptr[-1] = %d, cell has %d and val %d entries" % (what, int(gene_ptr[-1]), cell.shape[0], val.shape[0]))
-    return sf.shape[0], gene_ptr, cell, val, sf
-
-
 def _device_de(n_genes, m1, m2, set_ptr, members, pair_test, pair_ctrl, exp_frac_thresh, log2_fc_thresh, mem_budget=0, device=0):
     """the device step: per-pair arrays of shape (n_genes, n_pairs), see de_test_csc.  m1, m2: _csc tuples, m2 or None"""
     n_pairs = len(pair_test)
@@ -217,86 +202,6 @@ def _markers_from_csc(clusters, genes, m1, de_frequency, exp_frac_thresh, log2_f
 
 
 # ---- the Nabo dataset file ----------------------------------------------------------------------------------------
-class _DatasetFile:
-    """what the reference's Dataset reads of a Nabo HDF5 file for this path (nabo/_dataset.py:87-127, 165-206): cell and
-    gene names, the kept genes (all, when the file names none), the size factors (ones, when it holds none) and a
-    gene's (idx, val) column.  Opened read-only; the reference's Dataset creates `processed_data` when it is missing."""
-
-    def __init__(self, fn):
-        import h5py
-        self.h5 = h5py.File(fn, "r")
-        self.cells = [x.decode("UTF-8") for x in self.h5["names"]["cells"][:]]
-        self.genes = [x.decode("UTF-8") for x in self.h5["names"]["genes"][:]]
-        self.cell_idx = {x: n for n, x in enumerate(self.cells)}
-        grp = self.h5["processed_data"] if "processed_data" in self.h5 else {}
-        self.keep_genes_idx = [int(x) for x in grp["keep_genes_idx"][:]] if "keep_genes_idx" in grp else list(range(len(self.genes)))
-        self.keep_cells_idx = [int(x) for x in grp["keep_cells_idx"][:]] if "keep_cells_idx" in grp else list(range(len(self.cells)))
-        if "sf" in grp:
-            self.sf = grp["sf"][:]
-            if self.sf.dtype != np.float32:
-                raise ValueError("ERROR: processed_data/sf is %s; Nabo writes float32 size factors and the values are "
-                                 "defined as float32 products" % self.sf.dtype)
-        else:
-            self.sf = np.ones(len(self.cells), dtype=np.float32)
-
-    def close(self):
-        self.h5.close()
-
-    @staticmethod
-    def _record(d):
-        """(idx int64 strictly increasing, val float32) of an (idx, val) record; an index listed twice keeps its last
-        value, as the reference's scatter does"""
-        idx, val = np.asarray(d["idx"], dtype=np.int64), np.asarray(d["val"], dtype=np.float32)
-        if idx.shape[0] > 1 and (np.diff(idx) <= 0).any():
-            last = {int(c): k for k, c in enumerate(idx.tolist())}
-            keep = np.array(sorted(last.values()), dtype=np.int64)
-            idx, val = idx[keep], val[keep]
-            o = np.argsort(idx, kind="stable")
-            idx, val = idx[o], val[o]
-        return idx, val
-
-    def csr(self, cells_idx):
-        """(cell_ptr int64, gene int32, val float32, sf) over ALL cells of the file, from the `cell_data/<cell>` records
-        (nabo/_dataset.py:906-908): the rows of `cells_idx` are read, every other row is empty"""
-        n = len(self.cells)
-        counts = np.zeros(n, dtype=np.int64)
-        got = {}
-        cd = self.h5["cell_data"]
-        for i in dict.fromkeys(int(x) for x in cells_idx):
-            got[i] = self._record(cd[self.cells[i]][:])
-            counts[i] = got[i][0].shape[0]
-        order = sorted(got)
-        ptr = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(counts, out=ptr[1:])
-        gene = np.concatenate([got[i][0] for i in order] + [np.zeros(0, np.int64)])
-        if gene.size and (gene.min() < 0 or gene.max() >= len(self.genes)):
-            raise ValueError("ERROR: cell_data holds a gene index outside [0, %d)" % len(self.genes))
-        return ptr, gene.astype(np.int32), np.concatenate([got[i][1] for i in order] + [np.zeros(0, np.float32)]), self.sf
-
-    def csc(self, genes, upper=True):
-        """the columns of `genes` as a _csc tuple.  A cell listed twice in a column keeps its last value, as the
-        reference's scatter does.  `upper`: look the names up in upper case, as get_norm_exp does (:186)."""
-        ptr, cells, vals = [0], [], []
-        gd = self.h5["gene_data"]
-        for g in genes:
-            try:
-                d = gd[g.upper() if upper else g][:]
-            except KeyError:
-                raise KeyError("ERROR: This gene symbol does not exist in the dataset.")
-            idx, val = np.asarray(d["idx"], dtype=np.int64), np.asarray(d["val"], dtype=np.float32)
-            if idx.shape[0] > 1 and (np.diff(idx) <= 0).any():
-                last = {int(c): k for k, c in enumerate(idx.tolist())}
-                keep = np.array(sorted(last.values()), dtype=np.int64)
-                idx, val = idx[keep], val[keep]
-                o = np.argsort(idx, kind="stable")
-                idx, val = idx[o], val[o]
-            cells.append(idx)
-            vals.append(val)
-            ptr.append(ptr[-1] + idx.shape[0])
-        return _csc((np.array(ptr, dtype=np.int64), np.concatenate(cells) if cells else np.zeros(0, np.int64),
-                     np.concatenate(vals) if vals else np.zeros(0, np.float32), self.sf), "the dataset")
-
-
 def _valid_genes(d1, d2):
     """the genes the reference loops over (:57-66): the kept genes of dataset1 by name, repeats once, and with a second
     dataset only those it names too"""

@@ -14,41 +14,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._de import _DatasetFile, _csc
+from ._matrixio import DatasetFile as _DatasetFile, csc as _csc, csr as _csr, index_list as _index_list, int32 as _int32, ptr as _ptr
 
 _STAT_FIELDS = (("ncells", np.int64), ("valid", np.uint8), ("m", np.float64), ("nzm", np.float64), ("variance", np.float64))
 
 
 # ---- arrays -------------------------------------------------------------------------------------------------------
-def _int32(a, what):
-    a = np.asarray(a)
-    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-        raise ValueError("ERROR: %s: an index does not fit 32 bits" % what)
-    return np.ascontiguousarray(a, dtype=np.int32)
-
-
-def _csr(m):
-    """(n_cells, cell_ptr int64, gene int32, val float32, sf float32) from (cell_ptr, gene, val, sf)"""
-    cell_ptr, gene, val, sf = m
-    cell_ptr = np.ascontiguousarray(cell_ptr, dtype=np.int64)
-    gene = _int32(gene, "gene")
-    val, sf = np.ascontiguousarray(val, dtype=np.float32), np.ascontiguousarray(sf, dtype=np.float32)
-    if cell_ptr.ndim != 1 or gene.ndim != 1 or val.ndim != 1 or sf.ndim != 1 or cell_ptr.shape[0] < 1:
-        raise ValueError("ERROR: cell_ptr, gene, val and sf must be 1-D, cell_ptr with n_cells + 1 entries")
-    if sf.shape[0] != cell_ptr.shape[0] - 1:
-        raise ValueError("ERROR: cell_ptr describes %d cells, sf holds %d" % (cell_ptr.shape[0] - 1, sf.shape[0]))
-    if gene.shape != val.shape or int(cell_ptr[-1]) != gene.shape[0]:
-        raise ValueError("ERROR: cell_ptr[-1] = %d, gene has %d and val %d entries" % (int(cell_ptr[-1]), gene.shape[0], val.shape[0]))
-    return sf.shape[0], cell_ptr, gene, val, sf
-
-
-def _ptr(a):
-    """the address of an index list for the C ABI, where NULL means 'all': None -> NULL, an empty list -> not NULL"""
-    if a is None:
-        return None
-    return a.ctypes.data if a.shape[0] else np.zeros(1, dtype=np.int64).ctypes.data
-
-
 def _device_project(m, gene_pos, mu, sigma, mean, components, rows, mem_budget=0, device=0):
     """the device step of the projection: Z[n_rows, C].  m: a _csr tuple; the tables checked by _tables; rows int64 or None"""
     n_rows = m[0] if rows is None else rows.shape[0]
@@ -123,15 +94,6 @@ def _tables(gene_pos, mu, sigma, mean, components):
         raise ValueError("ERROR: mu holds %d genes, sigma %d, mean %d, components has shape %s: need [n_comps >= 1, %d]"
                          % (G, sigma.shape[0], mean.shape[0], components.shape, G))
     return gene_pos, mu, sigma, mean, components
-
-
-def _index_list(a, what):
-    if a is None:
-        return None
-    a = np.ascontiguousarray(a, dtype=np.int64)
-    if a.ndim != 1:
-        raise ValueError("ERROR: %s must be 1-D" % what)
-    return a
 
 
 def pca_project_csr(cell_ptr, gene, val, sf, gene_pos, mu, sigma, mean, components, rows=None, mem_budget=0, device=0):

@@ -13,9 +13,8 @@ import re
 
 import numpy as np
 
-from . import _lib
-from ._de import _DatasetFile
-from ._pca import _device_stats, _index_list, _int32, _ptr
+from . import _lib, _pca
+from ._matrixio import DatasetFile as _DatasetFile, csr as _csr, index_list as _index_list, ptr as _ptr
 
 LDS_TABLE_GENES = 65536             # QC_LDS_TABLE_GENES of cell_qc.hip: up to here the class table is staged in LDS
 MITO_PATTERNS = ("^MT-",)           # Dataset.__init__'s defaults (:128-132)
@@ -24,19 +23,8 @@ STAT_COLUMNS = ("valid_gene", "m", "nzm", "variance", "ncells")
 
 
 # ---- arrays -------------------------------------------------------------------------------------------------------
-def _csr3(cell_ptr, gene, val):
-    cell_ptr = np.ascontiguousarray(cell_ptr, dtype=np.int64)
-    gene = _int32(gene, "gene")
-    val = np.ascontiguousarray(val, dtype=np.float32)
-    if cell_ptr.ndim != 1 or gene.ndim != 1 or val.ndim != 1 or cell_ptr.shape[0] < 1:
-        raise ValueError("ERROR: cell_ptr, gene and val must be 1-D, cell_ptr with n_cells + 1 entries")
-    if gene.shape != val.shape or int(cell_ptr[-1]) != gene.shape[0]:
-        raise ValueError("ERROR: cell_ptr[-1] = %d, gene has %d and val %d entries" % (int(cell_ptr[-1]), gene.shape[0], val.shape[0]))
-    return cell_ptr, gene, val
-
-
 def _device_qc(cell_ptr, gene, val, gene_class, n_classes, rows=None, mem_budget=0, device=0):
-    """the device step: (n_entries int64 [n_rows], sums float64 [n_rows, 1 + n_classes]).  Arrays as _csr3 returns them;
+    """the device step: (n_entries int64 [n_rows], sums float64 [n_rows, 1 + n_classes]).  Arrays as _csr returns them;
     gene_class uint8 [n_raw_genes]; rows int64 or None"""
     n_cells, n_classes = cell_ptr.shape[0] - 1, int(n_classes)
     n_rows = n_cells if rows is None else rows.shape[0]
@@ -66,7 +54,7 @@ def cell_qc_csr(cell_ptr, gene, val, gene_class=None, n_classes=0, rows=None, me
     [n_rows], sums float64 [n_rows, 1 + n_classes]): column 0 the cell's total, column 1 + c the total over the genes
     of class c, float64 sums in the header's fixed order -- the same bits on every run and for every chunking.  Bad input
     raises ValueError before any device is touched."""
-    cell_ptr, gene, val = _csr3(cell_ptr, gene, val)
+    cell_ptr, gene, val = _csr((cell_ptr, gene, val))
     if gene_class is None:
         if int(n_classes) != 0:
             raise ValueError("ERROR: n_classes=%d without gene_class" % int(n_classes))
@@ -176,7 +164,7 @@ def _filter_from_csr(raw_genes, m, gene_abundance, keep_cells_idx, keep_genes_id
     """filter_data on arrays: raw_genes names the genes of the (cell_ptr, gene, val) tuple `m` over ALL raw cells.
     Returns (keep_cells, keep_genes, counts) as _filter_from_sums does."""
     cls, mito_idx, ribo_idx = _classes(raw_genes, None, mito_patterns, ribo_patterns)
-    n_ent, sums = step(*_csr3(*m), cls, 2)
+    n_ent, sums = step(*_csr(m), cls, 2)
     return _filter_from_sums(n_ent, sums[:, 0], sums[:, 1], sums[:, 2], gene_abundance, keep_cells_idx, keep_genes_idx, mito_idx, ribo_idx,
                              **thresholds)
 
@@ -193,10 +181,10 @@ def _sf_from_csr(cells, n_raw_genes, m, keep_genes_idx, sf_now, sf=None, size_sc
         return out
     cls = np.zeros(n_raw_genes, dtype=np.uint8)
     if all_genes:
-        _, sums = step(*_csr3(*m), cls, 0)
+        _, sums = step(*_csr(m), cls, 0)
         return _sf_from_sums(sums[:, 0], size_scale)
     cls[np.asarray(keep_genes_idx, dtype=np.int64)] = 1
-    _, sums = step(*_csr3(*m), cls, 1)
+    _, sums = step(*_csr(m), cls, 1)
     return _sf_from_sums(sums[:, 1], size_scale)
 
 
@@ -212,7 +200,7 @@ def _qc_and_sf_from_csr(raw_genes, m, gene_abundance, keep_cells_idx, keep_genes
     _, keep_genes, _ = _filter_from_sums(np.zeros(n_cells), np.zeros(n_cells), np.zeros(n_cells), np.zeros(n_cells), gene_abundance, [],
                                          keep_genes_idx, mito_idx, ribo_idx, **thresholds)
     cls[keep_genes] |= 4
-    n_ent, sums = step(*_csr3(*m), cls, 3)
+    n_ent, sums = step(*_csr(m), cls, 3)
     kw = dict(thresholds)
     if kw.get("min_gene_abundance", 0) < 0:
         kw["min_gene_abundance"] = 0                        # (the two lines were printed above)
@@ -527,5 +515,5 @@ def gene_stats(dataset_h5, device=0):
         d.close()
     keep = np.zeros(len(raw_genes), dtype=np.uint8)
     keep[np.asarray(keep_genes_idx, dtype=np.int64)] = 1
-    st = _device_stats(m, np.ascontiguousarray(keep_cells, dtype=np.int64), keep, device=device)
+    st = _pca._device_stats(m, np.ascontiguousarray(keep_cells, dtype=np.int64), keep, device=device)
     return _stats_table(raw_genes, st)

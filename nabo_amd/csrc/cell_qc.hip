@@ -147,15 +147,6 @@ constexpr int64_t QC_MAX_CHUNK_ROWS = (int64_t)1 << 30;
 thread_local double g_qc_ms[3] = {0, 0, 0};
 thread_local int64_t g_qc_chunks = 0;
 
-struct Events {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events()
-    {
-        for (int i = 0; i < 4; ++i)
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -171,68 +162,31 @@ int nabo_cell_qc(int32_t device, int64_t n_cells, int64_t n_raw_genes, const int
     if (!rows) n_rows = n_cells;
     if (n_rows < 0) return nabo::api_fail(NABO_E_INVALID, "n_rows=%lld is negative", (long long)n_rows);
     if (n_rows > 0 && (!out_n_entries || !out_sums)) return nabo::api_fail(NABO_E_INVALID, "an output array is NULL");
-    int rc = nabo::check_csr_ptr("cell_ptr", "cell", n_cells, cell_ptr);
+    int rc = nabo::check_sparse<nabo::SPARSE_RAW>(nullptr, "cell", "gene", n_cells, n_raw_genes, cell_ptr, gene, val, nullptr, true);
     if (rc) return rc;
-    if (cell_ptr[n_cells] > 0 && (!gene || !val)) return nabo::api_fail(NABO_E_INVALID, "gene or val is NULL");
-    for (int64_t i = 0; i < n_cells; ++i) {
-        int64_t last = -1;
-        for (int64_t e = cell_ptr[i]; e < cell_ptr[i + 1]; ++e) {
-            const int64_t j = gene[e];
-            if (j < 0 || j >= n_raw_genes)
-                return nabo::api_fail(NABO_E_INVALID, "gene[%lld] = %lld is not a gene in [0, %lld)", (long long)e, (long long)j, (long long)n_raw_genes);
-            if (j <= last)
-                return nabo::api_fail(NABO_E_INVALID, "the genes of cell %lld are not strictly increasing at entry %lld", (long long)i, (long long)e);
-            last = j;
-            const float v = val[e];
-            if (!(v >= 0.0f) || std::isinf(v))
-                return nabo::api_fail(NABO_E_INVALID, "entry %lld (cell %lld, gene %lld): value %g must be finite and >= 0", (long long)e, (long long)i,
-                                      (long long)j, (double)v);
-        }
-    }
-    for (int64_t r = 0; rows && r < n_rows; ++r)
-        if (rows[r] < 0 || rows[r] >= n_cells)
-            return nabo::api_fail(NABO_E_INVALID, "rows[%lld] = %lld is not a cell in [0, %lld)", (long long)r, (long long)rows[r], (long long)n_cells);
+    if ((rc = nabo::check_rows(n_rows, rows, n_cells))) return rc;
     // chunks of rows within the budget
     const int NS = 1 + n_classes;
     const int64_t budget = mem_budget_bytes > 0 ? mem_budget_bytes : QC_DEFAULT_BUDGET;
-    const int64_t per_row_fixed = 16 + 8 * (int64_t)NS;
-    auto row_entries = [&](int64_t r) {
-        const int64_t c = rows ? rows[r] : r;
-        return cell_ptr[c + 1] - cell_ptr[c];
-    };
-    std::vector<int64_t> chunk_start{0};
-    int64_t max_rows = 0, max_nnz = 0;
-    {
-        int64_t used = 0, nnz = 0;
-        for (int64_t r = 0; r < n_rows; ++r) {
-            const int64_t ne = row_entries(r), b = per_row_fixed + 8 * ne, r0 = chunk_start.back();
-            if (b > budget) return nabo::api_fail(NABO_E_NOMEM, "row %lld alone needs %lld bytes of device buffers, the budget is %lld", (long long)r, (long long)b, (long long)budget);
-            if (r > r0 && (used + b > budget || r - r0 >= QC_MAX_CHUNK_ROWS)) {
-                chunk_start.push_back(r);
-                used = nnz = 0;
-            }
-            used += b;
-            nnz += ne;
-            max_rows = r + 1 - chunk_start.back() > max_rows ? r + 1 - chunk_start.back() : max_rows;
-            max_nnz = nnz > max_nnz ? nnz : max_nnz;
-        }
-        chunk_start.push_back(n_rows);
-    }
+    const nabo::RowChunks plan = nabo::plan_row_chunks(n_rows, rows, cell_ptr, 16 + 8 * (int64_t)NS, budget, QC_MAX_CHUNK_ROWS);
+    if (plan.big_row >= 0)
+        return nabo::api_fail(NABO_E_NOMEM, "row %lld alone needs %lld bytes of device buffers, the budget is %lld", (long long)plan.big_row,
+                              (long long)plan.big_bytes, (long long)budget);
+    const int64_t max_rows = plan.max_rows;
     g_qc_ms[0] = g_qc_ms[1] = g_qc_ms[2] = 0;
     g_qc_chunks = 0;
     if ((rc = nabo::use_device(device))) return rc;
     if (n_rows == 0) return NABO_OK;
 
     hipStream_t st = nullptr;
-    Events E;
-    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&E.ev[i]));
+    nabo::Events<4> E;
+    HIP_TRY(E.create());
     // the class table, padded with zeros to whole 16-byte pieces
     const size_t table_bytes = (size_t)((n_raw_genes + 15) / 16) * 16;
-    DevBuf d_table, d_ptr, d_gene, d_val, d_n, d_sums;
+    DevBuf d_table, d_n, d_sums;
+    nabo::RowChunk chunk{cell_ptr, gene, val, nullptr, rows};
     HIP_TRY(d_table.alloc(table_bytes));
-    HIP_TRY(d_ptr.alloc((size_t)(max_rows + 1) * 8));
-    HIP_TRY(d_gene.alloc((size_t)max_nnz * 4));
-    HIP_TRY(d_val.alloc((size_t)max_nnz * 4));
+    if ((rc = chunk.reserve(max_rows, plan.max_nnz))) return rc;
     HIP_TRY(d_n.alloc((size_t)max_rows * 8));
     HIP_TRY(d_sums.alloc((size_t)max_rows * NS * 8));
     if (n_classes > 0 && n_raw_genes > 0) {
@@ -242,63 +196,21 @@ int nabo_cell_qc(int32_t device, int64_t n_cells, int64_t n_raw_genes, const int
         HIP_TRY(hipMemcpyAsync(d_table.p, h_table.data(), table_bytes, hipMemcpyHostToDevice, st));
         HIP_TRY(hipEventRecord(E.ev[1], st));
         HIP_TRY(hipStreamSynchronize(st));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
-        g_qc_ms[0] += ms;
+        HIP_TRY(E.elapsed(0, 1, &g_qc_ms[0]));
     }
-    std::vector<int64_t> h_ptr((size_t)max_rows + 1);
-    std::vector<float> h_val;
-    std::vector<int32_t> h_gene;
-    if (rows) {
-        h_gene.resize((size_t)max_nnz);
-        h_val.resize((size_t)max_nnz);
-    }
-    for (size_t ch = 0; ch + 1 < chunk_start.size(); ++ch) {
-        const int64_t r0 = chunk_start[ch], r1 = chunk_start[ch + 1], nr = r1 - r0;
+    for (size_t ch = 0; ch + 1 < plan.start.size(); ++ch) {
+        const int64_t r0 = plan.start[ch], nr = plan.start[ch + 1] - r0;
         if (nr == 0) continue;
-        // the chunk's rows as one CSR: a slice of the caller's arrays without `rows`, gathered in output order with it
-        const int32_t *src_gene = gene;
-        const float *src_val = val;
-        int64_t nnz = 0;
-        h_ptr[0] = 0;
-        if (!rows) {
-            const int64_t e0 = cell_ptr[r0];
-            for (int64_t r = 0; r < nr; ++r) h_ptr[r + 1] = cell_ptr[r0 + r + 1] - e0;
-            nnz = h_ptr[nr];
-            src_gene = gene + e0;
-            src_val = val + e0;
-        } else {
-            for (int64_t r = 0; r < nr; ++r) {
-                const int64_t c = rows[r0 + r], a = cell_ptr[c], ne = cell_ptr[c + 1] - a;
-                if (ne) {
-                    memcpy(h_gene.data() + nnz, gene + a, (size_t)ne * 4);
-                    memcpy(h_val.data() + nnz, val + a, (size_t)ne * 4);
-                }
-                nnz += ne;
-                h_ptr[r + 1] = nnz;
-            }
-            src_gene = h_gene.data();
-            src_val = h_val.data();
-        }
-        HIP_TRY(hipEventRecord(E.ev[0], st));
-        HIP_TRY(hipMemcpyAsync(d_ptr.p, h_ptr.data(), (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, st));
-        if (nnz) {
-            HIP_TRY(hipMemcpyAsync(d_gene.p, src_gene, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_val.p, src_val, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-        }
+        if ((rc = chunk.upload(r0, nr, st, E.ev[0]))) return rc;
         HIP_TRY(hipEventRecord(E.ev[1], st));
-        HIP_TRY(nabo::cell_qc_launch(d_ptr.as<int64_t>(), d_gene.as<int32_t>(), d_val.as<float>(), nr, d_table.as<uint8_t>(), n_raw_genes,
-                                     n_classes, d_n.as<int64_t>(), d_sums.as<double>(), st));
+        HIP_TRY(nabo::cell_qc_launch(chunk.d_ptr.as<int64_t>(), chunk.d_gene.as<int32_t>(), chunk.d_val.as<float>(), nr, d_table.as<uint8_t>(),
+                                     n_raw_genes, n_classes, d_n.as<int64_t>(), d_sums.as<double>(), st));
         HIP_TRY(hipEventRecord(E.ev[2], st));
         HIP_TRY(hipMemcpyAsync(out_n_entries + r0, d_n.p, (size_t)nr * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(out_sums + r0 * NS, d_sums.p, (size_t)nr * NS * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(E.ev[3], st));
         HIP_TRY(hipStreamSynchronize(st));
-        for (int i = 0; i < 3; ++i) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, E.ev[i], E.ev[i + 1]));
-            g_qc_ms[i] += ms;
-        }
+        for (int i = 0; i < 3; ++i) HIP_TRY(E.elapsed(i, i + 1, &g_qc_ms[i]));
         ++g_qc_chunks;
     }
     return NABO_OK;

@@ -271,22 +271,17 @@ int nabo_classify_targets(int32_t device, int64_t n_ref, const int32_t *ref_clus
         HIP_TRY(hipMemcpyAsync(d_nbr.p, nbr, (size_t)E * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_w.p, w, (size_t)E * 8, hipMemcpyHostToDevice, st));
     }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    HIP_TRY(hipEventCreate(&ev0));
-    hipError_t e = hipEventCreate(&ev1);
-    if (e == hipSuccess) e = hipEventRecord(ev0, st);
-    if (e == hipSuccess)
-        e = nabo::classify_launch(d_cl.as<int32_t>(), n_clusters, n_targets, d_ptr.as<int64_t>(), d_nbr.as<int64_t>(), d_w.as<double>(),
+    nabo::Events<2> events;
+    HIP_TRY(events.create());
+    HIP_TRY(hipEventRecord(events.ev[0], st));
+    HIP_TRY(nabo::classify_launch(d_cl.as<int32_t>(), n_clusters, n_targets, d_ptr.as<int64_t>(), d_nbr.as<int64_t>(), d_w.as<double>(),
                                   weight_frac, min_degree, min_weight, l_nb.as<int32_t>(), l_wt.as<double>(), l_cl.as<int32_t>(),
                                   d_lab.as<int32_t>(), out_best ? d_best.as<double>() : nullptr, out_total ? d_tot.as<double>() : nullptr,
-                                  out_counts ? d_cnt.as<int64_t>() : nullptr, st);
-    if (e == hipSuccess) e = hipEventRecord(ev1, st);
-    if (e == hipSuccess) e = hipEventSynchronize(ev1);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
-    (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    HIP_TRY(e);
+                                  out_counts ? d_cnt.as<int64_t>() : nullptr, st));
+    HIP_TRY(hipEventRecord(events.ev[1], st));
+    HIP_TRY(hipEventSynchronize(events.ev[1]));
+    double ms = 0;
+    HIP_TRY(events.elapsed(0, 1, &ms));
     g_device_ms[0] = ms;
     if (n_targets) {
         HIP_TRY(hipMemcpyAsync(out_label, d_lab.p, (size_t)n_targets * 4, hipMemcpyDeviceToHost, st));

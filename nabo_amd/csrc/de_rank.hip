@@ -285,32 +285,12 @@ struct Csc {
     const float *val, *sf;
 };
 
+// one matrix of the test: the values are the products with the cells' size factors, and only those are checked
 int check_csc(const char *which, int64_t n_genes, const Csc &m)
 {
     if (m.n_cells < 0 || m.n_cells >= ((int64_t)1 << 31) - 1)
         return nabo::api_fail(NABO_E_INVALID, "%s: n_cells=%lld out of range [0, 2^31 - 1)", which, (long long)m.n_cells);
-    if (!m.gene_ptr) return nabo::api_fail(NABO_E_INVALID, "%s: gene_ptr is NULL", which);
-    if (m.gene_ptr[0] != 0) return nabo::api_fail(NABO_E_INVALID, "%s: gene_ptr[0] = %lld, must be 0", which, (long long)m.gene_ptr[0]);
-    for (int64_t g = 0; g < n_genes; ++g)
-        if (m.gene_ptr[g + 1] < m.gene_ptr[g]) return nabo::api_fail(NABO_E_INVALID, "%s: gene_ptr is not monotone at gene %lld", which, (long long)g);
-    if (m.gene_ptr[n_genes] > 0 && (!m.cell || !m.val)) return nabo::api_fail(NABO_E_INVALID, "%s: cell or val is NULL", which);
-    if (m.n_cells > 0 && !m.sf) return nabo::api_fail(NABO_E_INVALID, "%s: sf is NULL", which);
-    for (int64_t g = 0; g < n_genes; ++g) {
-        int64_t last = -1;
-        for (int64_t e = m.gene_ptr[g]; e < m.gene_ptr[g + 1]; ++e) {
-            const int64_t c = m.cell[e];
-            if (c < 0 || c >= m.n_cells)
-                return nabo::api_fail(NABO_E_INVALID, "%s: cell[%lld] = %lld is not a cell in [0, %lld)", which, (long long)e, (long long)c, (long long)m.n_cells);
-            if (c <= last)
-                return nabo::api_fail(NABO_E_INVALID, "%s: the cells of gene %lld are not strictly increasing at entry %lld", which, (long long)g, (long long)e);
-            last = c;
-            const float v = m.val[e] * m.sf[c];
-            if (!(v >= 0.0f) || std::isinf(v))
-                return nabo::api_fail(NABO_E_INVALID, "%s: the scaled value of entry %lld (gene %lld, cell %lld) is %g: values must be finite and >= 0",
-                                      which, (long long)e, (long long)g, (long long)c, (double)v);
-        }
-    }
-    return NABO_OK;
+    return nabo::check_sparse<nabo::SPARSE_SCALED>(which, "gene", "cell", n_genes, m.n_cells, m.gene_ptr, m.cell, m.val, m.sf, false);
 }
 
 // cell -> the sets of `role` it is a member of, one entry per membership (CSR by cell)
@@ -491,16 +471,8 @@ int nabo_de_test(int32_t device, int64_t n_genes, int64_t n_cells, const int64_t
         HIP_TRY(s->d_off.alloc((size_t)nnz * 4));
         HIP_TRY(s->d_gptr.alloc((size_t)(max_genes + 1) * 8));
     }
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t *ev;
-        ~EvGuard()
-        {
-            for (int i = 0; i < 4; ++i)
-                if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    } guard{ev};
-    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+    nabo::Events<4> E;
+    HIP_TRY(E.create());
     std::vector<int64_t> h_i64((size_t)max_out * 5);
     std::vector<double> h_f64((size_t)max_out * 3);
 
@@ -524,7 +496,7 @@ int nabo_de_test(int32_t device, int64_t n_genes, int64_t n_cells, const int64_t
         HIP_TRY(hipMemsetAsync(d_status.p, 0, (size_t)no * 4, st));
         HIP_TRY(hipMemsetAsync(d_i64.p, 0, (size_t)no * 5 * 8, st));
         HIP_TRY(hipMemsetAsync(d_f64.p, 0, (size_t)no * 3 * 8, st));
-        HIP_TRY(hipEventRecord(ev[0], st));
+        HIP_TRY(hipEventRecord(E.ev[0], st));
         HIP_TRY(nabo::de_expand_launch(A.d_cell.as<int32_t>(), A.d_val.as<float>(), nnz_side[0], A.d_gptr.as<int64_t>(), (int32_t)ng,
                                        A.d_sf.as<float>(), A.d_inv_ptr.as<int64_t>(), A.d_inv_set.as<int32_t>(), n_sets, A.d_cnt.as<uint32_t>(),
                                        A.d_off.as<uint32_t>(), d_temp.p, temp_bytes, d_keys_a.as<uint64_t>(), 0, st));
@@ -533,22 +505,18 @@ int nabo_de_test(int32_t device, int64_t n_genes, int64_t n_cells, const int64_t
                                            B.d_sf.as<float>(), B.d_inv_ptr.as<int64_t>(), B.d_inv_set.as<int32_t>(), n_sets, B.d_cnt.as<uint32_t>(),
                                            B.d_off.as<uint32_t>(), d_temp.p, temp_bytes, d_keys_a.as<uint64_t>(),
                                            A.keys_of_gene[g1] - A.keys_of_gene[g0], st));
-        HIP_TRY(hipEventRecord(ev[1], st));
+        HIP_TRY(hipEventRecord(E.ev[1], st));
         HIP_TRY(nabo::de_sort_launch(d_keys_a.as<uint64_t>(), d_keys_b.as<uint64_t>(), nk, n_seg, d_temp.p, temp_bytes, d_seg.as<int64_t>(), st));
-        HIP_TRY(hipEventRecord(ev[2], st));
+        HIP_TRY(hipEventRecord(E.ev[2], st));
         HIP_TRY(nabo::de_rank_launch(d_keys_b.as<uint64_t>(), d_seg.as<int64_t>(), n_sets, d_size.as<int64_t>(), n_pairs, d_pt.as<int32_t>(),
                                      d_pc.as<int32_t>(), ng, exp_frac_thresh, log2_fc_thresh, d_status.as<int32_t>(), d_i64.as<int64_t>(),
                                      d_f64.as<double>(), st));
-        HIP_TRY(hipEventRecord(ev[3], st));
+        HIP_TRY(hipEventRecord(E.ev[3], st));
         HIP_TRY(hipMemcpyAsync(out_status + g0 * n_pairs, d_status.p, (size_t)no * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(h_i64.data(), d_i64.p, (size_t)no * 5 * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(h_f64.data(), d_f64.p, (size_t)no * 3 * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        for (int i = 0; i < 3; ++i) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-            g_de_ms[i] += ms;
-        }
+        for (int i = 0; i < 3; ++i) HIP_TRY(E.elapsed(i, i + 1, &g_de_ms[i]));
         ++g_de_chunks;
         const size_t o0 = (size_t)(g0 * n_pairs), nb = (size_t)no;
         memcpy(out_nonzero_test + o0, h_i64.data(), nb * 8);

@@ -191,9 +191,7 @@ hipError_t pca_densify_launch(const int64_t *ptr, const int32_t *gene, const flo
 hipError_t pca_colsum_launch(const double *Y, int64_t n_rows, int Gp, double *partial, double *colsum, hipStream_t st);
 hipError_t pca_syrk_launch(const double *Y, int64_t n_rows_pad, int Gp, double *partial, double *acc, hipStream_t st);
 hipError_t pca_cov_finish_launch(const double *acc, int G, int64_t n, double *cov, hipStream_t st);
-// host checks the PCA entry points share, and what nabo_pca_last_device_ms reports (pca_project.hip)
-int pca_check_sparse(const char *major, const char *minor, int64_t n_major, int64_t n_minor, const int64_t *ptr, const int32_t *idx,
-                     const float *val, const float *sf, bool sf_by_major);
+// the host check the projection and the fit share, and what nabo_pca_last_device_ms reports (pca_project.hip)
 int pca_check_selection(int64_t n_raw_genes, const int32_t *gene_pos, int64_t G, const double *sigma, int64_t n_cells, int64_t n_rows,
                         const int64_t *rows);
 void pca_set_device_ms(const double ms[3], int64_t n_chunks);

@@ -889,20 +889,15 @@ int nabo_refgraph_set_levels(nabo_refgraph *g, int64_t n_sets, const int64_t *se
         HIP_TRY(hipMemcpyAsync(d_node.p, node.data(), (size_t)M * 4, hipMemcpyHostToDevice, g->st));
         HIP_TRY(hipMemcpyAsync(d_bit.p, bit.data(), (size_t)M, hipMemcpyHostToDevice, g->st));
     }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    struct EventPair {
-        hipEvent_t a, b;
-        ~EventPair() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-    } events{ev0, ev1};
+    nabo::Events<2> E;
+    HIP_TRY(E.create());
     int32_t *cur = g->cur.as<int32_t>(), *nxt_list = g->next_list.as<int32_t>();
     int64_t *cnt = g->counters.as<int64_t>();
     double device_ms = 0;
     for (int64_t s0 = 0; s0 < n_sets; s0 += 64) {
         const int64_t ns = std::min<int64_t>(64, n_sets - s0), m0 = set_ptr[s0], nm = set_ptr[s0 + ns] - m0;
         HIP_TRY(hipMemsetAsync(d_level.p, 0xFF, (size_t)ns * n * 4, g->st));
-        HIP_TRY(hipEventRecord(ev0, g->st));
+        HIP_TRY(hipEventRecord(E.ev[0], g->st));
         HIP_TRY(nabo::paths_seed_sets_launch(d_node.as<int32_t>() + m0, d_bit.as<uint8_t>() + m0, nm, n, g->visited.as<uint64_t>(),
                                              g->front.as<uint64_t>(), cur, g->touched.as<int32_t>(), cnt, d_level.as<int32_t>(), g->st));
         HIP_TRY(hipMemcpyAsync(g->host_counters, cnt + 3, 8, hipMemcpyDeviceToHost, g->st));
@@ -919,12 +914,10 @@ int nabo_refgraph_set_levels(nabo_refgraph *g, int64_t n_sets, const int64_t *se
             std::swap(cur, nxt_list);
         }
         HIP_TRY(nabo::paths_clear_launch(g->touched.as<int32_t>(), cnt, g->visited.as<uint64_t>(), g->front.as<uint64_t>(), g->st));
-        HIP_TRY(hipEventRecord(ev1, g->st));
+        HIP_TRY(hipEventRecord(E.ev[1], g->st));
         HIP_TRY(hipMemcpyAsync(out_level + s0 * n, d_level.p, (size_t)ns * n * 4, hipMemcpyDeviceToHost, g->st));
         HIP_TRY(hipStreamSynchronize(g->st));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-        device_ms += ms;
+        HIP_TRY(E.elapsed(0, 1, &device_ms));
     }
     nabo::cluster_set_device_ms(1, device_ms);
     return NABO_OK;

@@ -271,15 +271,6 @@ constexpr int64_t FIT_MAX_CHUNK_ROWS = (int64_t)1 << 30;
 
 thread_local double g_fit_phase_ms[3] = {0, 0, 0};
 
-struct FitEvents {
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~FitEvents()
-    {
-        for (int i = 0; i < 5; ++i)
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -297,7 +288,7 @@ int nabo_pca_cov(int32_t device, int64_t n_cells, int64_t n_raw_genes, const int
     if (!rows) n_rows = n_cells;
     if (n_rows < 2) return nabo::api_fail(NABO_E_INVALID, "n_rows=%lld: a covariance needs at least 2 rows", (long long)n_rows);
     if (!out_mean || !out_cov) return nabo::api_fail(NABO_E_INVALID, "an output array is NULL");
-    int rc = nabo::pca_check_sparse("cell", "gene", n_cells, n_raw_genes, cell_ptr, gene, val, sf, true);
+    int rc = nabo::check_sparse<nabo::SPARSE_RAW_AND_SCALED>(nullptr, "cell", "gene", n_cells, n_raw_genes, cell_ptr, gene, val, sf, true);
     if (rc) return rc;
     if ((rc = nabo::pca_check_selection(n_raw_genes, gene_pos, G, sigma, n_cells, n_rows, rows))) return rc;
     for (int64_t p = 0; p < G; ++p)
@@ -308,36 +299,16 @@ int nabo_pca_cov(int32_t device, int64_t n_cells, int64_t n_raw_genes, const int
     const int64_t T = nabo::pca_fit_tile(), nT = (G + T - 1) / T, Gp = nT * T;
     const int64_t n_tiles = nT * (nT + 1) / 2, splits = nabo::pca_fit_splits(n_tiles);
     const double fixed_d = (double)n_tiles * (double)(T * T * 8) * (double)(1 + splits) + (double)Gp * 8.0 * (double)nabo::pca_fit_sum_slices();
-    auto row_entries = [&](int64_t r) {
-        const int64_t c = rows ? rows[r] : r;
-        return cell_ptr[c + 1] - cell_ptr[c];
-    };
     if (fixed_d + (double)(12 + 8 * Gp) > (double)budget)
         return nabo::api_fail(NABO_E_NOMEM, "the accumulator and its partial tiles for %lld genes need %.0f bytes and one row %lld more, the budget is %lld",
                               (long long)G, fixed_d, (long long)(12 + 8 * Gp), (long long)budget);
     const int64_t fixed = (int64_t)fixed_d;        // exact: it is below the budget
-    const int64_t room = budget - fixed, per_row_fixed = 12 + 8 * Gp, PAD = nabo::pca_fit_row_pad();
-    std::vector<int64_t> chunk_start{0};
-    int64_t max_rows = 0, max_nnz = 0;
-    {
-        int64_t used = 0, nnz = 0;
-        for (int64_t r = 0; r < n_rows; ++r) {
-            const int64_t ne = row_entries(r), b = per_row_fixed + 8 * ne, r0 = chunk_start.back();
-            if (b > room)
-                return nabo::api_fail(NABO_E_NOMEM, "row %lld alone needs %lld bytes of device buffers beside %lld resident ones, the budget is %lld",
-                                      (long long)r, (long long)b, (long long)fixed, (long long)budget);
-            if (r > r0 && (used + b > room || r - r0 >= FIT_MAX_CHUNK_ROWS)) {
-                chunk_start.push_back(r);
-                used = nnz = 0;
-            }
-            used += b;
-            nnz += ne;
-            max_rows = r + 1 - chunk_start.back() > max_rows ? r + 1 - chunk_start.back() : max_rows;
-            max_nnz = nnz > max_nnz ? nnz : max_nnz;
-        }
-        chunk_start.push_back(n_rows);
-    }
-    const size_t n_chunks = chunk_start.size() - 1;
+    const int64_t PAD = nabo::pca_fit_row_pad();
+    const nabo::RowChunks plan = nabo::plan_row_chunks(n_rows, rows, cell_ptr, 12 + 8 * Gp, budget - fixed, FIT_MAX_CHUNK_ROWS);
+    if (plan.big_row >= 0)
+        return nabo::api_fail(NABO_E_NOMEM, "row %lld alone needs %lld bytes of device buffers beside %lld resident ones, the budget is %lld",
+                              (long long)plan.big_row, (long long)plan.big_bytes, (long long)fixed, (long long)budget);
+    const size_t n_chunks = plan.start.size() - 1;
     double ms3[3] = {0, 0, 0};
     g_fit_phase_ms[0] = g_fit_phase_ms[1] = g_fit_phase_ms[2] = 0;
     nabo::pca_set_device_ms(ms3, 0);
@@ -346,10 +317,11 @@ int nabo_pca_cov(int32_t device, int64_t n_cells, int64_t n_raw_genes, const int
     std::vector<double> fill((size_t)G), mean((size_t)G, 0.0);
     for (int64_t p = 0; p < G; ++p) fill[p] = (0.0 - mu[p]) / sigma[p];
     hipStream_t st = nullptr;
-    FitEvents E;
-    for (int i = 0; i < 5; ++i) HIP_TRY(hipEventCreate(&E.ev[i]));
-    const int64_t max_pad = (max_rows + PAD - 1) / PAD * PAD;
-    DevBuf d_pos, d_mu, d_sigma, d_fill, d_mean, d_colsum, d_sumpart, d_acc, d_part, d_ptr, d_gene, d_val, d_sf, d_y, d_cov;
+    nabo::Events<4> E;
+    HIP_TRY(E.create());
+    const int64_t max_pad = (plan.max_rows + PAD - 1) / PAD * PAD;
+    DevBuf d_pos, d_mu, d_sigma, d_fill, d_mean, d_colsum, d_sumpart, d_acc, d_part, d_y, d_cov;
+    nabo::RowChunk chunk{cell_ptr, gene, val, sf, rows};
     HIP_TRY(d_pos.alloc((size_t)n_raw_genes * 4));
     HIP_TRY(d_mu.alloc((size_t)G * 8));
     HIP_TRY(d_sigma.alloc((size_t)G * 8));
@@ -359,18 +331,9 @@ int nabo_pca_cov(int32_t device, int64_t n_cells, int64_t n_raw_genes, const int
     HIP_TRY(d_sumpart.alloc((size_t)Gp * 8 * nabo::pca_fit_sum_slices()));
     HIP_TRY(d_acc.alloc((size_t)(n_tiles * T * T * 8)));
     HIP_TRY(d_part.alloc((size_t)(n_tiles * T * T * 8 * splits)));
-    HIP_TRY(d_ptr.alloc((size_t)(max_rows + 1) * 8));
-    HIP_TRY(d_gene.alloc((size_t)max_nnz * 4));
-    HIP_TRY(d_val.alloc((size_t)max_nnz * 4));
-    HIP_TRY(d_sf.alloc((size_t)max_rows * 4));
+    if ((rc = chunk.reserve(plan.max_rows, plan.max_nnz))) return rc;
     HIP_TRY(d_y.alloc((size_t)(max_pad * Gp * 8)));
     HIP_TRY(d_cov.alloc((size_t)(G * G * 8)));
-    auto elapsed = [&](int a, int b, double *into) -> hipError_t {
-        float ms = 0;
-        hipError_t e = hipEventElapsedTime(&ms, E.ev[a], E.ev[b]);
-        if (e == hipSuccess) *into += ms;
-        return e;
-    };
     HIP_TRY(hipEventRecord(E.ev[0], st));
     if (n_raw_genes) HIP_TRY(hipMemcpyAsync(d_pos.p, gene_pos, (size_t)n_raw_genes * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_mu.p, mu, (size_t)G * 8, hipMemcpyHostToDevice, st));
@@ -381,62 +344,18 @@ int nabo_pca_cov(int32_t device, int64_t n_cells, int64_t n_raw_genes, const int
     HIP_TRY(hipMemsetAsync(d_acc.p, 0, (size_t)(n_tiles * T * T * 8), st));
     HIP_TRY(hipEventRecord(E.ev[1], st));
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(elapsed(0, 1, &ms3[0]));
+    HIP_TRY(E.elapsed(0, 1, &ms3[0]));
 
-    std::vector<int64_t> h_ptr((size_t)max_rows + 1);
-    std::vector<float> h_sf((size_t)max_rows), h_val;
-    std::vector<int32_t> h_gene;
-    if (rows) {
-        h_gene.resize((size_t)max_nnz);
-        h_val.resize((size_t)max_nnz);
-    }
-    // the chunk's rows as one CSR on the device: a slice of the caller's arrays without `rows`, gathered in order with it
-    auto upload = [&](int64_t r0, int64_t nr) -> int {
-        const int32_t *src_gene = gene;
-        const float *src_val = val;
-        int64_t nnz = 0;
-        h_ptr[0] = 0;
-        if (!rows) {
-            const int64_t e0 = cell_ptr[r0];
-            for (int64_t r = 0; r < nr; ++r) {
-                h_ptr[r + 1] = cell_ptr[r0 + r + 1] - e0;
-                h_sf[r] = sf[r0 + r];
-            }
-            nnz = h_ptr[nr];
-            src_gene = gene + e0;
-            src_val = val + e0;
-        } else {
-            for (int64_t r = 0; r < nr; ++r) {
-                const int64_t c = rows[r0 + r], a = cell_ptr[c], ne = cell_ptr[c + 1] - a;
-                if (ne) {
-                    memcpy(h_gene.data() + nnz, gene + a, (size_t)ne * 4);
-                    memcpy(h_val.data() + nnz, val + a, (size_t)ne * 4);
-                }
-                nnz += ne;
-                h_ptr[r + 1] = nnz;
-                h_sf[r] = sf[c];
-            }
-            src_gene = h_gene.data();
-            src_val = h_val.data();
-        }
-        HIP_TRY(hipMemcpyAsync(d_ptr.p, h_ptr.data(), (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_sf.p, h_sf.data(), (size_t)nr * 4, hipMemcpyHostToDevice, st));
-        if (nnz) {
-            HIP_TRY(hipMemcpyAsync(d_gene.p, src_gene, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_val.p, src_val, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-        }
-        return NABO_OK;
-    };
     // pass 0: the column sums of y; pass 1: the centred rows and their product.  A single chunk is uploaded once.
     for (int pass = 0; pass < 2; ++pass) {
         for (size_t ch = 0; ch < n_chunks; ++ch) {
-            const int64_t r0 = chunk_start[ch], nr = chunk_start[ch + 1] - r0, nr_pad = (nr + PAD - 1) / PAD * PAD;
+            const int64_t r0 = plan.start[ch], nr = plan.start[ch + 1] - r0, nr_pad = (nr + PAD - 1) / PAD * PAD;
             HIP_TRY(hipEventRecord(E.ev[0], st));
             if (pass == 0 || n_chunks > 1)
-                if ((rc = upload(r0, nr))) return rc;
+                if ((rc = chunk.upload(r0, nr, st))) return rc;
             HIP_TRY(hipEventRecord(E.ev[1], st));
-            HIP_TRY(nabo::pca_densify_launch(d_ptr.as<int64_t>(), d_gene.as<int32_t>(), d_val.as<float>(), d_sf.as<float>(), nr, nr_pad,
-                                             d_pos.as<int32_t>(), d_mu.as<double>(), d_sigma.as<double>(), d_fill.as<double>(), d_mean.as<double>(),
+            HIP_TRY(nabo::pca_densify_launch(chunk.d_ptr.as<int64_t>(), chunk.d_gene.as<int32_t>(), chunk.d_val.as<float>(), chunk.d_sf.as<float>(), nr,
+                                             nr_pad, d_pos.as<int32_t>(), d_mu.as<double>(), d_sigma.as<double>(), d_fill.as<double>(), d_mean.as<double>(),
                                              (int)G, (int)Gp, d_y.as<double>(), st));
             HIP_TRY(hipEventRecord(E.ev[2], st));
             if (pass == 0)
@@ -445,13 +364,13 @@ int nabo_pca_cov(int32_t device, int64_t n_cells, int64_t n_raw_genes, const int
                 HIP_TRY(nabo::pca_syrk_launch(d_y.as<double>(), nr_pad, (int)Gp, d_part.as<double>(), d_acc.as<double>(), st));
             HIP_TRY(hipEventRecord(E.ev[3], st));
             HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(elapsed(0, 1, &ms3[0]));
-            HIP_TRY(elapsed(1, 3, &ms3[1]));
+            HIP_TRY(E.elapsed(0, 1, &ms3[0]));
+            HIP_TRY(E.elapsed(1, 3, &ms3[1]));
             if (pass == 0) {
-                HIP_TRY(elapsed(1, 3, &g_fit_phase_ms[0]));
+                HIP_TRY(E.elapsed(1, 3, &g_fit_phase_ms[0]));
             } else {
-                HIP_TRY(elapsed(1, 2, &g_fit_phase_ms[1]));
-                HIP_TRY(elapsed(2, 3, &g_fit_phase_ms[2]));
+                HIP_TRY(E.elapsed(1, 2, &g_fit_phase_ms[1]));
+                HIP_TRY(E.elapsed(2, 3, &g_fit_phase_ms[2]));
             }
         }
         if (pass == 0) {
@@ -467,8 +386,8 @@ int nabo_pca_cov(int32_t device, int64_t n_cells, int64_t n_raw_genes, const int
             HIP_TRY(hipMemcpyAsync(d_fill.p, fill.data(), (size_t)G * 8, hipMemcpyHostToDevice, st));
             HIP_TRY(hipEventRecord(E.ev[2], st));
             HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(elapsed(0, 1, &ms3[2]));
-            HIP_TRY(elapsed(1, 2, &ms3[0]));
+            HIP_TRY(E.elapsed(0, 1, &ms3[2]));
+            HIP_TRY(E.elapsed(1, 2, &ms3[0]));
         }
     }
     HIP_TRY(hipEventRecord(E.ev[0], st));
@@ -477,9 +396,9 @@ int nabo_pca_cov(int32_t device, int64_t n_cells, int64_t n_raw_genes, const int
     HIP_TRY(hipMemcpyAsync(out_cov, d_cov.p, (size_t)(G * G * 8), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(E.ev[2], st));
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(elapsed(0, 1, &ms3[1]));
-    HIP_TRY(elapsed(0, 1, &g_fit_phase_ms[2]));
-    HIP_TRY(elapsed(1, 2, &ms3[2]));
+    HIP_TRY(E.elapsed(0, 1, &ms3[1]));
+    HIP_TRY(E.elapsed(0, 1, &g_fit_phase_ms[2]));
+    HIP_TRY(E.elapsed(1, 2, &ms3[2]));
     memcpy(out_mean, mean.data(), (size_t)G * 8);
     nabo::pca_set_device_ms(ms3, (int64_t)n_chunks);
     return NABO_OK;

@@ -187,33 +187,6 @@ hipError_t gene_stats_launch(const int64_t *gptr, const int32_t *cell, const flo
     return hipGetLastError();
 }
 
-// a compressed sparse matrix with `n_major` lists over `n_minor` indices: pointers, order, range, and the float32
-// products (the size factor belongs to the cell: the list for rows of cells, the index for columns of genes)
-int pca_check_sparse(const char *major, const char *minor, int64_t n_major, int64_t n_minor, const int64_t *ptr, const int32_t *idx,
-                     const float *val, const float *sf, bool sf_by_major)
-{
-    const int rc = check_csr_ptr(sf_by_major ? "cell_ptr" : "gene_ptr", major, n_major, ptr);
-    if (rc) return rc;
-    if (ptr[n_major] > 0 && (!idx || !val)) return api_fail(NABO_E_INVALID, "%s or val is NULL", minor);
-    if ((sf_by_major ? n_major : n_minor) > 0 && !sf) return api_fail(NABO_E_INVALID, "sf is NULL");
-    for (int64_t i = 0; i < n_major; ++i) {
-        int64_t last = -1;
-        for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) {
-            const int64_t j = idx[e];
-            if (j < 0 || j >= n_minor)
-                return api_fail(NABO_E_INVALID, "%s[%lld] = %lld is not a %s in [0, %lld)", minor, (long long)e, (long long)j, minor, (long long)n_minor);
-            if (j <= last)
-                return api_fail(NABO_E_INVALID, "the %ss of %s %lld are not strictly increasing at entry %lld", minor, major, (long long)i, (long long)e);
-            last = j;
-            const float v = val[e], x = v * sf[sf_by_major ? i : j];
-            if (!(v >= 0.0f) || std::isinf(v) || !(x >= 0.0f) || std::isinf(x))
-                return api_fail(NABO_E_INVALID, "entry %lld (%s %lld, %s %lld): value %g, scaled value %g: both must be finite and >= 0",
-                                (long long)e, major, (long long)i, minor, (long long)j, (double)v, (double)x);
-        }
-    }
-    return NABO_OK;
-}
-
 // gene_pos, sigma and rows of the projection and of the fit
 int pca_check_selection(int64_t n_raw_genes, const int32_t *gene_pos, int64_t G, const double *sigma, int64_t n_cells, int64_t n_rows,
                         const int64_t *rows)
@@ -228,10 +201,7 @@ int pca_check_selection(int64_t n_raw_genes, const int32_t *gene_pos, int64_t G,
     for (int64_t p = 0; p < G; ++p)
         if (!(sigma[p] > 0.0) || std::isinf(sigma[p]))
             return api_fail(NABO_E_INVALID, "sigma[%lld] = %g: must be finite and > 0", (long long)p, sigma[p]);
-    for (int64_t r = 0; rows && r < n_rows; ++r)
-        if (rows[r] < 0 || rows[r] >= n_cells)
-            return api_fail(NABO_E_INVALID, "rows[%lld] = %lld is not a cell in [0, %lld)", (long long)r, (long long)rows[r], (long long)n_cells);
-    return NABO_OK;
+    return check_rows(n_rows, rows, n_cells);
 }
 
 }  // namespace nabo
@@ -246,15 +216,6 @@ constexpr int64_t PCA_MAX_CHUNK_ITEMS = (int64_t)1 << 30;      // rows (genes) o
 
 thread_local double g_pca_ms[3] = {0, 0, 0};
 thread_local int64_t g_pca_chunks = 0;
-
-struct Events {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events()
-    {
-        for (int i = 0; i < 4; ++i)
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-    }
-};
 
 }  // namespace
 
@@ -283,7 +244,7 @@ int nabo_pca_project(int32_t device, int64_t n_cells, int64_t n_raw_genes, const
     if (!rows) n_rows = n_cells;
     if (n_rows < 0) return nabo::api_fail(NABO_E_INVALID, "n_rows=%lld is negative", (long long)n_rows);
     if (n_rows > 0 && !out_z) return nabo::api_fail(NABO_E_INVALID, "the output array is NULL");
-    int rc = nabo::pca_check_sparse("cell", "gene", n_cells, n_raw_genes, cell_ptr, gene, val, sf, true);
+    int rc = nabo::check_sparse<nabo::SPARSE_RAW_AND_SCALED>(nullptr, "cell", "gene", n_cells, n_raw_genes, cell_ptr, gene, val, sf, true);
     if (rc) return rc;
     if ((rc = nabo::pca_check_selection(n_raw_genes, gene_pos, G, sigma, n_cells, n_rows, rows))) return rc;
     for (int64_t p = 0; p < G; ++p)
@@ -294,29 +255,11 @@ int nabo_pca_project(int32_t device, int64_t n_cells, int64_t n_raw_genes, const
             return nabo::api_fail(NABO_E_INVALID, "components[%lld][%lld] = %g: must be finite", (long long)(i / G), (long long)(i % G), components[i]);
     // chunks of rows within the budget
     const int64_t budget = mem_budget_bytes > 0 ? mem_budget_bytes : PCA_DEFAULT_BUDGET;
-    const int64_t per_row_fixed = 12 + 8 * (int64_t)C;
-    auto row_entries = [&](int64_t r) {
-        const int64_t c = rows ? rows[r] : r;
-        return cell_ptr[c + 1] - cell_ptr[c];
-    };
-    std::vector<int64_t> chunk_start{0};
-    int64_t max_rows = 0, max_nnz = 0;
-    {
-        int64_t used = 0, nnz = 0;
-        for (int64_t r = 0; r < n_rows; ++r) {
-            const int64_t ne = row_entries(r), b = per_row_fixed + 8 * ne, r0 = chunk_start.back();
-            if (b > budget) return nabo::api_fail(NABO_E_NOMEM, "row %lld alone needs %lld bytes of device buffers, the budget is %lld", (long long)r, (long long)b, (long long)budget);
-            if (r > r0 && (used + b > budget || r - r0 >= PCA_MAX_CHUNK_ITEMS)) {
-                chunk_start.push_back(r);
-                used = nnz = 0;
-            }
-            used += b;
-            nnz += ne;
-            max_rows = r + 1 - chunk_start.back() > max_rows ? r + 1 - chunk_start.back() : max_rows;
-            max_nnz = nnz > max_nnz ? nnz : max_nnz;
-        }
-        chunk_start.push_back(n_rows);
-    }
+    const nabo::RowChunks plan = nabo::plan_row_chunks(n_rows, rows, cell_ptr, 12 + 8 * (int64_t)C, budget, PCA_MAX_CHUNK_ITEMS);
+    if (plan.big_row >= 0)
+        return nabo::api_fail(NABO_E_NOMEM, "row %lld alone needs %lld bytes of device buffers, the budget is %lld", (long long)plan.big_row,
+                              (long long)plan.big_bytes, (long long)budget);
+    const int64_t max_rows = plan.max_rows;
     g_pca_ms[0] = g_pca_ms[1] = g_pca_ms[2] = 0;
     g_pca_chunks = 0;
     if ((rc = nabo::use_device(device))) return rc;
@@ -335,17 +278,15 @@ int nabo_pca_project(int32_t device, int64_t n_cells, int64_t n_raw_genes, const
         bias[c] = acc;
     }
     hipStream_t st = nullptr;
-    Events E;
-    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&E.ev[i]));
-    DevBuf d_pos, d_sigma, d_bias, d_tt, d_ptr, d_gene, d_val, d_sf, d_z;
+    nabo::Events<4> E;
+    HIP_TRY(E.create());
+    DevBuf d_pos, d_sigma, d_bias, d_tt, d_z;
+    nabo::RowChunk chunk{cell_ptr, gene, val, sf, rows};
     HIP_TRY(d_pos.alloc((size_t)n_raw_genes * 4));
     HIP_TRY(d_sigma.alloc((size_t)G * 8));
     HIP_TRY(d_bias.alloc((size_t)C * 8));
     HIP_TRY(d_tt.alloc((size_t)G * C * 8));
-    HIP_TRY(d_ptr.alloc((size_t)(max_rows + 1) * 8));
-    HIP_TRY(d_gene.alloc((size_t)max_nnz * 4));
-    HIP_TRY(d_val.alloc((size_t)max_nnz * 4));
-    HIP_TRY(d_sf.alloc((size_t)max_rows * 4));
+    if ((rc = chunk.reserve(max_rows, plan.max_nnz))) return rc;
     HIP_TRY(d_z.alloc((size_t)max_rows * C * 8));
     HIP_TRY(hipEventRecord(E.ev[0], st));
     if (n_raw_genes) HIP_TRY(hipMemcpyAsync(d_pos.p, gene_pos, (size_t)n_raw_genes * 4, hipMemcpyHostToDevice, st));
@@ -354,68 +295,19 @@ int nabo_pca_project(int32_t device, int64_t n_cells, int64_t n_raw_genes, const
     HIP_TRY(hipMemcpyAsync(d_tt.p, tt.data(), (size_t)G * C * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(E.ev[1], st));
     HIP_TRY(hipStreamSynchronize(st));
-    {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
-        g_pca_ms[0] += ms;
-    }
-    std::vector<int64_t> h_ptr((size_t)max_rows + 1);
-    std::vector<float> h_sf((size_t)max_rows), h_val;
-    std::vector<int32_t> h_gene;
-    if (rows) {
-        h_gene.resize((size_t)max_nnz);
-        h_val.resize((size_t)max_nnz);
-    }
-    for (size_t ch = 0; ch + 1 < chunk_start.size(); ++ch) {
-        const int64_t r0 = chunk_start[ch], r1 = chunk_start[ch + 1], nr = r1 - r0;
+    HIP_TRY(E.elapsed(0, 1, &g_pca_ms[0]));
+    for (size_t ch = 0; ch + 1 < plan.start.size(); ++ch) {
+        const int64_t r0 = plan.start[ch], nr = plan.start[ch + 1] - r0;
         if (nr == 0) continue;
-        // the chunk's rows as one CSR: a slice of the caller's arrays without `rows`, gathered in output order with it
-        const int32_t *src_gene = gene;
-        const float *src_val = val;
-        int64_t nnz = 0;
-        h_ptr[0] = 0;
-        if (!rows) {
-            const int64_t e0 = cell_ptr[r0];
-            for (int64_t r = 0; r < nr; ++r) {
-                h_ptr[r + 1] = cell_ptr[r0 + r + 1] - e0;
-                h_sf[r] = sf[r0 + r];
-            }
-            nnz = h_ptr[nr];
-            src_gene = gene + e0;
-            src_val = val + e0;
-        } else {
-            for (int64_t r = 0; r < nr; ++r) {
-                const int64_t c = rows[r0 + r], a = cell_ptr[c], ne = cell_ptr[c + 1] - a;
-                if (ne) {
-                    memcpy(h_gene.data() + nnz, gene + a, (size_t)ne * 4);
-                    memcpy(h_val.data() + nnz, val + a, (size_t)ne * 4);
-                }
-                nnz += ne;
-                h_ptr[r + 1] = nnz;
-                h_sf[r] = sf[c];
-            }
-            src_gene = h_gene.data();
-            src_val = h_val.data();
-        }
-        HIP_TRY(hipEventRecord(E.ev[0], st));
-        HIP_TRY(hipMemcpyAsync(d_ptr.p, h_ptr.data(), (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_sf.p, h_sf.data(), (size_t)nr * 4, hipMemcpyHostToDevice, st));
-        if (nnz) {
-            HIP_TRY(hipMemcpyAsync(d_gene.p, src_gene, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_val.p, src_val, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-        }
+        if ((rc = chunk.upload(r0, nr, st, E.ev[0]))) return rc;
         HIP_TRY(hipEventRecord(E.ev[1], st));
-        HIP_TRY(nabo::pca_project_launch(d_ptr.as<int64_t>(), d_gene.as<int32_t>(), d_val.as<float>(), d_sf.as<float>(), nr, d_pos.as<int32_t>(),
-                                         d_sigma.as<double>(), d_bias.as<double>(), d_tt.as<double>(), C, d_z.as<double>(), st));
+        HIP_TRY(nabo::pca_project_launch(chunk.d_ptr.as<int64_t>(), chunk.d_gene.as<int32_t>(), chunk.d_val.as<float>(), chunk.d_sf.as<float>(), nr,
+                                         d_pos.as<int32_t>(), d_sigma.as<double>(), d_bias.as<double>(), d_tt.as<double>(), C, d_z.as<double>(), st));
         HIP_TRY(hipEventRecord(E.ev[2], st));
         HIP_TRY(hipMemcpyAsync(out_z + r0 * C, d_z.p, (size_t)nr * C * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(E.ev[3], st));
         HIP_TRY(hipStreamSynchronize(st));
-        for (int i = 0; i < 3; ++i) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, E.ev[i], E.ev[i + 1]));
-            g_pca_ms[i] += ms;
-        }
+        for (int i = 0; i < 3; ++i) HIP_TRY(E.elapsed(i, i + 1, &g_pca_ms[i]));
         ++g_pca_chunks;
     }
     return NABO_OK;
@@ -428,7 +320,7 @@ int nabo_gene_stats(int32_t device, int64_t n_genes, int64_t n_cells, const int6
     if (n_genes < 0 || n_genes >= ((int64_t)1 << 31) - 1) return nabo::api_fail(NABO_E_INVALID, "n_genes=%lld out of range [0, 2^31 - 1)", (long long)n_genes);
     if (n_cells < 0 || n_cells >= ((int64_t)1 << 31) - 1) return nabo::api_fail(NABO_E_INVALID, "n_cells=%lld out of range [0, 2^31 - 1)", (long long)n_cells);
     if (n_genes > 0 && (!out_ncells || !out_valid || !out_m || !out_nzm || !out_variance)) return nabo::api_fail(NABO_E_INVALID, "an output array is NULL");
-    int rc = nabo::pca_check_sparse("gene", "cell", n_genes, n_cells, gene_ptr, cell, val, sf, false);
+    int rc = nabo::check_sparse<nabo::SPARSE_RAW_AND_SCALED>(nullptr, "gene", "cell", n_genes, n_cells, gene_ptr, cell, val, sf, false);
     if (rc) return rc;
     std::vector<uint8_t> kept((size_t)n_cells, keep_cells ? 0 : 1);
     if (!keep_cells) n_keep = n_cells;
@@ -457,8 +349,8 @@ int nabo_gene_stats(int32_t device, int64_t n_genes, int64_t n_cells, const int6
     if (n_genes == 0) return NABO_OK;
 
     hipStream_t st = nullptr;
-    Events E;
-    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&E.ev[i]));
+    nabo::Events<2> E;
+    HIP_TRY(E.create());
     DevBuf d_sf, d_kept, d_keepg, d_gptr, d_cell, d_val, d_nc, d_valid, d_m, d_nzm, d_var;
     HIP_TRY(d_sf.alloc((size_t)n_cells * 4));
     HIP_TRY(d_kept.alloc((size_t)n_cells));
@@ -498,9 +390,7 @@ int nabo_gene_stats(int32_t device, int64_t n_genes, int64_t n_cells, const int6
         HIP_TRY(hipMemcpyAsync(out_nzm + g0, d_nzm.p, (size_t)ng * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(out_variance + g0, d_var.p, (size_t)ng * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
-        g_pca_ms[1] += ms;
+        HIP_TRY(E.elapsed(0, 1, &g_pca_ms[1]));
         ++g_pca_chunks;
     }
     return NABO_OK;

@@ -45,10 +45,10 @@ def synth(n_cells, n_genes, n_clusters, seed=7):
 
 
 def run_gpu(a):
-    from nabo_amd import _de
+    from nabo_amd import _de, _matrixio
     cols, sf, cluster = synth(a.cells, a.genes, a.clusters)
     ptr = np.concatenate([[0], np.cumsum([len(i) for i, _ in cols])]).astype(np.int64)
-    m = _de._csc((ptr, np.concatenate([i for i, _ in cols]), np.concatenate([v for _, v in cols]), sf), "bench")
+    m = _matrixio.csc((ptr, np.concatenate([i for i, _ in cols]), np.concatenate([v for _, v in cols]), sf), "bench")
     genes = ["G%d" % j for j in range(a.genes)]
     clusters = {"c%d_S" % i: int(c) + 1 for i, c in enumerate(cluster)}
     cell_idx = {"c%d" % i: i for i in range(a.cells)}

@@ -59,8 +59,8 @@ def tables(n_raw, n_sel, n_comps, seed=12):
 
 
 def run_gpu(a):
-    from nabo_amd import _de, _pca
-    m = _pca._csr(synth_csr(a.cells, a.raw_genes, a.density))
+    from nabo_amd import _matrixio, _pca
+    m = _matrixio.csr(synth_csr(a.cells, a.raw_genes, a.density))
     t = _pca._tables(*tables(a.raw_genes, a.genes, a.comps))
     nnz = int(m[1][-1])
     selected = int((t[0][m[2]] >= 0).sum())
@@ -82,7 +82,7 @@ def run_gpu(a):
     cell = np.repeat(np.arange(a.cells, dtype=np.int32), np.diff(m[1]))
     order = np.argsort(m[2], kind="stable")
     gene_ptr = np.concatenate([[0], np.cumsum(np.bincount(m[2], minlength=a.raw_genes))]).astype(np.int64)
-    csc = _de._csc((gene_ptr, cell[order], m[3][order], m[4]), "bench")
+    csc = _matrixio.csc((gene_ptr, cell[order], m[3][order], m[4]), "bench")
     del cell, order
     secs = []
     for r in range(a.repeats + 1):

@@ -36,8 +36,8 @@ PEAK_SOURCE = "AMD Instinct MI355X data sheet, peak FP64 matrix"
 
 
 def run_gpu(a):
-    from nabo_amd import _pca
-    m = _pca._csr(synth_csr(a.cells, a.raw_genes, a.density))
+    from nabo_amd import _matrixio, _pca
+    m = _matrixio.csr(synth_csr(a.cells, a.raw_genes, a.density))
     rng = np.random.default_rng(12)
     gene_pos = np.full(a.raw_genes, -1, dtype=np.int32)
     gene_pos[np.sort(rng.permutation(a.raw_genes)[:a.genes])] = rng.permutation(a.genes)

@@ -33,9 +33,9 @@ sys.path.insert(0, os.path.join(REPO, "tools"))
 
 def run_gpu(a):
     from bench_pca import synth_csr
-    from nabo_amd import _qc
+    from nabo_amd import _matrixio, _qc
     cell_ptr, gene, val, _ = synth_csr(a.cells, a.raw_genes, a.density)
-    m = _qc._csr3(cell_ptr, gene, val)
+    m = _matrixio.csr((cell_ptr, gene, val))
     cls = np.random.default_rng(5).integers(0, 1 << max(a.classes, 1), a.raw_genes).astype(np.uint8)
     nnz = int(m[0][-1])
     secs, ms, chunks = [], None, 0
