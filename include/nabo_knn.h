@@ -100,7 +100,14 @@ int nabo_index_destroy(nabo_index *ix);
  * NABO_E_UNSUPPORTED), "local_seeds" (tournament seeds of a one-split launch of the one-product pass from each row's own
  * bucket of the references, the nearest of "local_anchors" reference cells: 0 = off, 1 = where a gain was measured (long one-split launches on the 23-entry lists),
  * 2 = on every such launch), "local_anchors" (buckets, 0 = 64, at most 256) and "local_cap" (references kept per bucket,
- * 0 = 16384, at most 32768).  Unknown names: NABO_E_INVALID.
+ * 0 = 16384, at most 32768), "two_level" (the two-level stream of the one-product pass, 28 < g <= 59: targets and references
+ * streamed in bucket order, a tile's second operand step only where its first step's lower bound passes a threshold:
+ * 0 = off, 1 = on the launches that take local seeds by default, 2 = on every one-split launch of the 23-entry lists, also
+ * at g = 29, where the plain operands need one step only), "two_level_share" and "two_level_stretch" (its mode control: the
+ * share of completed tiles, percent, 0 = 25, a wave tolerates before it runs the two-step loop for a stretch of tiles,
+ * 0 = 64, doubled while the probes behind it fail).  When the two-level stream ran, nabo_index_last_kernel reports its
+ * tile counters behind the kernel's name: " [two-level tiles: one-step N, refetched N, two-step N]", summed over the waves.
+ * Unknown names: NABO_E_INVALID.
  * The library reads TWO environment variables, once, in nabo_index_create: NABO_L2_MODE = f32 | f16x3 (which Euclidean /
  * cosine filter runs first; default: the one-product pass) and NABO_CANBERRA_MODE = exact | swar | bits; the sharded
  * transport reads NABO_COMM_TIMEOUT_S and NABO_RCCL_LIB. */
@@ -184,8 +191,10 @@ int nabo_index_last_row_pass(const nabo_index *ix, uint8_t *out, int64_t m);
  * reference splits, [7] kept list entries, [8] emitted list length, [9] reference tiles per split, [10] / [11] tournament
  * tiles and tiles per group (0: no tournament), [12] workgroups resident at once, [13] workgroups launched in all,
  * [14] padded target rows, [15] operand steps of 16 slots, [16] always 0 (it described the launch cut into pieces, which
- * was removed), [17] buckets of the local tournament seeds when the main launch takes them (option "local_seeds"), else 0.  kernel (optional): the kernel's name as nabo_index_last_kernel reports it. */
-#define NABO_PLAN_FIELDS 18
+ * was removed), [17] buckets of the local tournament seeds when the main launch takes them (option "local_seeds"), else 0,
+ * [18] the two-level stream (option "two_level"): 2 the main launch takes it (a query of an index may still decide against it:
+ * its probe, or the memory of one that did), 1 the operands are in its slot order only, 0 neither.  kernel (optional): the kernel's name as nabo_index_last_kernel reports it. */
+#define NABO_PLAN_FIELDS 19
 int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t k, int32_t drop_first, int32_t n_cand,
                     int32_t n_cu, const char *l2_mode, const char *options, int64_t out[NABO_PLAN_FIELDS], char *kernel,
                     size_t kernel_len);

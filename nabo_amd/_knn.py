@@ -4,6 +4,7 @@
 Everything here runs on the GPU through libnabo_knn.so; there is no CPU path.
 """
 import ctypes as C
+import re
 
 import numpy as np
 
@@ -72,13 +73,13 @@ def knn_devices(X, Y, k, devices, metric=EUCLIDEAN, dist_factor=0.25, ref_mask=N
 
 PLAN_FIELDS = ("first_pass", "geometry", "rows_per_wg", "workgroups_main", "workgroups_tail", "splits", "splits_tail", "lkeep",
                "list_len", "tiles_per_split", "tournament_tiles", "tournament_group", "resident_workgroups", "workgroups",
-               "rows_padded", "operand_steps", "pieces", "local_seed_buckets")
+               "rows_padded", "operand_steps", "pieces", "local_seed_buckets", "two_level")
 
 
 def query_plan(n_ref, g, m, k, metric=EUCLIDEAN, drop_first=False, n_cand=0, n_cu=256, l2_mode=None, options=None):
     """What a Euclidean / cosine query of this shape would launch first (nabo_query_plan: no index, no device)."""
     out = (C.c_int64 * len(PLAN_FIELDS))()
-    kern = C.create_string_buffer(192)
+    kern = C.create_string_buffer(256)
     opts = ",".join("%s=%d" % (a, int(b)) for a, b in (options or {}).items())
     _lib.check(_lib.lib().nabo_query_plan(int(n_ref), int(g), int(metric), int(m), int(k), int(bool(drop_first)), int(n_cand),
                                           int(n_cu), l2_mode.encode() if l2_mode else None, opts.encode() if opts else None,
@@ -174,9 +175,14 @@ class KnnIndex:
         _lib.check(_lib.lib().nabo_index_last_stats(self._h, ms, cn))
         ps = (C.c_int64 * 3)()
         _lib.check(_lib.lib().nabo_index_last_passes(self._h, ps))
+        # the two-level stream's tile counters, summed over the waves of its launch (0 when the query did not take it): the
+        # library reports them behind the kernel's name
+        tl = re.search(r"\[two-level tiles: one-step (\d+), refetched (\d+), two-step (\d+)\]", self.last_kernel())
+        one, refetched, two = (int(v) for v in tl.groups()) if tl else (0, 0, 0)
         return {"ms_pack": ms[0], "ms_topk": ms[1], "ms_refine": ms[2], "ms_fallback": ms[3], "ms_total": ms[4],
                 "fallback_rows": int(cn[0]), "splits": int(cn[1]), "list_len": int(cn[2]), "workgroups": int(cn[3]),
-                "seeded_pass_rows": int(ps[0]), "second_pass_rows": int(ps[1]), "wide_list_rows": int(ps[2])}
+                "seeded_pass_rows": int(ps[0]), "second_pass_rows": int(ps[1]), "wide_list_rows": int(ps[2]),
+                "two_level_one_step_tiles": one, "two_level_refetched_tiles": refetched, "two_level_two_step_tiles": two}
 
     PASS_NAMES = ("one_product", "seeded", "second_filter", "wide_lists", "exact", "canberra_filter")
 
@@ -188,8 +194,8 @@ class KnnIndex:
 
     def last_kernel(self):
         """name of the dominant kernel the last query ran (which filter the launch logic picked)"""
-        buf = C.create_string_buffer(192)
-        _lib.check(_lib.lib().nabo_index_last_kernel(self._h, buf, 192))
+        buf = C.create_string_buffer(256)
+        _lib.check(_lib.lib().nabo_index_last_kernel(self._h, buf, 256))
         return buf.value.decode("ascii", "replace")
 
     def close(self):

@@ -101,6 +101,9 @@ int nabo_index_set_option(nabo_index *ix, const char *name, int64_t value)
         ix->shape.opt.order_flags = 0;
         return api_fail(NABO_E_UNSUPPORTED, "option '%s' (locality-ordered streaming, once in experiments builds only) was removed", name);
     }
+    const int kc1 = ix->shape.kc1;
+    shape_refresh(ix->shape);
+    if (ix->shape.kc1 != kc1) ix->ref.l2.packed_c1 = false;      // (the one-product operands have another number of steps now)
     return NABO_OK;
 }
 

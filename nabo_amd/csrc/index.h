@@ -40,6 +40,11 @@ struct Options {
     // local tournament seeds (local_seeds.hip): 0 off, 1 where the planner expects a gain (lseed_applies), 2 on every
     // one-split launch of the one-product pass; anchors (0: 64) and references kept per bucket (0: 16384) pinned for A/B runs
     int local_seeds = 1, local_anchors = 0, local_cap = 0;
+    // the two-level stream of the one-product pass (l2c_topk.hip; operands in the two-level slot order, l2c_slots.h): 0 off,
+    // 1 where local seeds apply by default and the slots fit, 2 on every one-split geometry-B launch of the first pass
+    // (switches the local seeds' buckets on at any size); refetch share (percent, 0: 25) and first two-step stretch
+    // (tiles, 0: 64) of the kernel's mode control pinned for A/B runs
+    int two_level = 1, two_level_share = 0, two_level_stretch = 0;
 };
 bool option_set(Options &o, const char *name, int64_t value);
 
@@ -104,6 +109,8 @@ struct L2Plan {
     bool use_h = false;                  // an f16 kernel runs (one-product or f16x3 operands); false: the fp32-MFMA filter
     bool use_1 = false;                  // one-product operands
     bool on_l2c = false;                 // ... on the l2c kernel (geo: its geometry)
+    bool slots2 = false;                 // ... in the two-level slot order (two_level_slots: a property of the index)
+    bool tl_main = false;                // the main launch streams bucket-ordered operands with the one-step loop (l2c_topk.hip)
     bool r1 = false;                     // fp32 filter: one row-block per wave
     int geo = -1, kcq = 0, cslack = 0;
     int rows_per_wg = 256, wg_per_cu = 1, lkeep_max = 32, lkeep = 16, want = 16;
@@ -117,6 +124,9 @@ inline int list_epl(const PassCtx &ctx, int kk, bool cand_mode) { return ((kk <=
 int plan_l2(const IndexShape &sh, const PassCtx &ctx, int64_t m, int k, int drop, bool cand_mode, L2Plan *P);
 // local tournament seeds (local_seeds.hip): anchors and references kept per bucket of an index of this shape (*C = 0: none),
 // and whether a launch of `rows` target rows over S reference splits takes its seeds from them
+// the one-product operands of an index of this shape are packed in the two-level slot order (l2c_slots.h)
+bool two_level_slots(const IndexShape &sh);
+void shape_refresh(IndexShape &sh);          // kc1 after a change of options (g = 29 under option two_level = 2)
 void lseed_params(const IndexShape &sh, int *C, int *cap);
 bool lseed_applies(const IndexShape &sh, const L2Plan &P, int S, int64_t rows);
 
@@ -166,6 +176,17 @@ struct nabo_index {
             double fscale = 1.0;           // power-of-two input scale of the fp32 path: max |y~| * fscale in (1/2, 1]
             nabo::DevBuf centre, ypk, ycpk, ycpk1, normmax;
             bool packed_f32 = false, packed_c16 = false, packed_c1 = false;
+            bool slots2 = false;             // the slot order ycpk1 was packed in (two_level_slots when it was packed)
+            // the two-level stream (ensure_local_seeds): ALL unmasked references in bucket order, ord_tiles tiles and two
+            // all-padding tiles behind them; yordmap [position] = reference index (0xFFFFFFFF: a padding cell).
+            // tl_verdict: whether this index's data takes the stream -- 0 not known (the next long query probes), 1 yes,
+            // 2 no (a probe said so, or the waves of a launch proper ran most of their tiles two-step): the queries stream
+            // the caller-order operands and the ordered copy is not built.  A HEURISTIC, and remembered across set_ref /
+            // set_mask -- the usual caller refreshes the same kind of data -- for TL_VERDICT_REPACKS repacks (tl_age)
+            nabo::DevBuf yord, yordmap;
+            int64_t ord_tiles = 0;
+            bool ord_built = false;
+            int tl_verdict = 0, tl_age = 0;
             // local tournament seeds (local_seeds.hip): the buckets' runs live BEHIND the one-product operands in ycpk1, from
             // tile ref_tiles_alloc on (local_room tiles: one address space for l2c_pre_kernel's tile ranges); anchors and the
             // unmasked references per bucket; built by ensure_local_seeds for (local_C, local_cap), stale after every repack
@@ -205,6 +226,7 @@ struct nabo_index {
         // local tournament seeds: the counting sort's keys, block counts, bucket totals and layout (shared by the reference
         // build and the queries: one stream); the bucket-ordered target tiles, their row map and the columns' ranges
         nabo::DevBuf lkey, lblk, ltot, llay, xpre, lmap, lranges;
+        nabo::DevBuf tlstats;                     // the two-level launch's tile counters [3] (l2c_topk.hip)
     } ws;
 
     // ---- the last query's record (the nabo_index_last_* getters) ----
@@ -216,7 +238,8 @@ struct nabo_index {
         std::vector<uint8_t> row_pass;
         double ms[5] = {0, 0, 0, 0, 0};
         int64_t counters[4] = {0, 0, 0, 0};
-        char kernel[160] = "";          // dominant kernel of the last query (nabo_index_last_kernel)
+        char kernel[256] = "";          // dominant kernel of the last query (nabo_index_last_kernel)
+        bool tl_ran = false;
     } last;
 
     // nabo_index_query_async: the query runs on a host thread of its own (it synchronises its stream between its passes);
@@ -229,6 +252,7 @@ struct nabo_index {
 
 namespace nabo {
 
+constexpr int TL_VERDICT_REPACKS = 16;       // repacks of the references a two-level verdict outlives (nabo_index::Refs::L2::tl_verdict)
 constexpr int RERUN_WIDE = 2;     // nabo_index::Workspace::rerun: the set of the frame that sends rows to the 64-entry lists
 
 // api.hip: NABO_OK, or the refusal while an asynchronous query is in flight on the index

@@ -28,6 +28,9 @@
 //   * the staging / drain code sits out of line behind that unlikely branch, the drain itself behind a real call;
 //   * every vector instruction next to the MFMAs costs its ~4 issue cycles whoever issues it (also a second wave of the
 //     same SIMD): what counts is the instruction COUNT -- two waves per SIMD (geometry B) hide latency, not issue.
+// The TWO-LEVEL stream (geometry B on two steps, operands in the slot order of l2c_slots.h, both sides bucket-ordered by
+// local_seeds.hip): the first step alone is a rigorous lower bound of the score, a tile gets its second
+// step only when one of its bounds passes a threshold -- 4 MFMAs per pair of row-blocks instead of 8 on 92 % of the tiles.
 #include <cstdio>
 #include <cstdlib>
 
@@ -166,6 +169,46 @@ __device__ __forceinline__ cmins cmin8x2(const cacc &acc)
                    BC(b1[0]), BC(b1[1]), BC(b1[2]), BC(b1[3]), \
                    "v"(old.v[1][1][0]), "v"(old.v[1][1][1]), "v"(old.v[1][1][2]), "v"(old.v[1][1][3]), \
                    "v"(m0), "v"(tau0), "v"(tau1));
+// ONE-STEP pair (the two-level stream, l2c_slots.h): the FIRST operand step alone -- four MFMAs from C = 0, a lower bound of
+// every score of the pair -- with the same ten filter instructions on the previous tile's bounds beside them (five behind
+// the first two MFMAs, five behind the last two).  Same rules as above: an accumulator is one quad from the MFMA that writes
+// it to its last reader a tile later, B operands in arch VGPRs (two waves per SIMD), nothing padded inside a statement.
+#define L2C_PAIR1_STATEMENTS \
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %4, %6, 0\n\t" \
+                 "v_min_f32 %2, %7, %8\n\t" \
+                 "v_min3_f32 %2, %2, %9, %10\n\t" \
+                 "v_min3_f32 %2, %2, %11, %12\n\t" \
+                 "v_mfma_f32_16x16x32_f16 %1, %5, %6, 0\n\t" \
+                 "v_min3_f32 %2, %2, %13, %14\n\t" \
+                 "v_min_f32 %3, %15, %16" \
+                 : "=&v"(r00), "=&v"(r01), "=&v"(m0), "=&v"(m1) \
+                 : "v"(a0s), "v"(a1s), "v"(b0s), \
+                   "v"(old.v[0][0][0]), "v"(old.v[0][0][1]), "v"(old.v[0][0][2]), "v"(old.v[0][0][3]), \
+                   "v"(old.v[0][1][0]), "v"(old.v[0][1][1]), "v"(old.v[0][1][2]), "v"(old.v[0][1][3]), \
+                   "v"(old.v[1][0][0]), "v"(old.v[1][0][1])); \
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %5, %7, 0\n\t" \
+                 "v_min3_f32 %4, %4, %8, %9\n\t" \
+                 "v_min3_f32 %4, %4, %10, %11\n\t" \
+                 "v_min3_f32 %4, %4, %12, %13\n\t" \
+                 "v_mfma_f32_16x16x32_f16 %1, %6, %7, 0\n\t" \
+                 "v_cmp_lt_f32_e64 %2, %14, %15\n\t" \
+                 "v_cmp_lt_f32_e64 %3, %4, %16" \
+                 : "=&v"(r10), "=&v"(r11), "=&s"(h0), "=&s"(h1), "+v"(m1) \
+                 : "v"(a0s), "v"(a1s), "v"(b1s), \
+                   "v"(old.v[1][0][2]), "v"(old.v[1][0][3]), \
+                   "v"(old.v[1][1][0]), "v"(old.v[1][1][1]), "v"(old.v[1][1][2]), "v"(old.v[1][1][3]), \
+                   "v"(m0), "v"(tau0), "v"(tau1));
+// a0s / a1s: the tile's step-0 registers (reference halves), b0s / b1s: the two row-blocks' step-0 registers
+__device__ __forceinline__ void cpair1(const f16x8 &a0s, const f16x8 &a1s, const f16x8 &b0s, const f16x8 &b1s, cacc &cur,
+                                       const cacc &old, float tau0, float tau1, uint64_t &hit)
+{
+    float m0, m1;
+    uint64_t h0, h1;
+    f32x4 &r00 = cur.v[0][0], &r01 = cur.v[0][1], &r10 = cur.v[1][0], &r11 = cur.v[1][1];
+    L2C_PAIR1_STATEMENTS
+    hit = h0 | h1;
+}
+
 template <int KS, bool BAGPR>
 __device__ __forceinline__ void cpair(const f16x8 (&a)[2][KS], const f16x8 (&b0)[KS], const f16x8 (&b1)[KS], cacc &cur,
                                       const cacc &old, float tau0, float tau1, cmins &mm, uint64_t &hit)
@@ -238,7 +281,11 @@ __device__ __forceinline__ void cstage2(const cacc &acc, const cmins &m, int p, 
     const bool h0 = m.m0 < tauv[2 * p], h1 = m.m1 < tauv[2 * p + 1];
     const uint64_t b0 = __builtin_amdgcn_ballot_w64(h0), b1 = __builtin_amdgcn_ballot_w64(h1);
     const uint32_t n0 = (uint32_t)__builtin_popcountll(b0), n = n0 + (uint32_t)__builtin_popcountll(b1);
-    const uint32_t row = (uint32_t)(2 * p * C::RPB + (lane_id() & (C::RPB - 1)));
+    // (the lane id through an empty assembly statement: what derives from it is computed HERE, on the rare path, instead of
+    // being hoisted out of the tile loop as one more register that lives through the whole kernel, per site)
+    int lid = lane_id();
+    asm volatile("" : "+v"(lid));
+    const uint32_t row = (uint32_t)(2 * p * C::RPB + (lid & (C::RPB - 1)));
     if (__builtin_expect(scnt + n <= (uint32_t)NREC, 1)) {
         if (h0) {
             const uint32_t q = scnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0u));
@@ -279,8 +326,19 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                                                           float *__restrict__ cand_key,
                                                           float *__restrict__ cand_tau, int64_t pad_tile, int dbg_arg,
                                                           int64_t rows_valid, const float *__restrict__ tau_init,
-                                                          int tau_stride, int64_t tau_row0)
+                                                          int tau_stride, int64_t tau_row0,
+                                                          const uint32_t *__restrict__ row_map,
+                                                          const uint32_t *__restrict__ ref_map,
+                                                          unsigned long long *__restrict__ tl_stats, int tl_share,
+                                                          int tl_stretch)
 {
+    // TWO-LEVEL stream (geometry B on two operand steps; row_map != null selects it at run time, every other launch of this
+    // instantiation runs the plain loop below): operands in the two-level slot order (l2c_slots.h), targets AND references
+    // bucket-ordered copies (local_seeds.hip).  A tile's first operand step alone bounds its scores from below, and between
+    // rows and references of different regions of the data the bound already fails every threshold: such a tile costs 4
+    // MFMAs per pair of row-blocks and half its bytes.  Only when some bound of a tile passes does the wave fetch the tile's
+    // second step, finish the scores on the bounds (the accumulators are the C operands) and filter those (`complete`).
+    constexpr bool TL = KS == 2 && WPS == 2;
     // dbg: the run-time switch of timing ablations that are gone; every launch passes 0.  The four-step kernel on the
     // 64-entry lists keeps it a RUN-TIME value, never-taken selects and all: that one instantiation runs 16 % faster with
     // them than with them folded away (cosine 1M x 1M, d = 100, k = 50, same box: 308 against 365 ms; no such effect, or
@@ -334,16 +392,45 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
     auto seed_of = [&](int64_t r) -> float {
         return tau_stride ? tau_init[(r - tau_row0) * tau_stride + split] : tau_init[r];
     };
+    // (ordered targets: position r of the copy is the launch's row row_map[r], which indexes the seeds; -1: padding)
+    const bool ordered = TL && row_map != nullptr;
+    auto ordered_row = [&](int64_t r) -> int64_t {
+        const uint32_t v = row_map[r];
+        return v == 0xFFFFFFFFu ? -1 : (int64_t)v;
+    };
 #pragma unroll
     for (int rb = 0; rb < NB; ++rb) {
         const int64_t r = row0 + rb * 16 + (lane & 15);
-        tauv[rb] = r < rows_valid ? ((tau_init && !(dbg & 1)) ? seed_of(r) : tau0) : -__builtin_inff();
+        if (ordered) {
+            const int64_t src = ordered_row(r);
+            tauv[rb] = src >= 0 ? (tau_init ? tau_init[src * tau_stride + split] : tau0) : -__builtin_inff();
+        } else {
+            tauv[rb] = r < rows_valid ? ((tau_init && !(dbg & 1)) ? seed_of(r) : tau0) : -__builtin_inff();
+        }
+    }
+    if (ordered) {      // a wave of padding positions only (every bucket's rows end in some): nothing to find, nothing to emit
+        bool live = false;
+#pragma unroll
+        for (int rb = 0; rb < NB; ++rb) live = live || tauv[rb] > -__builtin_inff();
+        if (__builtin_amdgcn_ballot_w64(live) == 0) return;
     }
     uint32_t scnt = 0;
     const int t_begin = split * tiles_per_split;
     const int t_end = t_begin + tiles_per_split;
     lists_init<C>(wl, lkeep, tau0, (uint32_t)t_begin * 32u);
-    {
+    if (ordered) {
+        uint2 *rows = C::rows(wl);
+        for (int r = lane; r < C::NROWS; r += 64) {
+            const int64_t src = ordered_row(row0 + r);
+            if (src < 0) C::tauL(wl)[r] = -__builtin_inff();
+            else if (tau_init) C::tauL(wl)[r] = tau_init[src * tau_stride + split];
+        }
+        for (int e = lane; tau_init && e < C::NROWS * lkeep; e += 64) {
+            const int r = e / lkeep, sl = e - r * lkeep;
+            const int64_t src = ordered_row(row0 + r);
+            if (src >= 0) rows[r * C::ROW + sl].y = __float_as_uint(tau_init[src * tau_stride + split]);
+        }
+    } else {
         const int64_t nv = rows_valid - row0;            // valid rows of this wave
         if (nv < C::NROWS)
             for (int r = lane; r < C::NROWS; r += 64)
@@ -447,6 +534,144 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
     // ring-of-four geometry: cosine 1M x 1M, d = 100, k = 50: kernel 425 -> 318 ms.
     __builtin_amdgcn_s_waitcnt(0x0F70);
     int t = t_begin;
+    if constexpr (TL) {
+        {
+            // ---- the two-level stream (a launch without it is ONE two-step stretch over the whole split) -------------------
+            // the pending tile's scores (complete ones) through the filter, as the code behind the plain loop does
+            auto flush_pending = [&](const cacc(&acc)[NP], int tl) {
+                const uint32_t jb = (uint32_t)(tl * 32 + 4 * lq);
+                bool drained = false;
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    const cmins m = cmin8x2(acc[p]);
+                    cstage2<C, NB, NREC>(acc[p], m, p, jb, wl, scnt, lkeep, tauv, drained);
+                }
+                if (drained) {
+#pragma unroll
+                    for (int rb = 0; rb < NB; ++rb) tauv[rb] = C::tauL(wl)[rb * C::RPB + (lane & (C::RPB - 1))];
+                }
+            };
+            // The wait states between inline-assembly MFMAs and the first instruction of hipcc's that reads their results (12
+            // for this shape), with the accumulators as operands of the pad: a reader cannot be scheduled above it.
+            static_assert(NP == 3, "geometry B: three pairs of row-blocks");
+            auto pad_acc = [&](cacc(&acc)[NP]) {
+                asm volatile("s_nop 15\n\ts_nop 15"
+                             : "+v"(acc[0].v[0][0]), "+v"(acc[0].v[0][1]), "+v"(acc[0].v[1][0]), "+v"(acc[0].v[1][1]),
+                               "+v"(acc[1].v[0][0]), "+v"(acc[1].v[0][1]), "+v"(acc[1].v[1][0]), "+v"(acc[1].v[1][1]),
+                               "+v"(acc[2].v[0][0]), "+v"(acc[2].v[0][1]), "+v"(acc[2].v[1][0]), "+v"(acc[2].v[1][1])
+                             :
+                             : "memory");
+            };
+            // tile ts's bounds -> its scores: the second operand step on top of the accumulators, in place (inline assembly
+            // like every MFMA of this kernel: an accumulator stays ONE quad; the pad behind them is the 12 wait states
+            // their first reader needs)
+            auto complete = [&](cacc(&acc)[NP], int ts) {
+                const f16x8 *tp = reinterpret_cast<const f16x8 *>(tile_ptr(ts));
+                const f16x8 s0 = tp[(0 * KS + 1) * 64 + lane], s1 = tp[(1 * KS + 1) * 64 + lane];
+#pragma unroll
+                for (int p = 0; p < NP; ++p)
+                    asm volatile("v_mfma_f32_16x16x32_f16 %0, %4, %6, %0\n\t"
+                                 "v_mfma_f32_16x16x32_f16 %1, %5, %6, %1\n\t"
+                                 "v_mfma_f32_16x16x32_f16 %2, %4, %7, %2\n\t"
+                                 "v_mfma_f32_16x16x32_f16 %3, %5, %7, %3"
+                                 : "+v"(acc[p].v[0][0]), "+v"(acc[p].v[0][1]), "+v"(acc[p].v[1][0]), "+v"(acc[p].v[1][1])
+                                 : "v"(s0), "v"(s1), "v"(xb[2 * p][1]), "v"(xb[2 * p + 1][1]));
+                pad_acc(acc);
+            };
+            auto reset = [&](cacc(&acc)[NP]) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p)
+#pragma unroll
+                    for (int r = 0; r < 2; ++r)
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) acc[p].v[r][h] = f32x4{__builtin_inff(), __builtin_inff(), __builtin_inff(), __builtin_inff()};
+            };
+            // MODE CONTROL, wave-uniform, in scalar registers, and outside the hot path: a refetch costs a memory round trip
+            // and twelve MFMAs out of line, so the one-step loop pays while fewer than `share` percent of its tiles need one
+            // (a one-step tile is 104 SIMD cycles per pair against 168).  A leaky bucket in the refetch path keeps the
+            // account -- every refetch takes 100, every tile of the segment gives `share`, TL_BURST refetches of credit --
+            // and when it is overdrawn the wave leaves for a stretch of the plain two-step loop, then probes again; the
+            // stretch doubles while the probes fail (a probe that lasted fewer than TL_PROBE tiles) and starts over after
+            // one that held.  Unclustered data pays the probes only.
+            constexpr int TL_BURST = 8, TL_PROBE = 64;
+            const int share = tl_share > 0 ? tl_share : 25;
+            const int stretch0 = tl_stretch > 0 ? ((tl_stretch < (1 << 20) ? tl_stretch : 1 << 20) + 1) & ~1 : 64;
+            int stretch = ordered ? stretch0 : 1 << 30;
+            uint32_t n_one = 0, n_ref = 0, n_two = 0;
+            int seg_end = 0, seg_t0 = 0, seg_ref = 0;
+            // A tile's second step is fetched ON DEMAND, not kept in the ring's idle registers: 16 waves of a CU that load
+            // whole tiles at the one-step loop's rate ask more of the CU's vector cache than it delivers (4 KB per tile and
+            // wave against ~100 SIMD cycles per pair of row-blocks) -- with every tile loaded whole the step took 143 ms
+            // where the parent takes 91 and this loop 83 (1M x 1M, d = 50, 7.7 % of the tiles completed).
+            auto tile_load1 = [&](f16x8(&a)[2][KS], int ts) {
+                const f16x8 *p = reinterpret_cast<const f16x8 *>(tile_ptr(ts));
+                a[0][0] = p[(0 * KS + 0) * 64 + lane];
+                a[1][0] = p[(1 * KS + 0) * 64 + lane];
+            };
+            // bounds of tile t into `cur`, filter of tile t - 1's bounds (`old`) beside them; a passing bound: refetch
+            auto tile_step1 = [&](const f16x8(&a)[2][KS], f16x8(&an)[2][KS], cacc(&cur)[NP], cacc(&old)[NP], int t) {
+                tile_load1(an, t + 1);
+                uint64_t hit[NP];
+#pragma unroll
+                for (int p = 0; p < NP; ++p)
+                    cpair1(a[0][0], a[1][0], xb[2 * p][0], xb[2 * p + 1][0], cur[p], old[p], tauv[2 * p], tauv[2 * p + 1], hit[p]);
+                uint64_t any = hit[0];
+#pragma unroll
+                for (int p = 1; p < NP; ++p) any |= hit[p];
+                if (__builtin_expect(any != 0, 0)) {
+                    // (hipcc does not know the inline-assembly MFMAs' latency: nothing it places here may come within 12
+                    // wait states of them -- `old` itself is a tile old)
+                    __builtin_amdgcn_s_setprio(3);
+                    complete(old, t - 1);
+                    flush_pending(old, t - 1);
+                    __builtin_amdgcn_s_setprio(0);
+                    ++seg_ref;
+                    if (seg_ref * 100 > TL_BURST * 100 + share * (t - seg_t0)) seg_end = 0;      // overdrawn: leave after this pair of tiles
+                }
+            };
+            // Segments alternate; each ends with its last tile pending in accO -- bounds after a one-step segment (completed
+            // here), scores after a two-step stretch -- and ONE filter site takes it, so that the next segment starts from
+            // +inf accumulators like the kernel does.
+            bool one_step = ordered;
+            while (t < t_end) {
+                seg_t0 = t;
+                if (one_step) {
+                    seg_ref = 0;
+                    seg_end = t_end;
+                    tile_load1(a0, t);
+                    for (; t < seg_end; t += 2) {
+                        tile_step1(a0, a1, accE, accO, t);
+                        tile_step1(a1, a0, accO, accE, t + 1);
+                    }
+                    pad_acc(accO);
+                    complete(accO, t - 1);
+                    n_one += (uint32_t)(t - seg_t0);
+                    n_ref += (uint32_t)seg_ref;       // (refetches of the loop only: the segment's last tile is completed whatever its bounds say)
+                    if (t - seg_t0 >= TL_PROBE) stretch = stretch0;       // the probe held
+                } else {
+                    const int t2_end = stretch < t_end - t ? t + stretch : t_end;
+                    if (stretch < (1 << 24)) stretch *= 2;
+                    if (ordered) tile_load(a0, t);      // (a plain launch: its one stretch starts on the preamble's tile)
+                    for (; t < t2_end; t += 2) {
+                        tile_step(a0, a1, accE, accO, t);
+                        tile_step(a1, a0, accO, accE, t + 1);
+                    }
+                    pad_acc(accO);
+                    n_two += (uint32_t)(t - seg_t0);
+                }
+                flush_pending(accO, t - 1);
+                reset(accO);
+                one_step = !one_step;
+            }
+            if (tl_stats && lane == 0) {
+                atomicAdd(tl_stats, (unsigned long long)n_one);
+                atomicAdd(tl_stats + 1, (unsigned long long)n_ref);
+                atomicAdd(tl_stats + 2, (unsigned long long)n_two);
+            }
+            lists_flush<C, EPL, NB>(wl, scnt, ltile0 * 32, split, S, lkeep, tauv, cand_idx, cand_key, cand_tau, row_map, ref_map);
+            return;
+        }
+    }
     if (RING == 4) {
         for (; t < t_end; t += 4) {
             tile_step(a0, a3, accE, accO, t);
@@ -650,7 +875,7 @@ template <int KS, int EPL, int ROWN, int NBv, int NRECv, int WAVES, int WPS>
 static hipError_t claunch_geo(const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S, int gx,
                               int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
                               int64_t pad_tile, hipStream_t st, int64_t rows_valid, const float *tau_init, int tau_stride,
-                              int64_t tau_row0)
+                              int64_t tau_row0, const L2cOrdered *ord)
 {
     constexpr size_t lds = (size_t)WAVES * ListCfg<EPL, ROWN, NBv, NRECv, 16, (ROWN >= 64)>::BYTES;
     static_assert(lds <= 163840, "LDS budget");
@@ -660,7 +885,8 @@ static hipError_t claunch_geo(const unsigned char *Xpk, const unsigned char *Ypk
     dim3 block(64 * WAVES);
     hipLaunchKernelGGL((l2c_topk_kernel<KS, EPL, ROWN, NBv, NRECv, WAVES, WPS>), dim3(gx, S), block, lds, st, Xpk, Ypk,
                        tiles_per_split, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, 0, rows_valid, tau_init, tau_stride,
-                       tau_row0);
+                       tau_row0, ord ? ord->row_map : nullptr, ord ? ord->ref_map : nullptr, ord ? ord->stats : nullptr,
+                       ord ? ord->share_pct : 0, ord ? ord->stretch : 0);
     return hipGetLastError();
 }
 
@@ -668,18 +894,18 @@ template <int KS>
 static hipError_t claunch_one(int geo, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S, int gx,
                               int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
                               int64_t pad_tile, hipStream_t st, int64_t rows_valid, const float *tau_init, int tau_stride,
-                              int64_t tau_row0)
+                              int64_t tau_row0, const L2cOrdered *ord)
 {
     if constexpr (KS <= 2) {
         if (geo == 1)
             return claunch_geo<KS, 1, L2C_ROW_B, 6, L2C_NREC_B, 4, 2>(Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx,
-                                                                  cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
+                                                                  cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, ord);
     }
     if (geo == 2)
         return claunch_geo<KS, 2, L2C_ROW_C, 4, L2C_NREC, 4, 1>(Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key,
-                                                            cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
+                                                            cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, ord);
     return claunch_geo<KS, 1, L2C_ROW, 8, L2C_NREC, 4, 1>(Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau,
-                                                      pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
+                                                      pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, ord);
 }
 
 // Which geometry serves lists of `lkeep_want` kept entries: 1 = B (two waves per SIMD) up to 23 entries and KS <= 2 (its
@@ -716,16 +942,20 @@ int l2c_pick_kc(int g)
 hipError_t l2c_topk_launch(int kc, int geo, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
                            int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
                            int64_t pad_tile, hipStream_t st, int64_t rows_valid, const float *tau_init, int tau_stride,
-                           int64_t tau_row0)
+                           int64_t tau_row0, const L2cOrdered *ord)
 {
     if ((int64_t)tiles_per_split * 32 >= NABO_LIST_SPLIT_REFS) return hipErrorInvalidValue;   // topk_lists.h: 25 bits of offset per entry
+    // the two-level stream: geometry B on two operand steps, one split, both maps, seeds indexed [row][1]
+    if (ord && (geo != 1 || kc != 4 || S != 1 || !ord->row_map || !ord->ref_map || tile_off != 0 || (tiles_per_split & 1) ||
+                (tau_init && tau_stride != 1)))
+        return hipErrorInvalidValue;
     if (geo < 0 || geo > 2 || (geo == 1 && (kc > 4 || lkeep > L2C_ROW_B)) || (geo == 0 && lkeep > 32) || lkeep > 64)
         return hipErrorInvalidValue;
     switch (kc) {
-    case 2: return claunch_one<1>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
-    case 4: return claunch_one<2>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
-    case 6: return claunch_one<3>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
-    case 8: return claunch_one<4>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0);
+    case 2: return claunch_one<1>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, ord);
+    case 4: return claunch_one<2>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, ord);
+    case 6: return claunch_one<3>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, ord);
+    case 8: return claunch_one<4>(geo, Xpk, Ypk, tiles_per_split, S, gx, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, st, rows_valid, tau_init, tau_stride, tau_row0, ord);
     default: return hipErrorInvalidValue;
     }
 }

@@ -53,14 +53,25 @@ hipError_t l2q_topk_launch(int kc, const unsigned char *Xpk, const unsigned char
                            int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
                            int64_t pad_tile, hipStream_t st);
 void l2q_topk_geometry(int kc, int *rows_per_wg, int *wg_per_cu, int *lkeep_max);
-// the one-product first pass (l2c_topk.hip; operands packed with layout16, nseg = 1)
+// the one-product first pass (l2c_topk.hip; operands packed with layout16, nseg = 1 or 2)
+// A TWO-LEVEL launch (geometry B, two steps, operands in the two-level slot order): targets and references are bucket-ordered
+// copies -- position p of the targets is the launch's row row_map[p] (0xFFFFFFFF: padding), position j of the stream is
+// reference ref_map[j]; lists and seeds are indexed by the launch's rows, emitted candidates are reference indices.
+// stats [3] (may be null): tiles run one-step, tiles of those refetched inside the loop (a segment's last tile, completed
+// unconditionally, is not counted), tiles run two-step, summed over the waves.
+// share_pct / stretch: the mode control's refetch share and first two-step stretch (0: the kernel's defaults).
+struct L2cOrdered {
+    const uint32_t *row_map, *ref_map;
+    unsigned long long *stats;
+    int share_pct, stretch;
+};
 int l2c_pick_kc(int g);
 int l2c_geometry(int kc, int lkeep_want, int pin);
 void l2c_topk_geometry(int kc, int lkeep_want, int pin, int *rows_per_wg, int *wg_per_cu, int *lkeep_max);
 hipError_t l2c_topk_launch(int kc, int geo, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
                            int gx, int64_t tile_off, int lkeep, uint32_t *cand_idx, float *cand_key, float *cand_tau,
                            int64_t pad_tile, hipStream_t st, int64_t rows_valid, const float *tau_init, int tau_stride = 0,
-                           int64_t tau_row0 = 0);
+                           int64_t tau_row0 = 0, const struct L2cOrdered *ord = nullptr);
 // tournament seeds for the one-product pass (l2c_topk.hip: l2c_pre_kernel)
 void l2c_pre_plan(int kc, int lkeep, int tiles_per_split, int scale_pct, int *pre_tiles, int *gt);
 hipError_t l2c_pre_launch(int kc, int lkeep, const unsigned char *Xpk, const unsigned char *Ypk, int tiles_per_split, int S,
@@ -72,9 +83,12 @@ size_t lseed_key_bytes(int64_t ncell);
 size_t lseed_blockcnt_bytes(int64_t ncell, int C);
 size_t lseed_layout_bytes(int C);
 size_t lseed_anchor_bytes(int kc, int C);
-hipError_t lseed_anchors_launch(int kc, const unsigned char *Ypk, int64_t n, int g, int C, void *anchors, hipStream_t st);
+// (two_level: the packed operands are in the two-level slot order, l2c_slots.h)
+hipError_t lseed_anchors_launch(int kc, const unsigned char *Ypk, int64_t n, int g, int C, void *anchors, hipStream_t st,
+                                bool two_level = false);
 hipError_t lseed_sort_launch(int kc, bool is_ref, const unsigned char *pk, int64_t ncell, int g, const void *anchors, int C,
-                             uint32_t *key, uint32_t *blockcnt, uint32_t *tot, hipStream_t st);
+                             uint32_t *key, uint32_t *blockcnt, uint32_t *tot, hipStream_t st, bool two_level = false);
+hipError_t lseed_fill_launch(int kc, const unsigned char *src, int64_t pad_cell, unsigned char *dst, int64_t ncell, hipStream_t st);
 hipError_t lseed_layout_launch(int C, const uint32_t *ref_cnt, const uint32_t *row_cnt, int cap, int lkeep, int tile0,
                                const int rest[4], int64_t *lay, int *ranges, int64_t ncol, hipStream_t st);
 hipError_t lseed_move_launch(int kc, const unsigned char *src, int64_t ncell, const uint32_t *key, const uint32_t *blockoff, int C,

@@ -91,6 +91,24 @@ NABO_HD inline void lseed_layout(int C, const uint32_t *ref_cnt, const uint32_t 
     pade[C] = base[C] + (pos - base[C] + LSEED_COL_ROWS - 1) / LSEED_COL_ROWS * LSEED_COL_ROWS;
 }
 
+// The FULL bucket-ordered copy of the references (the two-level stream of l2c_topk.hip): every unmasked cell of bucket b at
+// base[b] + its rank, buckets back to back in whole tiles, [padb[b], pade[b]) the padding of a bucket's last tile.  The
+// copy holds at most ref_tiles + C tiles (lseed_ordered_tiles; what the buckets leave unused is padding cells too).
+NABO_HD inline void lseed_layout_full(int C, const uint32_t *ref_cnt, int64_t *base, int64_t *padb, int64_t *pade)
+{
+    int64_t pos = 0;
+    for (int b = 0; b < C; ++b) {
+        base[b] = pos;
+        padb[b] = pos + ref_cnt[b];
+        pos += ((int64_t)ref_cnt[b] + 31) / 32 * 32;
+        pade[b] = pos;
+    }
+    base[C] = pos;
+    padb[C] = pade[C] = 0;
+}
+// tiles the ordered stream runs over (even: the filter's loop runs in twos), without the two padding tiles behind them
+inline int64_t lseed_ordered_tiles(int64_t ref_tiles, int C) { return (ref_tiles + C + 1) / 2 * 2; }
+
 // The columns of class b (b == C: the rest class, whose tournament `rest` is the stream's own) get their range; columns
 // no class reaches keep (0, 0, 0, 0) -- no tournament, nothing written.
 NABO_HD inline void lseed_fill_columns(int b, int C, const uint32_t *ref_cnt, int cap, int lkeep, int tile0, LseedRange rest,

@@ -16,6 +16,7 @@
 #include "local_seeds.h"
 
 #include "knn_common.h"
+#include "l2c_slots.h"
 #include "launch.h"
 
 namespace nabo {
@@ -48,9 +49,11 @@ __device__ __forceinline__ void cell_copy(const unsigned char *__restrict__ src,
         for (int lq = 0; lq < 4; ++lq) *reinterpret_cast<uint4 *>(dp + chunk_off<KS>((int)(di & 31), s, lq)) = v[s][lq];
 }
 
-// anchors [C][KS][4] chunks: the component slots of reference cell c * stride, every other slot (norms, error) zero
+// anchors [C][KS][4] chunks: the component slots of reference cell c * stride, every other slot (norms, error, tail
+// bounds) zero.  two_level: the operands are in the two-level slot order (l2c_slots.h).
 template <int KS>
-__global__ void lseed_anchors_kernel(const unsigned char *__restrict__ Ypk, int64_t stride, int g, int C, lh8 *__restrict__ anchors)
+__global__ void lseed_anchors_kernel(const unsigned char *__restrict__ Ypk, int64_t stride, int g, int C, lh8 *__restrict__ anchors,
+                                     bool two_level)
 {
     constexpr int TB = 2 * KS * 1024;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -60,7 +63,7 @@ __global__ void lseed_anchors_kernel(const unsigned char *__restrict__ Ypk, int6
     lh8 v = *reinterpret_cast<const lh8 *>(Ypk + (cell >> 5) * TB + chunk_off<KS>((int)(cell & 31), s, lq));
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-        if (32 * s + 8 * lq + j >= g) v[j] = (_Float16)0.0f;
+        if (!l2c_slot_is_comp(g, 32 * s + 8 * lq + j, two_level)) v[j] = (_Float16)0.0f;
     anchors[e] = v;
 }
 
@@ -72,7 +75,7 @@ template <int KS, bool IS_REF>
 __global__ __launch_bounds__(LSEED_BLOCK) void lseed_assign_kernel(const unsigned char *__restrict__ pk, int64_t ncell, int g,
                                                                    const lh8 *__restrict__ anchors, int C,
                                                                    uint32_t *__restrict__ key, uint32_t *__restrict__ blockcnt,
-                                                                   int64_t nblk)
+                                                                   int64_t nblk, bool two_level)
 {
     constexpr int TB = 2 * KS * 1024;
     extern __shared__ __attribute__((aligned(16))) unsigned char lseed_smem[];
@@ -105,8 +108,9 @@ __global__ __launch_bounds__(LSEED_BLOCK) void lseed_assign_kernel(const unsigne
 #pragma unroll
         for (int lq = 0; lq < 4; ++lq) x[s][lq] = *reinterpret_cast<const lh8 *>(tp + chunk_off<KS>(c32, s, lq));
     bool none = !live;
-    if (IS_REF) {           // slot g: the high part of the norm, +inf for a masked, non-finite or padding cell
-        const _Float16 nh = *reinterpret_cast<const _Float16 *>(tp + chunk_off<KS>(c32, g >> 5, (g & 31) >> 3) + 2 * (g & 7));
+    if (IS_REF) {           // the high part of the norm (slot g, or the two-level order's): +inf for a masked, non-finite or padding cell
+        const int ns = l2c_norm_slot(g, two_level);
+        const _Float16 nh = *reinterpret_cast<const _Float16 *>(tp + chunk_off<KS>(c32, ns >> 5, (ns & 31) >> 3) + 2 * (ns & 7));
         none = none || !((float)nh < __builtin_inff());
     }
     float best = __builtin_inff();
@@ -176,7 +180,10 @@ __global__ __launch_bounds__(256) void lseed_layout_kernel(int C, const uint32_t
                                                            LseedRange *__restrict__ ranges, int64_t ncol)
 {
     int64_t *base = lay, *padb = lay + (C + 1), *pade = lay + 2 * (C + 1);
-    if (threadIdx.x == 0) lseed_layout(C, ref_cnt, row_cnt, cap, lkeep, tile0, base, padb, pade);
+    if (threadIdx.x == 0) {
+        if (!row_cnt && cap == 0) lseed_layout_full(C, ref_cnt, base, padb, pade);      // the full ordered copy of the references
+        else lseed_layout(C, ref_cnt, row_cnt, cap, lkeep, tile0, base, padb, pade);
+    }
     __syncthreads();
     if (!ranges) return;
     for (int b = threadIdx.x; b <= C; b += 256) lseed_fill_columns(b, C, ref_cnt, cap, lkeep, tile0, rest, base, pade, ranges, ncol);
@@ -211,34 +218,44 @@ __global__ __launch_bounds__(LSEED_COL_ROWS) void lseed_pad_kernel(const unsigne
     if (p < lay[2 * (C + 1) + blockIdx.x]) cell_copy<KS>(src, pad_cell, dst, p);
 }
 
+// every cell of dst [0, ncell) receives cell `pad_cell` of src
+template <int KS>
+__global__ __launch_bounds__(256) void lseed_fill_kernel(const unsigned char *__restrict__ src, int64_t pad_cell, int64_t ncell,
+                                                         unsigned char *__restrict__ dst)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < ncell) cell_copy<KS>(src, pad_cell, dst, i);
+}
+
 size_t lseed_key_bytes(int64_t ncell) { return (size_t)ncell * sizeof(uint32_t); }
 size_t lseed_blockcnt_bytes(int64_t ncell, int C) { return (size_t)((ncell + LSEED_BLOCK - 1) / LSEED_BLOCK) * C * sizeof(uint32_t); }
 size_t lseed_layout_bytes(int C) { return (size_t)3 * (C + 1) * sizeof(int64_t); }
 size_t lseed_anchor_bytes(int kc, int C) { return (size_t)C * (kc / 2) * 4 * 16; }
 
 template <int KS>
-static hipError_t lseed_anchors_t(const unsigned char *Ypk, int64_t n, int g, int C, void *anchors, hipStream_t st)
+static hipError_t lseed_anchors_t(const unsigned char *Ypk, int64_t n, int g, int C, void *anchors, hipStream_t st, bool two_level)
 {
     const int tot = C * KS * 4;
-    hipLaunchKernelGGL((lseed_anchors_kernel<KS>), dim3((tot + 255) / 256), dim3(256), 0, st, Ypk, n / C, g, C, reinterpret_cast<lh8 *>(anchors));
+    hipLaunchKernelGGL((lseed_anchors_kernel<KS>), dim3((tot + 255) / 256), dim3(256), 0, st, Ypk, n / C, g, C, reinterpret_cast<lh8 *>(anchors),
+                       two_level);
     return hipGetLastError();
 }
 
-hipError_t lseed_anchors_launch(int kc, const unsigned char *Ypk, int64_t n, int g, int C, void *anchors, hipStream_t st)
+hipError_t lseed_anchors_launch(int kc, const unsigned char *Ypk, int64_t n, int g, int C, void *anchors, hipStream_t st, bool two_level)
 {
-    if (C < 1 || C > LSEED_MAX_ANCHORS || n < C) return hipErrorInvalidValue;
+    if (C < 1 || C > LSEED_MAX_ANCHORS || n < C || (two_level && (kc != 4 || !l2c_slots_fit(g)))) return hipErrorInvalidValue;
     switch (kc) {
-    case 2: return lseed_anchors_t<1>(Ypk, n, g, C, anchors, st);
-    case 4: return lseed_anchors_t<2>(Ypk, n, g, C, anchors, st);
-    case 6: return lseed_anchors_t<3>(Ypk, n, g, C, anchors, st);
-    case 8: return lseed_anchors_t<4>(Ypk, n, g, C, anchors, st);
+    case 2: return lseed_anchors_t<1>(Ypk, n, g, C, anchors, st, two_level);
+    case 4: return lseed_anchors_t<2>(Ypk, n, g, C, anchors, st, two_level);
+    case 6: return lseed_anchors_t<3>(Ypk, n, g, C, anchors, st, two_level);
+    case 8: return lseed_anchors_t<4>(Ypk, n, g, C, anchors, st, two_level);
     default: return hipErrorInvalidValue;
     }
 }
 
 template <int KS, bool IS_REF>
 static hipError_t lseed_assign_t(const unsigned char *pk, int64_t ncell, int g, const void *anchors, int C, uint32_t *key,
-                                 uint32_t *blockcnt, hipStream_t st)
+                                 uint32_t *blockcnt, hipStream_t st, bool two_level)
 {
     const int64_t nblk = (ncell + LSEED_BLOCK - 1) / LSEED_BLOCK;
     const size_t lds = (size_t)C * KS * 4 * 16 + (size_t)C * 8 + LSEED_BLOCK * sizeof(uint16_t);
@@ -246,21 +263,21 @@ static hipError_t lseed_assign_t(const unsigned char *pk, int64_t ncell, int g, 
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((lseed_assign_kernel<KS, IS_REF>), dim3((unsigned)nblk), dim3(LSEED_BLOCK), lds, st, pk, ncell, g,
-                       reinterpret_cast<const lh8 *>(anchors), C, key, blockcnt, nblk);
+                       reinterpret_cast<const lh8 *>(anchors), C, key, blockcnt, nblk, two_level);
     return hipGetLastError();
 }
 
 // Sort `ncell` packed cells (tile 0 of pk holds cell 0) by bucket: key [ncell], blockcnt [C][blocks] (-> block offsets),
 // tot [C].  is_ref: cells with +inf norm get no bucket.
 hipError_t lseed_sort_launch(int kc, bool is_ref, const unsigned char *pk, int64_t ncell, int g, const void *anchors, int C,
-                             uint32_t *key, uint32_t *blockcnt, uint32_t *tot, hipStream_t st)
+                             uint32_t *key, uint32_t *blockcnt, uint32_t *tot, hipStream_t st, bool two_level)
 {
-    if (C < 1 || C > LSEED_MAX_ANCHORS || ncell < 1) return hipErrorInvalidValue;
+    if (C < 1 || C > LSEED_MAX_ANCHORS || ncell < 1 || (two_level && (kc != 4 || !l2c_slots_fit(g)))) return hipErrorInvalidValue;
     hipError_t e;
 #define NABO_LSEED_ASSIGN(KSV)                                                                                                       \
     case 2 * KSV:                                                                                                                    \
-        e = is_ref ? lseed_assign_t<KSV, true>(pk, ncell, g, anchors, C, key, blockcnt, st)                                          \
-                   : lseed_assign_t<KSV, false>(pk, ncell, g, anchors, C, key, blockcnt, st);                                        \
+        e = is_ref ? lseed_assign_t<KSV, true>(pk, ncell, g, anchors, C, key, blockcnt, st, two_level)                               \
+                   : lseed_assign_t<KSV, false>(pk, ncell, g, anchors, C, key, blockcnt, st, two_level);                             \
         break;
     switch (kc) {
         NABO_LSEED_ASSIGN(1) NABO_LSEED_ASSIGN(2) NABO_LSEED_ASSIGN(3) NABO_LSEED_ASSIGN(4)
@@ -272,7 +289,7 @@ hipError_t lseed_sort_launch(int kc, bool is_ref, const unsigned char *pk, int64
     return hipGetLastError();
 }
 
-// row_cnt == nullptr: the reference side (ranges unused)
+// row_cnt == nullptr: the reference side (ranges unused); with cap == 0 the layout of the full ordered copy
 hipError_t lseed_layout_launch(int C, const uint32_t *ref_cnt, const uint32_t *row_cnt, int cap, int lkeep, int tile0,
                                const int rest[4], int64_t *lay, int *ranges, int64_t ncol, hipStream_t st)
 {
@@ -305,6 +322,20 @@ hipError_t lseed_move_launch(int kc, const unsigned char *src, int64_t ncell, co
     case 8: return lseed_move_t<4>(src, ncell, key, blockoff, C, lay, cap, pad_cell, dst, row_map, st);
     default: return hipErrorInvalidValue;
     }
+}
+
+// dst [0, ncell) filled with cell pad_cell of src (the full ordered copy starts as padding cells)
+hipError_t lseed_fill_launch(int kc, const unsigned char *src, int64_t pad_cell, unsigned char *dst, int64_t ncell, hipStream_t st)
+{
+    const dim3 grid((unsigned)((ncell + 255) / 256));
+    switch (kc) {
+    case 2: hipLaunchKernelGGL((lseed_fill_kernel<1>), grid, dim3(256), 0, st, src, pad_cell, ncell, dst); break;
+    case 4: hipLaunchKernelGGL((lseed_fill_kernel<2>), grid, dim3(256), 0, st, src, pad_cell, ncell, dst); break;
+    case 6: hipLaunchKernelGGL((lseed_fill_kernel<3>), grid, dim3(256), 0, st, src, pad_cell, ncell, dst); break;
+    case 8: hipLaunchKernelGGL((lseed_fill_kernel<4>), grid, dim3(256), 0, st, src, pad_cell, ncell, dst); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 
 }  // namespace nabo

@@ -8,6 +8,7 @@
 #include <hip/hip_fp16.h>
 
 #include "knn_common.h"
+#include "l2c_slots.h"
 #include "launch.h"
 
 namespace nabo {
@@ -172,6 +173,10 @@ hipError_t maxabs_launch(const double *V, int64_t n, int g, const double *centre
 // to nearest AFTER a factor (1 + 2^-9) so that the f16 value is never below the real one, and never below 2^-13 (f16
 // subnormals round with an absolute error).  The error term is a product of two slots: it costs no instruction, and it
 // is per PAIR -- a per-row constant would have to assume max ||y||.
+// NSEG = 2 -- the same one-product operands in the TWO-LEVEL slot order (l2c_slots.h, g + 5 slots): the first step of 32
+// slots alone is a lower bound of the score.  ty / tx2 bound the norms of the f16 components behind the first 28; a target
+// whose 2 tx2 leaves the f16 range is a bad cell like one with a component out of range (zero operands, NaN norm: the exact
+// kernels answer it).  References are scaled to |y~| <= 2^12: ty <= 2^12 sqrt(31) 1.002 < 2^15.
 // Register layouts (16 bytes per lane and register, a tile is kc KiB either way):
 //   L16 = false (v_mfma_f32_32x32x16_f16; the removed l2h / l2s kernels): register s < kc, lane l: cell l & 31,
 //                slots 16 s + 8 (l >> 5) + j;
@@ -228,7 +233,8 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void pack_ctiles_kernel(const doub
     }
     __syncthreads();
     // whole-row pass, lane c < 32 for cell c: range check, ||rep||^2, and the norm slots that derive from them
-    float nh = 0.0f, nl = 0.0f, er = 0.0f;
+    constexpr bool ONE = NSEG != 3;                          // one-product operands (either slot order)
+    float nh = 0.0f, nl = 0.0f, er = 0.0f, tl = 0.0f;
     int bad_i = 0;
     unsigned int nmax = 0;
     if (on && lane < 32) {
@@ -237,7 +243,7 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void pack_ctiles_kernel(const doub
         // locality order (order.hip, removed: see git history): packed position `cell` holds caller row perm[cell]; norm64 is indexed by POSITION
         const int64_t src = (live && perm) ? (int64_t)perm[cell] : cell;
         bool bad = false;
-        double ss = 0.0;
+        double ss = 0.0, st2 = 0.0;                           // st2: ||hi[28..g)||^2 (two-level order)
         for (int e = 0; e < g && live; ++e) {
             const float f = stage[lane * gs + e];
             bad = bad || !(fabsf(f) <= 30000.0f);                 // f16 range (targets carry a factor 2); NaN / inf input
@@ -245,6 +251,11 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void pack_ctiles_kernel(const doub
             const _Float16 l = (_Float16)(f - (float)h);
             const double rep = (double)(float)h + (double)(float)l;
             ss += rep * rep;
+            if (NSEG == 2 && e >= L2C_HEAD) st2 += (double)(float)h * (double)(float)h;
+        }
+        if (NSEG == 2 && live) {
+            tl = l2c_round_up(sqrt(st2));
+            if (!IS_REF) bad = bad || !(tl <= 32000.0f);          // 2 tx2 must be an f16
         }
         if (IS_REF) {
             float nf = __builtin_inff();
@@ -255,14 +266,16 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void pack_ctiles_kernel(const doub
             const _Float16 h = (_Float16)nf;
             nh = (float)h;
             if (nf < __builtin_inff()) nl = (float)(_Float16)(nf - (float)h);
-            if (NSEG == 1 && nf < __builtin_inff()) er = fmaxf((float)(sqrt(ss) * (1.002 * 1.001953125)), 1.220703125e-4f);
+            if (ONE && nf < __builtin_inff()) er = fmaxf((float)(sqrt(ss) * (1.002 * 1.001953125)), 1.220703125e-4f);
+            if (!(nf < __builtin_inff())) tl = 0.0f;              // (a masked reference has no error slot and no tail bound)
         } else {
             // segments 0 and 1; NOT scaled by -2: the product is +||y||^2.  (One-product operands: padding rows carry the
             // slots too -- 0 x inf would be the only NaN that kernel could see, and it is compiled with -fno-honor-nans.)
-            nh = nl = (live || NSEG == 1) ? 32768.0f : 0.0f;
+            nh = nl = (live || ONE) ? 32768.0f : 0.0f;
             if (live) norm64[cell] = bad ? __builtin_nan("") : ss / (scale * scale);
-            if (NSEG == 1 && live && !bad)
+            if (ONE && live && !bad)
                 er = -fmaxf((float)(sqrt(ss) * (0.001953125 * 1.01 * 1.001953125)), 1.220703125e-4f);
+            if (bad) tl = 0.0f;
         }
         bad_i = bad;
     }
@@ -283,7 +296,7 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void pack_ctiles_kernel(const doub
     for (int hc = 0; hc < nh_cells; ++hc) {
         const int c = L16 ? 16 * hc + (lane & 15) : lane & 31;
         const bool live = on && tile * 32 + c < ncell;
-        const float nh_c = __shfl(nh, c, 64), nl_c = __shfl(nl, c, 64), er_c = __shfl(er, c, 64);
+        const float nh_c = __shfl(nh, c, 64), nl_c = __shfl(nl, c, 64), er_c = __shfl(er, c, 64), tl_c = __shfl(tl, c, 64);
         const bool bad = __shfl(bad_i, c, 64) != 0;
         const float *row = stage + c * gs;
         for (int s = 0; s < ks && on; ++s) {
@@ -305,6 +318,17 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void pack_ctiles_kernel(const doub
                             val = want_lo ? lo : (float)h;
                             if (!IS_REF) val *= -2.0f;
                         }
+                    }
+                } else if (NSEG == 2) {
+                    const int what = l2c_slot_holds(g, p);
+                    if (what == L2C_IS_NH) val = nh_c;
+                    else if (what == L2C_IS_NL) val = nl_c;
+                    else if (what == L2C_IS_EY) val = er_c;
+                    else if (what == L2C_IS_TAIL) val = IS_REF ? tl_c : -2.0f * tl_c;
+                    else if (what == L2C_IS_TAIL2) val = IS_REF ? tl_c : 2.0f * tl_c;
+                    else if (what >= 0 && live && !bad) {
+                        val = (float)(_Float16)row[what];
+                        if (!IS_REF) val *= -2.0f;
                     }
                 } else {
                     if (p == g) val = nh_c;
@@ -328,12 +352,15 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void pack_ctiles_kernel(const doub
                        dim3(64 * PACK_WAVES), (size_t)PACK_WAVES * 32 * (g | 1) * sizeof(float), st, V, ncell, g, centre, scale, \
                        kc, ntiles_total, mask, out, norm64, nmax, perm)
 
-// nseg: 3 = f16x3 operands, 1 = the one-product operands
+// nseg: 3 = f16x3 operands, 1 = the one-product operands, 2 = the one-product operands in the two-level slot order (layout16)
 hipError_t pack_cref_launch(const double *Y, int64_t n, int g, const double *centre, double scale, int kc,
                             int64_t ntiles_total, const uint8_t *mask, unsigned char *out, unsigned int *norm_max_bits,
                             bool layout16, hipStream_t st, const uint32_t *perm, int nseg)
 {
-    if (nseg == 1 && layout16)
+    if (nseg == 2 && (!layout16 || !l2c_slots_fit(g) || kc != 4)) return hipErrorInvalidValue;
+    if (nseg == 2)
+        PACK_CTILES_LAUNCH(true, true, 2, Y, n, mask, (double *)nullptr, norm_max_bits);
+    else if (nseg == 1 && layout16)
         PACK_CTILES_LAUNCH(true, true, 1, Y, n, mask, (double *)nullptr, norm_max_bits);
     else if (nseg == 1)
         PACK_CTILES_LAUNCH(true, false, 1, Y, n, mask, (double *)nullptr, norm_max_bits);
@@ -348,7 +375,10 @@ hipError_t pack_cquery_launch(const double *X, int64_t m, int g, const double *c
                               int64_t ntiles_total, unsigned char *out, double *xnorm, bool layout16, hipStream_t st,
                               const uint32_t *perm, int nseg)
 {
-    if (nseg == 1 && layout16)
+    if (nseg == 2 && (!layout16 || !l2c_slots_fit(g) || kc != 4)) return hipErrorInvalidValue;
+    if (nseg == 2)
+        PACK_CTILES_LAUNCH(false, true, 2, X, m, (const uint8_t *)nullptr, xnorm, (unsigned int *)nullptr);
+    else if (nseg == 1 && layout16)
         PACK_CTILES_LAUNCH(false, true, 1, X, m, (const uint8_t *)nullptr, xnorm, (unsigned int *)nullptr);
     else if (nseg == 1)
         PACK_CTILES_LAUNCH(false, false, 1, X, m, (const uint8_t *)nullptr, xnorm, (unsigned int *)nullptr);

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "index.h"
+#include "l2c_slots.h"
 #include "local_seeds.h"
 
 namespace nabo {
@@ -36,8 +37,19 @@ static const OptionName LOCAL_SEED_OPTION_NAMES[] = {
     {"local_seeds", &Options::local_seeds}, {"local_anchors", &Options::local_anchors}, {"local_cap", &Options::local_cap},
 };
 
+// The two-level stream's options (l2c_topk.hip): tests/test_two_level_gpu.py runs it on small shapes against the oracle.
+static const OptionName TWO_LEVEL_OPTION_NAMES[] = {
+    {"two_level", &Options::two_level}, {"two_level_share", &Options::two_level_share}, {"two_level_stretch", &Options::two_level_stretch},
+};
+
 bool option_set(Options &o, const char *name, int64_t value)
 {
+    for (const OptionName &e : TWO_LEVEL_OPTION_NAMES)
+        if (strcmp(e.name, name) == 0) {            // clamped: 0 .. 2, percent, tiles
+            const int64_t hi = e.field == &Options::two_level ? 2 : e.field == &Options::two_level_share ? 100 : 1 << 20;
+            o.*(e.field) = (int)(value < 0 ? 0 : value > hi ? hi : value);
+            return true;
+        }
     for (const OptionName &e : OPTION_NAMES)
         if (strcmp(e.name, name) == 0) {
             o.*(e.field) = (int)value;
@@ -51,6 +63,27 @@ bool option_set(Options &o, const char *name, int64_t value)
     return false;
 }
 
+// The two-level slot order serves the l2c kernel's one-step loop, which exists for two operand steps (28 < g <= 59) and runs
+// on launches that take local seeds: by default where those are on by default, with option two_level = 2 at any size.
+static bool two_level_wanted(const IndexShape &sh)
+{
+    if (sh.opt.two_level == 0 || !sh.coarse || !l2c_slots_fit(sh.g) || sh.opt.local_seeds == 0 || sh.opt.prepass <= 0) return false;
+    int c = sh.opt.local_anchors > 0 ? sh.opt.local_anchors : 64;
+    if (sh.n < c) return false;
+    return sh.opt.two_level >= 2 || sh.n >= LSEED_MIN_REFS;
+}
+bool two_level_slots(const IndexShape &sh) { return sh.kc1 == 4 && two_level_wanted(sh); }
+
+// The operand steps of the one-product pass follow the options: g = 29 fills ONE step of 32 slots in the plain order
+// (29 + 3) and needs two in the two-level order (29 + 5) -- twice the matrix work for nothing by default, so only option
+// two_level = 2 asks for it (the smallest tail there is: tests).  Called wherever an option may have changed.
+void shape_refresh(IndexShape &sh)
+{
+    if (!sh.coarse) return;
+    sh.kc1 = l2c_pick_kc(sh.g);
+    if (sh.kc1 == 2 && sh.opt.two_level >= 2 && two_level_wanted(sh)) sh.kc1 = 4;
+}
+
 void lseed_params(const IndexShape &sh, int *C, int *cap)
 {
     int c = sh.opt.local_anchors > 0 ? sh.opt.local_anchors : 64;
@@ -61,7 +94,8 @@ void lseed_params(const IndexShape &sh, int *C, int *cap)
     // no one-product operands, switched off, or fewer references than anchors
     if (!sh.coarse || sh.opt.local_seeds == 0 || sh.n < c) c = 0;
     // by default only where a launch can take them (lseed_applies): the runs cost C * cap cells of memory
-    if (sh.opt.local_seeds == 1 && sh.n < LSEED_MIN_REFS) c = 0;
+    // (option two_level = 2 brings its buckets along at any size -- where its slot order fits)
+    if (sh.opt.local_seeds == 1 && sh.n < LSEED_MIN_REFS && !(sh.opt.two_level >= 2 && l2c_slots_fit(sh.g))) c = 0;
     *C = c;
     *cap = k;
 }
@@ -78,7 +112,7 @@ bool lseed_applies(const IndexShape &sh, const L2Plan &P, int S, int64_t rows)
     int C = 0, cap = 0;
     lseed_params(sh, &C, &cap);
     if (C == 0 || !P.on_l2c || S != 1 || rows < 1 || sh.opt.prepass <= 0) return false;
-    return sh.opt.local_seeds >= 2 || (P.geo == 1 && rows >= LSEED_MIN_ROWS);
+    return sh.opt.local_seeds >= 2 || (P.geo == 1 && (rows >= LSEED_MIN_ROWS || (sh.opt.two_level >= 2 && P.slots2)));
 }
 
 // Which filter kernels serve an index of this shape, and its reference tiles (IndexShape, index.h)
@@ -291,6 +325,14 @@ int plan_l2(const IndexShape &sh, const PassCtx &ctx, int64_t m, int k, int drop
     P->rows_per_wg = rows_per_wg; P->wg_per_cu = wg_per_cu; P->lkeep_max = lkeep_max; P->lkeep = lkeep; P->want = want;
     P->S = S; P->S2 = S2; P->one_round = one_round;
     P->gx = gx; P->gx_main = gx_main; P->gx_tail = gx_tail; P->rows_pad = rows_pad; P->tps = tps; P->tps2 = tps2;
+    // the two-level stream: the main launch of the first pass in geometry B where it takes local seeds (their bucket-ordered
+    // target copy is what it reads; a tail launch with local seeds of its own would overwrite that copy)
+    P->slots2 = use_1 && two_level_slots(sh);
+    {
+        const int64_t rows_main = gx_main * rows_per_wg < m ? gx_main * rows_per_wg : m;
+        P->tl_main = P->slots2 && on_l2c && geo == 1 && kcq == 4 && ctx.first() && !cand_mode && gx_main > 0 &&
+                     lseed_applies(sh, *P, S, rows_main) && !(gx_tail > 0 && lseed_applies(sh, *P, S2, m - rows_main));
+    }
     // (option coarse_kernel_q runs the one-product operands through the l2q kernel)
     if (use_1 && !on_l2c)
         snprintf(P->kernel, sizeof(P->kernel), "l2q_topk_kernel<%d,1,33> (v_mfma_f32_16x16x32_f16, one-product f16 filter with the split error as an operand slot)", kcq);
@@ -395,6 +437,7 @@ int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t
             *eq = 0;
             if (!option_set(sh.opt, tok, atoll(eq + 1))) return api_fail(NABO_E_INVALID, "unknown option '%s'", tok);
         }
+        shape_refresh(sh);
     }
     const int drop = drop_first ? 1 : 0;
     const bool cand = n_cand > 0;
@@ -422,6 +465,7 @@ int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t
         const int64_t rows_main = P.gx_main * P.rows_per_wg < m ? P.gx_main * P.rows_per_wg : m;
         out[17] = lseed_applies(sh, P, P.S, rows_main) ? lc : 0;
     }
+    out[18] = P.tl_main ? 2 : P.slots2 ? 1 : 0;      // two-level: 2 the main launch streams one-step, 1 the slot order only
     if (kernel && kernel_len) snprintf(kernel, kernel_len, "%s", P.kernel);
     return NABO_OK;
 }

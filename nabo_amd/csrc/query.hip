@@ -116,19 +116,22 @@ static int local_seeds(nabo_index *ix, const Query &q, const L2Plan &P, L2Part &
     const int C = l2.local_C, cap = l2.local_cap, kc = P.kcq;
     const int64_t nrows = p.end(q.m) - p.row0;
     const int64_t ncol = lseed_columns(nrows, C), prow = ncol * LSEED_COL_ROWS;
+    // (a two-level launch reads the copy in whole workgroups: positions up to prow_wg, the ones past prow padding)
+    const int64_t prow_wg = (prow + P.rows_per_wg - 1) / P.rows_per_wg * P.rows_per_wg;
     const size_t tile_bytes = (size_t)kc * 1024;
     if ((rc = p.pre->reserve((size_t)p.rows * sizeof(float))) || (rc = ws.lkey.reserve(lseed_key_bytes(nrows))) ||
         (rc = ws.lblk.reserve(lseed_blockcnt_bytes(nrows, C))) || (rc = ws.ltot.reserve((size_t)C * sizeof(uint32_t))) ||
-        (rc = ws.llay.reserve(lseed_layout_bytes(C))) || (rc = ws.xpre.reserve((size_t)(prow / 32) * tile_bytes)) ||
-        (rc = ws.lmap.reserve((size_t)prow * sizeof(uint32_t))) || (rc = ws.lranges.reserve((size_t)ncol * 4 * sizeof(int))))
+        (rc = ws.llay.reserve(lseed_layout_bytes(C))) || (rc = ws.xpre.reserve((size_t)(prow_wg / 32) * tile_bytes)) ||
+        (rc = ws.lmap.reserve((size_t)prow_wg * sizeof(uint32_t))) || (rc = ws.lranges.reserve((size_t)ncol * 4 * sizeof(int))))
         return rc;
     const unsigned char *xh = ws.xpk.as<unsigned char>() + (size_t)(p.row0 / 32) * tile_bytes;
     const int rest[4] = {0, (int)p.tps, pt, pt > 0 ? gt : 0};
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.pre->p), 0x7F800000, (size_t)p.rows, st));      // +inf: rows without a tournament
-    HIP_TRY(hipMemsetAsync(ws.lmap.p, 0xFF, (size_t)prow * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(ws.lmap.p, 0xFF, (size_t)prow_wg * sizeof(uint32_t), st));
+    if (prow_wg > prow) HIP_TRY(hipMemsetAsync(ws.xpre.as<unsigned char>() + (size_t)(prow / 32) * tile_bytes, 0, (size_t)((prow_wg - prow) / 32) * tile_bytes, st));
     HIP_TRY(hipMemsetAsync(ws.lranges.p, 0, (size_t)ncol * 4 * sizeof(int), st));
     HIP_TRY(lseed_sort_launch(kc, false, xh, nrows, sh.g, l2.lanchors.p, C, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(),
-                              ws.ltot.as<uint32_t>(), st));
+                              ws.ltot.as<uint32_t>(), st, l2.slots2));
     HIP_TRY(lseed_layout_launch(C, l2.lrefcnt.as<uint32_t>(), ws.ltot.as<uint32_t>(), cap, P.lkeep, (int)sh.ref_tiles_alloc, rest,
                                 ws.llay.as<int64_t>(), ws.lranges.as<int>(), ncol, st));
     HIP_TRY(lseed_move_launch(kc, xh, nrows, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), 0, 0,
@@ -174,6 +177,7 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
     const float *seed[2] = {seeds, seeds};
     int stride[2] = {0, 0};
     if (first) ix->last.pre_tiles_last = 0;
+    bool ordered = false;                // the main launch streams the bucket-ordered operands (two-level, l2c_topk.hip)
     for (int i = 0; i < 2 && pre_pct > 0; ++i) {
         L2Part &p = part[i];
         int pt = 0, gt = 2;
@@ -183,6 +187,7 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
             seed[i] = p.pre->as<float>();
             stride[i] = p.S;
             if (i == 0 && first) ix->last.pre_tiles_last = pt;
+            if (i == 0 && P.tl_main && l2.ord_built && l2.tl_verdict != 2) ordered = true;
             continue;
         }
         if (pt <= 0 || p.gx == 0) continue;
@@ -196,6 +201,44 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
     for (int i = 0; i < 2; ++i) {
         L2Part &p = part[i];
         if (p.gx == 0) continue;
+        const int64_t prow = ordered ? lseed_columns(p.end(q.m) - p.row0, l2.local_C) * LSEED_COL_ROWS : 0;
+        const int64_t gx_ord = (prow + P.rows_per_wg - 1) / P.rows_per_wg;
+        L2cOrdered ord = {ws.lmap.as<uint32_t>(), l2.yordmap.as<uint32_t>(), nullptr, sh.opt.two_level_share, sh.opt.two_level_stretch};
+        if (i == 0 && ordered) {
+            if ((rc = ws.tlstats.reserve(3 * sizeof(unsigned long long)))) return rc;
+            ord.stats = ws.tlstats.as<unsigned long long>();
+        }
+        // PROBE (long launches, default setting): on data without clusters the bounds of the first step reject nothing, the
+        // waves run the two-step loop anyway, and the bucket-ordered stream is the worst order for their lists (every row
+        // of a wave meets its neighbours at once: one broad Gaussian cloud, 1M x 1M: 119 ms per step against 89).  The
+        // kernel's own counters tell the two apart in a few hundred microseconds: the first 128 workgroups (rows of the
+        // first buckets) over the first 1024 tiles (the same buckets' references, own and foreign).  Fewer than 30 % of
+        // those tiles run one-step: this query and the next ones take the caller-order stream.  The verdict, yes or no,
+        // is remembered (tl_verdict, index.h): the probe runs once per TL_VERDICT_REPACKS repacks of the references, not
+        // per query.  A HEURISTIC -- two or three buckets stand for all, the threshold was set on two kinds of data; a
+        // wrong "yes" is corrected by the launch's own counters, a wrong "no" costs the gain until the verdict expires.
+        // Its lists are scratch: the launch proper writes every row again.  One host wait.
+        if (i == 0 && ordered && l2.tl_verdict == 0 && sh.opt.two_level == 1 && gx_ord >= 512 && l2.ord_tiles >= 4096) {
+            unsigned long long probe[3] = {0, 0, 0};
+            HIP_TRY(hipMemsetAsync(ws.tlstats.p, 0, sizeof(probe), st));
+            HIP_TRY(l2c_topk_launch(P.kcq, P.geo, ws.xpre.as<unsigned char>(), l2.yord.as<unsigned char>(), 1024, 1, 128, 0, P.lkeep,
+                                    p.idx->as<uint32_t>(), nullptr, p.tau->as<float>(), l2.ord_tiles, st, prow, seed[i], stride[i], 0, &ord));
+            HIP_TRY(hipMemcpyAsync(probe, ws.tlstats.p, sizeof(probe), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            l2.tl_verdict = probe[0] * 10 < (probe[0] + probe[2]) * 3 ? 2 : 1;
+            l2.tl_age = 0;
+            if (l2.tl_verdict == 2) ordered = false;
+        }
+        if (i == 0 && ordered) {
+            // targets: the bucket-ordered copy local_seeds made (whole workgroups of positions); references: the ordered
+            // copy and its two padding tiles; lists and seeds by the launch's rows, candidates as reference indices
+            HIP_TRY(hipMemsetAsync(ws.tlstats.p, 0, 3 * sizeof(unsigned long long), st));
+            HIP_TRY(l2c_topk_launch(P.kcq, P.geo, ws.xpre.as<unsigned char>(), l2.yord.as<unsigned char>(), (int)l2.ord_tiles, 1,
+                                    (int)((prow + P.rows_per_wg - 1) / P.rows_per_wg), 0, P.lkeep, p.idx->as<uint32_t>(),
+                                    p.merge ? p.key->as<float>() : nullptr, p.tau->as<float>(), l2.ord_tiles, st, prow, seed[i],
+                                    stride[i], 0, &ord));
+            ix->last.tl_ran = true;
+        } else
         HIP_TRY(l2c_topk_launch(P.kcq, P.geo, xh, yh, (int)p.tps, p.S, (int)p.gx, p.row0 / 32, P.lkeep,
                                 p.idx->as<uint32_t>(), p.merge ? p.key->as<float>() : nullptr, p.tau->as<float>(),
                                 pad_tile, st, q.m, seed[i], stride[i], p.row0));
@@ -224,7 +267,11 @@ static int l2_refine(nabo_index *ix, const Query &q, const L2Plan &P, L2Part (&p
     // representation error of the hi + lo split)
     // (one-product pass: the hi x lo, lo x hi and lo x lo terms are INSIDE its score -- the error slot of
     // pack_ctiles_kernel<.,.,1> -- so the same accumulation / representation coefficient applies to its kc1 steps)
-    const double err_coef = P.use_h ? 1.05 * ((16.0 * P.kcq + 8.0) * std::ldexp(1.0, -24) + std::ldexp(1.0, -20) + std::ldexp(1.0, -21))
+    // (two-level slot order: two more terms, -2 tx2 ty and +2 tx2 ty, pass through the fp32 accumulation -- in g + 5 <= 64
+    // slots, still 16 kc products, but their magnitudes add 4 tx2 ty <= 4.02 ||x|| ||y|| <= 1.005 (||x|| + ||y||)^2 to the
+    // sum of magnitudes the accumulation error scales with: twice the coefficient of the accumulated part)
+    const double acc_terms = P.slots2 ? 2.01 * 16.0 * P.kcq : 16.0 * P.kcq;
+    const double err_coef = P.use_h ? 1.05 * ((acc_terms + 8.0) * std::ldexp(1.0, -24) + std::ldexp(1.0, -20) + std::ldexp(1.0, -21))
                                     : 1.05 * (2.0 * sh.ksteps + 4.0) * std::ldexp(1.0, -24);
     const double tau_scale = P.use_h ? 1.0 / (l2.hscale * l2.hscale) : 1.0 / (l2.fscale * l2.fscale);
     int rc;
@@ -333,6 +380,7 @@ static int query_l2(nabo_index *ix, const PassCtx &ctx, Query &q)
     if (ctx.first()) {
         ix->last.pass_rows[0] = ix->last.pass_rows[1] = ix->last.pass_rows[2] = 0;
         snprintf(ix->last.kernel, sizeof(ix->last.kernel), "%s", P.kernel);
+        ix->last.tl_ran = false;
     }
     if ((rc = ensure_packed(ix, P.use_1 ? 2 : P.use_h ? 1 : 0))) return rc;
     // (before anything takes the operands' address: a change of options since the pack moves them)
@@ -375,7 +423,8 @@ static int query_l2(nabo_index *ix, const PassCtx &ctx, Query &q)
     HIP_TRY(hipMemsetAsync(ws.failcnt.p, 0, sizeof(unsigned int), st));
     if (P.use_h)
         HIP_TRY(pack_cquery_launch(dXp, m, g, l2.centre.as<double>(), l2.hscale, P.kcq, P.rows_pad / 32,
-                                   ws.xpk.as<unsigned char>(), ws.xnorm.as<double>(), true, st, nullptr, P.use_1 ? 1 : 3));
+                                   ws.xpk.as<unsigned char>(), ws.xnorm.as<double>(), true, st, nullptr,
+                                   P.use_1 ? (P.slots2 ? 2 : 1) : 3));
     else
         HIP_TRY(pack_query_launch(dXp, m, g, l2.centre.as<double>(), l2.fscale, sh.ksteps, P.rows_pad / 32,
                                   ws.xpk.as<float>(), ws.xnorm.as<double>(), st));
@@ -399,7 +448,22 @@ static int query_l2(nabo_index *ix, const PassCtx &ctx, Query &q)
         return NABO_OK;
     }
     HIP_TRY(hipMemcpyAsync(&q.n_fail, ws.failcnt.p, sizeof(q.n_fail), hipMemcpyDeviceToHost, st));
+    unsigned long long tl_tiles[3] = {0, 0, 0};
+    const bool tl_ran = ctx.first() && ix->last.tl_ran;
+    if (tl_ran) HIP_TRY(hipMemcpyAsync(tl_tiles, ws.tlstats.p, sizeof(tl_tiles), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    if (tl_ran) {
+        // the two-level launch's tile counters: into the record (the kernel string carries them to nabo_index_last_kernel),
+        // and the memory of a poor outcome -- waves that ran fewer than a quarter of their tiles one-step paid the
+        // bucket-ordered stream for nothing: the next queries take the caller-order stream (tl_verdict)
+        const size_t len = strlen(ix->last.kernel);
+        snprintf(ix->last.kernel + len, sizeof(ix->last.kernel) - len, " [two-level tiles: one-step %lld, refetched %lld, two-step %lld]",
+                 (long long)tl_tiles[0], (long long)tl_tiles[1], (long long)tl_tiles[2]);
+        if (sh.opt.coarse_adapt != 0 && m >= 1024 && tl_tiles[0] * 3 < tl_tiles[2]) {
+            l2.tl_verdict = 2;
+            l2.tl_age = 0;
+        }
+    }
     if (P.use_1 && q.n_fail > 0) {
         // Rows this one-product pass could not certify: from level 0 on the l2c kernel to the SEEDED one-product pass
         // (level 1: every row starts from the threshold refine.hip derived from its failed certificate), otherwise to

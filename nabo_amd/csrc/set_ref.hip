@@ -17,6 +17,8 @@ int ensure_packed(nabo_index *ix, int want)
     auto &ref = ix->ref;
     auto &l2 = ix->ref.l2;
     const bool want_h = want != 0;
+    // (option two_level changed since the pack: the one-product operands are in the other slot order)
+    if (want == 2 && l2.packed_c1 && l2.slots2 != two_level_slots(sh)) l2.packed_c1 = false;
     if (want == 2 ? l2.packed_c1 : want == 1 ? l2.packed_c16 : l2.packed_f32) return NABO_OK;
     hipStream_t st = ix->stream;
     int rc;
@@ -43,12 +45,13 @@ int ensure_packed(nabo_index *ix, int want)
         int lc = 0, lcap = 0;
         lseed_params(sh, &lc, &lcap);
         l2.local_room = (int64_t)lc * (lcap / 32);
-        l2.local_built = false;
+        l2.local_built = l2.ord_built = false;
+        l2.slots2 = two_level_slots(sh);
         if ((rc = l2.ycpk1.reserve((size_t)(sh.ref_tiles_alloc + l2.local_room) * sh.kc1 * 1024 + 128))) return rc;
         l2.hscale = scale = std::ldexp(1.0, e2 + 12);
         HIP_TRY(pack_cref_launch(l2.dYp, sh.n, sh.g, l2.centre.as<double>(), l2.hscale, sh.kc1,
                                  sh.ref_tiles_alloc, ref.dmask, l2.ycpk1.as<unsigned char>(),
-                                 l2.normmax.as<unsigned int>(), true, st, nullptr, 1));
+                                 l2.normmax.as<unsigned int>(), true, st, nullptr, l2.slots2 ? 2 : 1));
     } else if (want_h) {
         if ((rc = l2.ycpk.reserve((size_t)sh.ref_tiles_alloc * sh.kc * 1024 + 128))) return rc;
         // |v| <= 2^12 after scaling (f16 overflows at 65504; targets carry a factor 2)
@@ -91,7 +94,8 @@ int ensure_local_seeds(nabo_index *ix)
     int rc, C = 0, cap = 0;
     lseed_params(sh, &C, &cap);
     if (C == 0) return NABO_OK;
-    if (l2.local_built && l2.local_C == C && l2.local_cap == cap && l2.packed_c1) return NABO_OK;
+    if (l2.packed_c1 && l2.slots2 != two_level_slots(sh)) l2.packed_c1 = false;
+    if (l2.local_built && l2.local_C == C && l2.local_cap == cap && l2.packed_c1 && (l2.ord_built || !l2.slots2 || l2.tl_verdict == 2)) return NABO_OK;
     if (!l2.packed_c1 || l2.local_room < (int64_t)C * (cap / 32)) {           // (options changed since the pack: room for the runs)
         l2.packed_c1 = false;
         if ((rc = ensure_packed(ix, 2))) return rc;
@@ -103,13 +107,28 @@ int ensure_local_seeds(nabo_index *ix)
         return rc;
     unsigned char *ypk = l2.ycpk1.as<unsigned char>();
     const int rest[4] = {0, 0, 0, 0};
-    HIP_TRY(lseed_anchors_launch(sh.kc1, ypk, sh.n, sh.g, C, l2.lanchors.p, st));
+    HIP_TRY(lseed_anchors_launch(sh.kc1, ypk, sh.n, sh.g, C, l2.lanchors.p, st, l2.slots2));
     HIP_TRY(lseed_sort_launch(sh.kc1, true, ypk, sh.n, sh.g, l2.lanchors.p, C, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(),
-                              l2.lrefcnt.as<uint32_t>(), st));
+                              l2.lrefcnt.as<uint32_t>(), st, l2.slots2));
     HIP_TRY(lseed_layout_launch(C, l2.lrefcnt.as<uint32_t>(), nullptr, cap, 1, 0, rest, ws.llay.as<int64_t>(), nullptr, 0, st));
     // (padding positions: a cell of the stream's last tile, which lies beyond the references -- +inf norm)
     HIP_TRY(lseed_move_launch(sh.kc1, ypk, sh.n, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), cap,
                               (sh.ref_tiles_alloc - 1) * 32, ypk + (size_t)sh.ref_tiles_alloc * sh.kc1 * 1024, nullptr, st));
+    if (l2.slots2 && l2.tl_verdict != 2) {
+        // The two-level stream (not for data that is known not to take it): ALL unmasked references in bucket order (the same keys and block offsets, no cap), every
+        // bucket in whole tiles, and the map from position to reference index.  The copy starts as padding cells (+inf
+        // norm): what the buckets leave of its ref_tiles + C tiles, and the two tiles behind them the filter's ring reads.
+        const int64_t ot = lseed_ordered_tiles(sh.ref_tiles, C);
+        if ((rc = l2.yord.reserve((size_t)(ot + 2) * sh.kc1 * 1024 + 128)) || (rc = l2.yordmap.reserve((size_t)(ot + 2) * 32 * sizeof(uint32_t))))
+            return rc;
+        HIP_TRY(lseed_fill_launch(sh.kc1, ypk, (sh.ref_tiles_alloc - 1) * 32, l2.yord.as<unsigned char>(), (ot + 2) * 32, st));
+        HIP_TRY(hipMemsetAsync(l2.yordmap.p, 0xFF, (size_t)(ot + 2) * 32 * sizeof(uint32_t), st));
+        HIP_TRY(lseed_layout_launch(C, l2.lrefcnt.as<uint32_t>(), nullptr, 0, 1, 0, rest, ws.llay.as<int64_t>(), nullptr, 0, st));
+        HIP_TRY(lseed_move_launch(sh.kc1, ypk, sh.n, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), 0,
+                                  (sh.ref_tiles_alloc - 1) * 32, l2.yord.as<unsigned char>(), l2.yordmap.as<uint32_t>(), st));
+        l2.ord_tiles = ot;
+        l2.ord_built = true;
+    }
     l2.local_C = C;
     l2.local_cap = cap;
     l2.local_built = true;
@@ -169,6 +188,7 @@ static int repack_refs(nabo_index *ix)
     l2.packed_f32 = l2.packed_c16 = l2.packed_c1 = false;
     l2.ymax_pending = false;                      // (a read still in flight belongs to operands that are gone)
     l2.coarse_weak = false;
+    if (++l2.tl_age >= TL_VERDICT_REPACKS) l2.tl_verdict = l2.tl_age = 0;      // (the two-level verdict: asked again now and then)
     return ensure_packed(ix, ix->shape.coarse ? 2 : ix->shape.mode == 1 ? 1 : 0);
 }
 

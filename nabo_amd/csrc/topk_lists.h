@@ -380,7 +380,9 @@ __device__ __forceinline__ void filter_stage(const f32x16 &acc, const FilterVerd
 template <typename C, int EPL, int NB>
 __device__ __forceinline__ void lists_flush(unsigned char *w, uint32_t scnt, int64_t lrow0, int split, int S, int lkeep,
                                             float (&tauv)[NB], uint32_t *__restrict__ cand_idx,
-                                            float *__restrict__ cand_key, float *__restrict__ cand_tau)
+                                            float *__restrict__ cand_key, float *__restrict__ cand_tau,
+                                            const uint32_t *__restrict__ row_map = nullptr,
+                                            const uint32_t *__restrict__ ref_map = nullptr)
 {
     const uint32_t idx_base = C::base(w)[0];
     constexpr int LMAX = C::LMAX;
@@ -388,8 +390,16 @@ __device__ __forceinline__ void lists_flush(unsigned char *w, uint32_t scnt, int
     if (scnt > 0) lists_drain<C, NB>(w, scnt, lkeep, tauv);
     const uint2 *rows = C::rows(w);
     for (int row = 0; row < C::NROWS; ++row) {
+        // row_map (bucket-ordered targets, l2c_topk.hip): the list of position lrow0 + row belongs to row row_map[.] of the
+        // launch, a padding position (0xFFFFFFFF) emits nothing; ref_map: stream position -> reference index
+        int64_t orow = lrow0 + row;
+        if (row_map) {
+            const uint32_t r = row_map[orow];
+            if (r == 0xFFFFFFFFu) continue;
+            orow = r;
+        }
         // kept entries in list order (unsorted: refine.hip orders candidates by their exact distances anyway)
-        const int64_t o = ((lrow0 + row) * S + split) * (int64_t)LMAX;
+        const int64_t o = (orow * S + split) * (int64_t)LMAX;
 #pragma unroll
         for (int r = 0; r < EPL; ++r) {
             const uint32_t e = (uint32_t)(r * 64 + lane);
@@ -397,11 +407,11 @@ __device__ __forceinline__ void lists_flush(unsigned char *w, uint32_t scnt, int
                 uint2 v = make_uint2(C::IDX_MASK, __float_as_uint(__builtin_inff()));
                 if (e < (uint32_t)lkeep) v = rows[row * C::ROW + e];
                 const uint32_t off = v.x & C::IDX_MASK;
-                cand_idx[o + e] = off == C::IDX_MASK ? 0xFFFFFFFFu : idx_base + off;
+                cand_idx[o + e] = off == C::IDX_MASK ? 0xFFFFFFFFu : ref_map ? ref_map[idx_base + off] : idx_base + off;
                 if (cand_key) cand_key[o + e] = __uint_as_float(v.y);
             }
         }
-        if (lane == 0) cand_tau[(lrow0 + row) * S + split] = C::tauL(w)[row];
+        if (lane == 0) cand_tau[orow * S + split] = C::tauL(w)[row];
     }
 }
 
