@@ -193,8 +193,10 @@ int nabo_index_last_row_pass(const nabo_index *ix, uint8_t *out, int64_t m);
  * [14] padded target rows, [15] operand steps of 16 slots, [16] always 0 (it described the launch cut into pieces, which
  * was removed), [17] buckets of the local tournament seeds when the main launch takes them (option "local_seeds"), else 0,
  * [18] the two-level stream (option "two_level"): 2 the main launch takes it (a query of an index may still decide against it:
- * its probe, or the memory of one that did), 1 the operands are in its slot order only, 0 neither.  kernel (optional): the kernel's name as nabo_index_last_kernel reports it. */
-#define NABO_PLAN_FIELDS 19
+ * its probe, or the memory of one that did), 1 the operands are in its slot order only, 0 neither, [19] target rows of the main
+ * launch (the tail launch takes the rest; all of them without one) -- as planned for an index that takes the two-level stream
+ * or has not decided yet: one that decided against it keeps whole workgroups, [3] x [2] rows.  kernel (optional): the kernel's name as nabo_index_last_kernel reports it. */
+#define NABO_PLAN_FIELDS 20
 int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t k, int32_t drop_first, int32_t n_cand,
                     int32_t n_cu, const char *l2_mode, const char *options, int64_t out[NABO_PLAN_FIELDS], char *kernel,
                     size_t kernel_len);

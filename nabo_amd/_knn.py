@@ -73,7 +73,7 @@ def knn_devices(X, Y, k, devices, metric=EUCLIDEAN, dist_factor=0.25, ref_mask=N
 
 PLAN_FIELDS = ("first_pass", "geometry", "rows_per_wg", "workgroups_main", "workgroups_tail", "splits", "splits_tail", "lkeep",
                "list_len", "tiles_per_split", "tournament_tiles", "tournament_group", "resident_workgroups", "workgroups",
-               "rows_padded", "operand_steps", "pieces", "local_seed_buckets", "two_level")
+               "rows_padded", "operand_steps", "pieces", "local_seed_buckets", "two_level", "rows_main")
 
 
 def query_plan(n_ref, g, m, k, metric=EUCLIDEAN, drop_first=False, n_cand=0, n_cu=256, l2_mode=None, options=None):

@@ -139,6 +139,7 @@ static int query_top(nabo_index *ix, const double *X, int32_t x_on_device, int64
     if (!ix) return api_fail(NABO_E_INVALID, "NULL argument");
     PassCtx top;
     top.coarse_weak = ix->ref.l2.coarse_weak;
+    top.tl_no = ix->ref.l2.tl_verdict == 2;
     PassResult res;
     return query_impl(ix, top, X, x_on_device, m, k, drop_first, out_idx, out_dist, out_on_device, cand_mode, out_bound, &res);
 }

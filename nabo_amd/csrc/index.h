@@ -90,6 +90,7 @@ struct PassCtx {
     const std::vector<uint32_t> *row_map = nullptr;      // rows of this batch -> rows of the top-level query (null at the top)
     bool top = true;               // the top-level call: the per-row pass record starts over
     bool coarse_weak = false;      // nabo_index::Refs::L2::coarse_weak when the query started
+    bool tl_no = false;            // nabo_index::Refs::L2::tl_verdict was "no" when the query started: the caller-order stream
     bool first() const { return pass_level == 0 && !wide_retry; }
 };
 
@@ -117,6 +118,8 @@ struct L2Plan {
     int S = 1, S2 = 1;                   // reference splits of the main / tail launch
     bool one_round = false;              // fewer column-workgroups than slots: splits (+ a tail launch on long streams) fill one round
     int64_t gx = 0, gx_main = 0, gx_tail = 0, rows_pad = 0, tps = 0, tps2 = 0;
+    // first target row of the tail launch: gx_main rows_per_wg, or fewer where the two-level main launch ends on whole rounds
+    int64_t rows_main = 0;
     char kernel[160] = "";
 };
 // entries per lane of the emitted candidate lists (they hold 32 epl entries): 64-entry lists for k' > 24 and the wide retry

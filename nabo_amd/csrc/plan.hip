@@ -238,6 +238,18 @@ int plan_l2(const IndexShape &sh, const PassCtx &ctx, int64_t m, int k, int drop
     // 261 x 1 2.42), and so did cutting the (column, tile) space into equal chunks ("pieces", removed): workgroups of a uniform
     // split stream the same tiles at the same time and share them in L2, unaligned pieces do not (49k x 100k: kernel
     // 1.99 ms as 603 pieces, 1.10 ms as 128 x 4).
+    // split count of a tail launch of `tail` workgroups: the one that takes the smallest part of a round (1: none does)
+    // (at most 8 splits: 11 would fill the chip exactly at 1M x 1M -- kernel 0.6 ms shorter, refine of the tail rows' 11
+    // lists 1.1 ms longer)
+    auto tail_splits = [&](int64_t tail) {
+        int s = 1;
+        double best = 1.0;
+        for (int s2 = 2; s2 <= 8; ++s2) {
+            const double t = (double)((tail * s2 + slots - 1) / slots) / s2;
+            if (t < best - 1e-9) { best = t; s = s2; }
+        }
+        return s;
+    };
     bool one_round = false;
     if (!forced && on_l2c && sh.opt.one_round != 0 && sh.opt.merge_lists != 0 && ctx.pass_level == 0 && !ctx.wide_retry &&
         gx < slots) {
@@ -284,13 +296,7 @@ int plan_l2(const IndexShape &sh, const PassCtx &ctx, int64_t m, int k, int drop
             }
         } else if (gx % slots != 0 && sh.opt.tail_split != 0 && sh.ref_tiles >= 256) {
             const int64_t tail = gx % slots;
-            double best = 1.0;
-            // (at most 8 splits: 11 would fill the chip exactly at 1M x 1M -- kernel 0.6 ms shorter, refine of the tail
-            // rows' 11 lists 1.1 ms longer)
-            for (int s2 = 2; s2 <= 8; ++s2) {
-                const double t = (double)((tail * s2 + slots - 1) / slots) / s2;
-                if (t < best - 1e-9) { best = t; S2 = s2; }
-            }
+            S2 = tail_splits(tail);
             if (S2 > 1) { gx_tail = tail; gx_main = gx - tail; }
         }
     }
@@ -332,6 +338,29 @@ int plan_l2(const IndexShape &sh, const PassCtx &ctx, int64_t m, int k, int drop
         const int64_t rows_main = gx_main * rows_per_wg < m ? gx_main * rows_per_wg : m;
         P->tl_main = P->slots2 && on_l2c && geo == 1 && kcq == 4 && ctx.first() && !cand_mode && gx_main > 0 &&
                      lseed_applies(sh, *P, S, rows_main) && !(gx_tail > 0 && lseed_applies(sh, *P, S2, m - rows_main));
+    }
+    // WHOLE ROUNDS for the two-level main launch.  It runs its rows as POSITIONS of the bucket-ordered copy:
+    // lseed_columns(rows, C) columns of 128, every bucket padding its rows to whole columns -- gx_main workgroups' worth of
+    // rows are up to (C + 1) x 128 positions more, a few workgroups of one more round, each streaming the whole reference set
+    // while the chip idles.  So the main launch takes as many rows as fit gx_main workgroups as positions and the tail
+    // launch the rest, its split count by the tail's rule.  Not where the index decided against the stream (ctx.tl_no: such
+    // data must not pay for a larger tail), and not where the larger tail would no longer be a part of ONE round.
+    P->rows_main = gx_main * rows_per_wg;
+    if (P->tl_main && gx_tail > 0 && !ctx.tl_no) {
+        int lc = 0, lcap = 0;
+        lseed_params(sh, &lc, &lcap);
+        const int64_t rows_tl = (gx_main * rows_per_wg / LSEED_COL_ROWS - (lc + 1)) * LSEED_COL_ROWS;
+        const int64_t tail = rows_tl > 0 ? (m - rows_tl + rows_per_wg - 1) / rows_per_wg : 0;
+        const int s2 = tail > 0 ? tail_splits(tail) : 1;
+        const int64_t tps2_tl = (sh.ref_tiles + s2 - 1) / s2;
+        if (s2 > 1 && tail * s2 <= slots && s2 <= 1024 / L && tps2_tl * s2 <= sh.ref_tiles_alloc && lseed_applies(sh, *P, S, rows_tl)) {
+            P->rows_main = rows_tl;
+            P->gx_tail = tail;
+            P->S2 = s2;
+            P->tps2 = tps2_tl;
+            P->gx = gx_main + tail;
+            P->rows_pad = P->gx * rows_per_wg;
+        }
     }
     // (option coarse_kernel_q runs the one-product operands through the l2q kernel)
     if (use_1 && !on_l2c)
@@ -462,8 +491,9 @@ int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t
     {   // out[17]: the buckets of the local tournament seeds where the main launch takes them (local_seeds.hip), else 0
         int lc = 0, lcap = 0;
         lseed_params(sh, &lc, &lcap);
-        const int64_t rows_main = P.gx_main * P.rows_per_wg < m ? P.gx_main * P.rows_per_wg : m;
+        const int64_t rows_main = P.rows_main < m ? P.rows_main : m;
         out[17] = lseed_applies(sh, P, P.S, rows_main) ? lc : 0;
+        out[19] = rows_main;
     }
     out[18] = P.tl_main ? 2 : P.slots2 ? 1 : 0;      // two-level: 2 the main launch streams one-step, 1 the slot order only
     if (kernel && kernel_len) snprintf(kernel, kernel_len, "%s", P.kernel);

@@ -99,6 +99,7 @@ struct L2Part {
     bool merge = false;              // merge_lists_kernel reduces the S lists of a row to one of `keep` entries (lout slots)
     int keep = 0, lout = 0;
     int64_t end(int64_t m) const { return row0 + rows < m ? row0 + rows : m; }
+    int64_t wgs(int rows_per_wg) const { return (rows + rows_per_wg - 1) / rows_per_wg; }     // of a plain launch (gx, or fewer: a main part cut on whole rounds of positions)
 };
 
 // LOCAL tournament seeds of a one-split launch (local_seeds.hip): the launch's rows sorted by bucket -- assignment on the
@@ -239,9 +240,11 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
                                     stride[i], 0, &ord));
             ix->last.tl_ran = true;
         } else
-        HIP_TRY(l2c_topk_launch(P.kcq, P.geo, xh, yh, (int)p.tps, p.S, (int)p.gx, p.row0 / 32, P.lkeep,
+        // (rows beyond the part's are padding to it: the main part of a plan cut on whole rounds of positions, run in
+        // caller order after all, ends inside a workgroup and the tail launch takes over there)
+        HIP_TRY(l2c_topk_launch(P.kcq, P.geo, xh, yh, (int)p.tps, p.S, (int)p.wgs(P.rows_per_wg), p.row0 / 32, P.lkeep,
                                 p.idx->as<uint32_t>(), p.merge ? p.key->as<float>() : nullptr, p.tau->as<float>(),
-                                pad_tile, st, q.m, seed[i], stride[i], p.row0));
+                                pad_tile, st, p.end(q.m), seed[i], stride[i], p.row0));
         // the tail launch (a fraction of a round, reference splits) leaves most CUs idle: the refine of the main
         // launch's rows (an HBM gather) runs beside it on the second stream
         if (i == 0 && part[1].gx > 0 && !q.cand_mode && sh.opt.refine_overlap != 0) {
@@ -384,12 +387,14 @@ static int query_l2(nabo_index *ix, const PassCtx &ctx, Query &q)
     }
     if ((rc = ensure_packed(ix, P.use_1 ? 2 : P.use_h ? 1 : 0))) return rc;
     // (before anything takes the operands' address: a change of options since the pack moves them)
-    if (ctx.first() && (lseed_applies(sh, P, P.S, P.gx_main * P.rows_per_wg < m ? P.gx_main * P.rows_per_wg : m) ||
-                          (P.gx_tail > 0 && lseed_applies(sh, P, P.S2, m - P.gx_main * P.rows_per_wg))) &&
+    if (ctx.first() && (lseed_applies(sh, P, P.S, P.rows_main < m ? P.rows_main : m) ||
+                          (P.gx_tail > 0 && lseed_applies(sh, P, P.S2, m - P.rows_main))) &&
         (rc = ensure_local_seeds(ix)))
         return rc;
     if (q.top) ix->last.row_pass.assign((size_t)m, (uint8_t)(P.use_1 ? NABO_PASS_ONE_PRODUCT : NABO_PASS_SECOND));
-    const int64_t rows_main = P.gx_main * P.rows_per_wg;
+    // (the tail launch begins at row P.rows_main: whole workgroups of the main launch, or fewer rows where the two-level
+    // main launch ends on whole rounds of POSITIONS, plan.hip)
+    const int64_t rows_main = P.rows_main;
     L2Part part[2] = {
         {P.gx_main, 0, rows_main, P.S, P.tps, &ws.cand_idx, &ws.cand_tau, &ws.cand_key, &ws.cand_mi, &ws.cand_mt, &ws.taupre},
         {P.gx_tail, rows_main, P.gx_tail * P.rows_per_wg, P.S2, P.tps2, &ws.cand_idx2, &ws.cand_tau2, &ws.cand_key2,
@@ -411,9 +416,12 @@ static int query_l2(nabo_index *ix, const PassCtx &ctx, Query &q)
         p.merge = merging && p.S > 1;
         p.keep = seeded_merge ? (p.S * q.L < 128 ? p.S * q.L : 128) : P.lkeep;
         p.lout = seeded_merge ? p.keep : q.L;
-        if ((rc = p.idx->reserve((size_t)p.rows * p.S * q.L * sizeof(uint32_t) + 16))) return rc;
-        if ((rc = p.tau->reserve((size_t)p.rows * p.S * sizeof(float) + 16))) return rc;
-        if (p.merge && ((rc = p.key->reserve((size_t)p.rows * p.S * q.L * sizeof(float))) ||
+        // (whole workgroups: a plain launch writes the lists of all its rows, and a main part cut on whole rounds of
+        // positions is no multiple of a workgroup's rows)
+        const size_t rows_wg = (size_t)(p.wgs(P.rows_per_wg) * P.rows_per_wg);
+        if ((rc = p.idx->reserve(rows_wg * p.S * q.L * sizeof(uint32_t) + 16))) return rc;
+        if ((rc = p.tau->reserve(rows_wg * p.S * sizeof(float) + 16))) return rc;
+        if (p.merge && ((rc = p.key->reserve(rows_wg * p.S * q.L * sizeof(float))) ||
                         (rc = p.mi->reserve((size_t)p.rows * p.lout * sizeof(uint32_t))) ||
                         (rc = p.mt->reserve((size_t)p.rows * sizeof(float)))))
             return rc;
