@@ -103,9 +103,12 @@ int nabo_index_destroy(nabo_index *ix);
  * 0 = 16384, at most 32768), "two_level" (the two-level stream of the one-product pass, 28 < g <= 59: targets and references
  * streamed in bucket order, a tile's second operand step only where its first step's lower bound passes a threshold:
  * 0 = off, 1 = on the launches that take local seeds by default, 2 = on every one-split launch of the 23-entry lists, also
- * at g = 29, where the plain operands need one step only), "two_level_share" and "two_level_stretch" (its mode control: the
- * share of completed tiles, percent, 0 = 25, a wave tolerates before it runs the two-step loop for a stretch of tiles,
- * 0 = 64, doubled while the probes behind it fail).  When the two-level stream ran, nabo_index_last_kernel reports its
+ * at g = 29, where the plain operands need one step only), "two_level_share", "two_level_burst" and "two_level_stretch" (its
+ * mode control: a wave keeps one account per bucket of the references -- "two_level_burst" completed tiles of credit, 0 = 3,
+ * at most 64, plus "two_level_share" percent of the bucket's tiles so far, 0 = 25 -- and runs the two-step loop to the end of
+ * a bucket whose account is spent; "two_level_stretch" > 0 selects the control before that one instead: one account per
+ * one-step segment, burst 0 = 8, and blind two-step stretches, the first of that many tiles, doubled while the probes behind
+ * them fail; 0, the default, the per-bucket control).  When the two-level stream ran, nabo_index_last_kernel reports its
  * tile counters behind the kernel's name: " [two-level tiles: one-step N, refetched N, two-step N]", summed over the waves.
  * Unknown names: NABO_E_INVALID.
  * The library reads TWO environment variables, once, in nabo_index_create: NABO_L2_MODE = f32 | f16x3 (which Euclidean /

@@ -42,9 +42,10 @@ struct Options {
     int local_seeds = 1, local_anchors = 0, local_cap = 0;
     // the two-level stream of the one-product pass (l2c_topk.hip; operands in the two-level slot order, l2c_slots.h): 0 off,
     // 1 where local seeds apply by default and the slots fit, 2 on every one-split geometry-B launch of the first pass
-    // (switches the local seeds' buckets on at any size); refetch share (percent, 0: 25) and first two-step stretch
-    // (tiles, 0: 64) of the kernel's mode control pinned for A/B runs
-    int two_level = 1, two_level_share = 0, two_level_stretch = 0;
+    // (switches the local seeds' buckets on at any size); refetch share (percent, 0: 25) and credit (refetches, 0: the
+    // control's default) of the kernel's mode control pinned for A/B runs; stretch > 0: the control that keeps no account
+    // per reference bucket, with that first two-step stretch (tiles)
+    int two_level = 1, two_level_share = 0, two_level_stretch = 0, two_level_burst = 0;
 };
 bool option_set(Options &o, const char *name, int64_t value);
 
@@ -186,7 +187,8 @@ struct nabo_index {
             // 2 no (a probe said so, or the waves of a launch proper ran most of their tiles two-step): the queries stream
             // the caller-order operands and the ordered copy is not built.  A HEURISTIC, and remembered across set_ref /
             // set_mask -- the usual caller refreshes the same kind of data -- for TL_VERDICT_REPACKS repacks (tl_age)
-            nabo::DevBuf yord, yordmap;
+            // yordend [local_C] (int32): the buckets' ends in tiles of the copy (lseed_bucket_ends), the mode control's table.
+            nabo::DevBuf yord, yordmap, yordend;
             int64_t ord_tiles = 0;
             bool ord_built = false;
             int tl_verdict = 0, tl_age = 0;

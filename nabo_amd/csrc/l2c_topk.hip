@@ -330,7 +330,8 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                                                           const uint32_t *__restrict__ row_map,
                                                           const uint32_t *__restrict__ ref_map,
                                                           unsigned long long *__restrict__ tl_stats, int tl_share,
-                                                          int tl_stretch)
+                                                          int tl_stretch, const int32_t *__restrict__ tl_bend, int tl_nbend,
+                                                          int tl_burst)
 {
     // TWO-LEVEL stream (geometry B on two operand steps; row_map != null selects it at run time, every other launch of this
     // instantiation runs the plain loop below): operands in the two-level slot order (l2c_slots.h), targets AND references
@@ -588,17 +589,30 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
             };
             // MODE CONTROL, wave-uniform, in scalar registers, and outside the hot path: a refetch costs a memory round trip
             // and twelve MFMAs out of line, so the one-step loop pays while fewer than `share` percent of its tiles need one
-            // (a one-step tile is 104 SIMD cycles per pair against 168).  A leaky bucket in the refetch path keeps the
-            // account -- every refetch takes 100, every tile of the segment gives `share`, TL_BURST refetches of credit --
-            // and when it is overdrawn the wave leaves for a stretch of the plain two-step loop, then probes again; the
-            // stretch doubles while the probes fail (a probe that lasted fewer than TL_PROBE tiles) and starts over after
-            // one that held.  Unclustered data pays the probes only.
-            constexpr int TL_BURST = 8, TL_PROBE = 64;
+            // (a one-step tile is 104 SIMD cycles per pair against 168).  Both sides are bucket-ordered, and whether a tile
+            // passes is almost a property of the pair (the wave's bucket, the reference bucket): three quarters of the pairs
+            // have no passing tile at all, 6 % hardly any other (tools/two_level_mode_model.py).  So the account is kept PER
+            // REFERENCE BUCKET (tl_bend: the buckets' ends in tiles, non-decreasing): the refetch path moves a cursor past every end
+            // <= its tile and opens a new account on every move; a bucket's account pays burst + share x (tiles since the
+            // bucket's start) / 100 refetches, and the refetch that takes the last of it sends the wave into the two-step
+            // loop TO THAT BUCKET'S END (the pair of tiles in flight is finished first and may refetch once more: at most
+            // burst + 1 + share T_b / 100 refetches per wave and bucket of T_b tiles).  Dense pairs cost a few refetches
+            // each, sparse ones nothing, and no stretch is guessed.
+            // The control before this one (tl_stretch > 0, or a launch without the table) does not know where it is in the
+            // stream: one leaky bucket per one-step segment -- every refetch takes 100, every tile gives `share`, `burst`
+            // refetches of credit -- and when it is overdrawn the wave leaves for a stretch of the plain two-step loop, then
+            // probes again; the stretch doubles while the probes fail (a probe that lasted fewer than TL_PROBE tiles) and
+            // starts over after one that held.  Unclustered data pays the probes only.
+            constexpr int TL_PROBE = 64;
+            const bool by_bucket = ordered && tl_bend != nullptr && tl_stretch <= 0;
+            const int burst = tl_burst > 0 ? tl_burst : (by_bucket ? 3 : 8);
             const int share = tl_share > 0 ? tl_share : 25;
             const int stretch0 = tl_stretch > 0 ? ((tl_stretch < (1 << 20) ? tl_stretch : 1 << 20) + 1) & ~1 : 64;
             int stretch = ordered ? stretch0 : 1 << 30;
             uint32_t n_one = 0, n_ref = 0, n_two = 0;
             int seg_end = 0, seg_t0 = 0, seg_ref = 0;
+            int bk_cur = 0, bk_t0 = 0, bk_ref = 0;         // the cursor's bucket: index, first tile, refetches charged to it
+            int t2_end = 0;                                // where the next two-step stretch ends
             // A tile's second step is fetched ON DEMAND, not kept in the ring's idle registers: 16 waves of a CU that load
             // whole tiles at the one-step loop's rate ask more of the CU's vector cache than it delivers (4 KB per tile and
             // wave against ~100 SIMD cycles per pair of row-blocks) -- with every tile loaded whole the step took 143 ms
@@ -626,7 +640,24 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                     flush_pending(old, t - 1);
                     __builtin_amdgcn_s_setprio(0);
                     ++seg_ref;
-                    if (seg_ref * 100 > TL_BURST * 100 + share * (t - seg_t0)) seg_end = 0;      // overdrawn: leave after this pair of tiles
+                    if (by_bucket) {
+                        bool moved = false;
+                        while (bk_cur < tl_nbend) {
+                            const int e = tl_bend[bk_cur];
+                            if (e > t - 1) break;
+                            bk_t0 = e;
+                            ++bk_cur;
+                            moved = true;
+                        }
+                        bk_ref = moved ? 1 : bk_ref + 1;
+                        if (seg_end != 0 && (bk_ref + 1) * 100 > burst * 100 + share * (t - 1 - bk_t0)) {
+                            // the account's last: leave after this pair of tiles, two-step to the end of THIS bucket in the
+                            // loop's twos (the pair's other tile may move the cursor on)
+                            const int e = bk_cur < tl_nbend ? (tl_bend[bk_cur] + 1) & ~1 : t_end;
+                            t2_end = e < t_end ? e : t_end;
+                            seg_end = 0;
+                        }
+                    } else if (seg_ref * 100 > burst * 100 + share * (t - seg_t0)) seg_end = 0;      // overdrawn: leave after this pair of tiles
                 }
             };
             // Segments alternate; each ends with its last tile pending in accO -- bounds after a one-step segment (completed
@@ -647,10 +678,15 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                     complete(accO, t - 1);
                     n_one += (uint32_t)(t - seg_t0);
                     n_ref += (uint32_t)seg_ref;       // (refetches of the loop only: the segment's last tile is completed whatever its bounds say)
-                    if (t - seg_t0 >= TL_PROBE) stretch = stretch0;       // the probe held
+                    // (a bucket that ended inside the pair just finished leaves nothing to run two-step: the one-step loop
+                    // goes on behind the filter site; flipped below)
+                    if (by_bucket) one_step = t2_end > t;
+                    else if (t - seg_t0 >= TL_PROBE) stretch = stretch0;       // the probe held
                 } else {
-                    const int t2_end = stretch < t_end - t ? t + stretch : t_end;
-                    if (stretch < (1 << 24)) stretch *= 2;
+                    if (!by_bucket) {
+                        t2_end = stretch < t_end - t ? t + stretch : t_end;
+                        if (stretch < (1 << 24)) stretch *= 2;
+                    }
                     if (ordered) tile_load(a0, t);      // (a plain launch: its one stretch starts on the preamble's tile)
                     for (; t < t2_end; t += 2) {
                         tile_step(a0, a1, accE, accO, t);
@@ -886,7 +922,8 @@ static hipError_t claunch_geo(const unsigned char *Xpk, const unsigned char *Ypk
     hipLaunchKernelGGL((l2c_topk_kernel<KS, EPL, ROWN, NBv, NRECv, WAVES, WPS>), dim3(gx, S), block, lds, st, Xpk, Ypk,
                        tiles_per_split, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, 0, rows_valid, tau_init, tau_stride,
                        tau_row0, ord ? ord->row_map : nullptr, ord ? ord->ref_map : nullptr, ord ? ord->stats : nullptr,
-                       ord ? ord->share_pct : 0, ord ? ord->stretch : 0);
+                       ord ? ord->share_pct : 0, ord ? ord->stretch : 0, ord ? ord->bucket_end : nullptr,
+                       ord && ord->bucket_end ? ord->nbucket : 0, ord ? ord->burst : 0);
     return hipGetLastError();
 }
 

@@ -59,11 +59,16 @@ void l2q_topk_geometry(int kc, int *rows_per_wg, int *wg_per_cu, int *lkeep_max)
 // reference ref_map[j]; lists and seeds are indexed by the launch's rows, emitted candidates are reference indices.
 // stats [3] (may be null): tiles run one-step, tiles of those refetched inside the loop (a segment's last tile, completed
 // unconditionally, is not counted), tiles run two-step, summed over the waves.
-// share_pct / stretch: the mode control's refetch share and first two-step stretch (0: the kernel's defaults).
+// share_pct / burst: the mode control's refetch share and credit (0: the kernel's defaults).  bucket_end [nbucket] (may be
+// null): the reference buckets' ends in tiles of the stream, non-decreasing (lseed_bucket_ends) -- the mode control keeps its
+// account per bucket and runs two-step to a bucket's end.  stretch > 0, or no table: the control before that one, one
+// account per one-step segment and blind two-step stretches, the first of `stretch` tiles (0: 64).
 struct L2cOrdered {
     const uint32_t *row_map, *ref_map;
     unsigned long long *stats;
     int share_pct, stretch;
+    const int32_t *bucket_end;
+    int nbucket, burst;
 };
 int l2c_pick_kc(int g);
 int l2c_geometry(int kc, int lkeep_want, int pin);
@@ -91,6 +96,7 @@ hipError_t lseed_sort_launch(int kc, bool is_ref, const unsigned char *pk, int64
 hipError_t lseed_fill_launch(int kc, const unsigned char *src, int64_t pad_cell, unsigned char *dst, int64_t ncell, hipStream_t st);
 hipError_t lseed_layout_launch(int C, const uint32_t *ref_cnt, const uint32_t *row_cnt, int cap, int lkeep, int tile0,
                                const int rest[4], int64_t *lay, int *ranges, int64_t ncol, hipStream_t st);
+hipError_t lseed_ends_launch(int C, const int64_t *lay, int32_t *end, hipStream_t st);
 hipError_t lseed_move_launch(int kc, const unsigned char *src, int64_t ncell, const uint32_t *key, const uint32_t *blockoff, int C,
                              const int64_t *lay, int cap, int64_t pad_cell, unsigned char *dst, uint32_t *row_map, hipStream_t st);
 

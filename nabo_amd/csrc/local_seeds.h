@@ -106,6 +106,13 @@ NABO_HD inline void lseed_layout_full(int C, const uint32_t *ref_cnt, int64_t *b
     base[C] = pos;
     padb[C] = pade[C] = 0;
 }
+// The buckets' ENDS in tiles of the full ordered copy (pade of lseed_layout_full): end[b] = first tile behind bucket b --
+// non-decreasing, an empty bucket repeats its predecessor's end, the last one <= lseed_ordered_tiles.  The table the
+// filter's mode control walks (l2c_topk.hip).
+NABO_HD inline void lseed_bucket_ends(int C, const int64_t *pade, int32_t *end)
+{
+    for (int b = 0; b < C; ++b) end[b] = (int32_t)(pade[b] / 32);
+}
 // tiles the ordered stream runs over (even: the filter's loop runs in twos), without the two padding tiles behind them
 inline int64_t lseed_ordered_tiles(int64_t ref_tiles, int C) { return (ref_tiles + C + 1) / 2 * 2; }
 

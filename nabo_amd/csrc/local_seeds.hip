@@ -189,6 +189,12 @@ __global__ __launch_bounds__(256) void lseed_layout_kernel(int C, const uint32_t
     for (int b = threadIdx.x; b <= C; b += 256) lseed_fill_columns(b, C, ref_cnt, cap, lkeep, tile0, rest, base, pade, ranges, ncol);
 }
 
+// lay (of the full ordered copy) -> the buckets' ends in tiles
+__global__ __launch_bounds__(64) void lseed_ends_kernel(int C, const int64_t *__restrict__ lay, int32_t *__restrict__ end)
+{
+    if (threadIdx.x == 0) lseed_bucket_ends(C, lay + 2 * (C + 1), end);
+}
+
 // cell i -> position base[bucket] + (its block's offset + its rank); a reference beyond its bucket's cap stays behind.
 // row_map [position] = i (the query side).
 template <int KS>
@@ -296,6 +302,13 @@ hipError_t lseed_layout_launch(int C, const uint32_t *ref_cnt, const uint32_t *r
     const LseedRange r = {rest[0], rest[1], rest[2], rest[3]};
     hipLaunchKernelGGL(lseed_layout_kernel, dim3(1), dim3(256), 0, st, C, ref_cnt, row_cnt, cap, lkeep, tile0, r, lay,
                        reinterpret_cast<LseedRange *>(ranges), ncol);
+    return hipGetLastError();
+}
+
+// end [C]: the buckets' ends in tiles, from the layout lseed_layout_launch made of the full ordered copy (cap == 0)
+hipError_t lseed_ends_launch(int C, const int64_t *lay, int32_t *end, hipStream_t st)
+{
+    hipLaunchKernelGGL(lseed_ends_kernel, dim3(1), dim3(64), 0, st, C, lay, end);
     return hipGetLastError();
 }
 

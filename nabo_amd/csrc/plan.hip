@@ -40,13 +40,15 @@ static const OptionName LOCAL_SEED_OPTION_NAMES[] = {
 // The two-level stream's options (l2c_topk.hip): tests/test_two_level_gpu.py runs it on small shapes against the oracle.
 static const OptionName TWO_LEVEL_OPTION_NAMES[] = {
     {"two_level", &Options::two_level}, {"two_level_share", &Options::two_level_share}, {"two_level_stretch", &Options::two_level_stretch},
+    {"two_level_burst", &Options::two_level_burst},
 };
 
 bool option_set(Options &o, const char *name, int64_t value)
 {
     for (const OptionName &e : TWO_LEVEL_OPTION_NAMES)
-        if (strcmp(e.name, name) == 0) {            // clamped: 0 .. 2, percent, tiles
-            const int64_t hi = e.field == &Options::two_level ? 2 : e.field == &Options::two_level_share ? 100 : 1 << 20;
+        if (strcmp(e.name, name) == 0) {            // clamped: 0 .. 2, percent, refetches, tiles
+            const int64_t hi = e.field == &Options::two_level ? 2 : e.field == &Options::two_level_share ? 100
+                               : e.field == &Options::two_level_burst ? 64 : 1 << 20;
             o.*(e.field) = (int)(value < 0 ? 0 : value > hi ? hi : value);
             return true;
         }

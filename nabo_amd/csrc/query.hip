@@ -204,7 +204,8 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
         if (p.gx == 0) continue;
         const int64_t prow = ordered ? lseed_columns(p.end(q.m) - p.row0, l2.local_C) * LSEED_COL_ROWS : 0;
         const int64_t gx_ord = (prow + P.rows_per_wg - 1) / P.rows_per_wg;
-        L2cOrdered ord = {ws.lmap.as<uint32_t>(), l2.yordmap.as<uint32_t>(), nullptr, sh.opt.two_level_share, sh.opt.two_level_stretch};
+        L2cOrdered ord = {ws.lmap.as<uint32_t>(), l2.yordmap.as<uint32_t>(), nullptr, sh.opt.two_level_share, sh.opt.two_level_stretch,
+                          l2.yordend.as<int32_t>(), l2.local_C, sh.opt.two_level_burst};
         if (i == 0 && ordered) {
             if ((rc = ws.tlstats.reserve(3 * sizeof(unsigned long long)))) return rc;
             ord.stats = ws.tlstats.as<unsigned long long>();
@@ -226,6 +227,9 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
                                     p.idx->as<uint32_t>(), nullptr, p.tau->as<float>(), l2.ord_tiles, st, prow, seed[i], stride[i], 0, &ord));
             HIP_TRY(hipMemcpyAsync(probe, ws.tlstats.p, sizeof(probe), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
+#ifdef NABO_TL_TRACE        // (a build of its own, _build.py --out ... -DNABO_TL_TRACE: the probe's counters, for the records)
+            fprintf(stderr, "two-level probe: one-step %llu, refetched %llu, two-step %llu\n", probe[0], probe[1], probe[2]);
+#endif
             l2.tl_verdict = probe[0] * 10 < (probe[0] + probe[2]) * 3 ? 2 : 1;
             l2.tl_age = 0;
             if (l2.tl_verdict == 2) ordered = false;

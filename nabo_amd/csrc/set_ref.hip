@@ -119,11 +119,13 @@ int ensure_local_seeds(nabo_index *ix)
         // bucket in whole tiles, and the map from position to reference index.  The copy starts as padding cells (+inf
         // norm): what the buckets leave of its ref_tiles + C tiles, and the two tiles behind them the filter's ring reads.
         const int64_t ot = lseed_ordered_tiles(sh.ref_tiles, C);
-        if ((rc = l2.yord.reserve((size_t)(ot + 2) * sh.kc1 * 1024 + 128)) || (rc = l2.yordmap.reserve((size_t)(ot + 2) * 32 * sizeof(uint32_t))))
+        if ((rc = l2.yord.reserve((size_t)(ot + 2) * sh.kc1 * 1024 + 128)) || (rc = l2.yordmap.reserve((size_t)(ot + 2) * 32 * sizeof(uint32_t))) ||
+            (rc = l2.yordend.reserve((size_t)C * sizeof(int32_t))))
             return rc;
         HIP_TRY(lseed_fill_launch(sh.kc1, ypk, (sh.ref_tiles_alloc - 1) * 32, l2.yord.as<unsigned char>(), (ot + 2) * 32, st));
         HIP_TRY(hipMemsetAsync(l2.yordmap.p, 0xFF, (size_t)(ot + 2) * 32 * sizeof(uint32_t), st));
         HIP_TRY(lseed_layout_launch(C, l2.lrefcnt.as<uint32_t>(), nullptr, 0, 1, 0, rest, ws.llay.as<int64_t>(), nullptr, 0, st));
+        HIP_TRY(lseed_ends_launch(C, ws.llay.as<int64_t>(), l2.yordend.as<int32_t>(), st));      // (the query reuses llay: the ends are kept)
         HIP_TRY(lseed_move_launch(sh.kc1, ypk, sh.n, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), 0,
                                   (sh.ref_tiles_alloc - 1) * 32, l2.yord.as<unsigned char>(), l2.yordmap.as<uint32_t>(), st));
         l2.ord_tiles = ot;

@@ -2,7 +2,9 @@
 in one process on one GPU -- on bench.py's clustered data or on ONE broad Gaussian cloud, which bench.py cannot generate and
 where the stream gains nothing: the mode control has to keep its cost to the probes.
     python tools/bench_two_level.py [steps] [m n g k] [--cloud] [name=value,...;name=value,...;...]
-Configurations are separated by ';' and run in the order given, the first one again at the end (the spread)."""
+Configurations are separated by ';' and run in the order given, the first one again at the end (the spread).  The mode
+control's knobs are index options like any other: "two_level_burst=3,two_level_share=25" is the per-bucket control with that
+account, "two_level_stretch=64" the control before it."""
 import json
 import os
 import sys
