@@ -60,6 +60,14 @@ UMAP_SYMBOLS = ["nabo_umap_create", "nabo_umap_destroy", "nabo_umap_set_params",
                 "nabo_umap_graph_size", "nabo_umap_get_graph", "nabo_umap_set_embedding", "nabo_umap_get_embedding",
                 "nabo_umap_run", "nabo_umap_rewind", "nabo_umap_last_epoch_counts", "nabo_umap_last_ms", "nabo_umap_geometry"]
 
+# every symbol include/nabo_umap_transform.h declares (UMAP transform: target cells placed in a fitted reference embedding)
+UMAP_TRANSFORM_SYMBOLS = ["nabo_umap_transform_create", "nabo_umap_transform_destroy", "nabo_umap_transform_set_params",
+                          "nabo_umap_transform_set_embedding", "nabo_umap_transform_set_cells", "nabo_umap_transform_query",
+                          "nabo_umap_transform_set_knn", "nabo_umap_transform_set_graph", "nabo_umap_transform_get_graph",
+                          "nabo_umap_transform_set_positions", "nabo_umap_transform_get_positions", "nabo_umap_transform_run",
+                          "nabo_umap_transform_rewind", "nabo_umap_transform_last_run_counts", "nabo_umap_transform_last_ms",
+                          "nabo_umap_transform_geometry"]
+
 # every symbol include/nabo_community.h declares (communities of the reference graph: seeded synchronous Louvain)
 COMMUNITY_SYMBOLS = ["nabo_community_create", "nabo_community_destroy", "nabo_community_set_params", "nabo_community_run",
                      "nabo_community_labels", "nabo_community_history", "nabo_community_modularity", "nabo_community_split",
@@ -174,6 +182,22 @@ def lib():
     L.nabo_umap_last_epoch_counts.argtypes = [vp, vp, vp, vp]
     L.nabo_umap_last_ms.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
     L.nabo_umap_geometry.argtypes = [C.POINTER(i32)]
+    L.nabo_umap_transform_create.argtypes = [C.POINTER(vp), i32, i64, i32]
+    L.nabo_umap_transform_destroy.argtypes = [vp]
+    L.nabo_umap_transform_set_params.argtypes = [vp, i64, i32, dbl, dbl, dbl, C.c_uint64]
+    L.nabo_umap_transform_set_embedding.argtypes = [vp, vp]
+    L.nabo_umap_transform_set_cells.argtypes = [vp, vp, i32, i32, dbl]
+    L.nabo_umap_transform_query.argtypes = [vp, i64, i64, vp, i32]
+    L.nabo_umap_transform_set_knn.argtypes = [vp, i64, i64, vp, vp, i32]
+    L.nabo_umap_transform_set_graph.argtypes = [vp, i64, i64, vp, vp, i32]
+    L.nabo_umap_transform_get_graph.argtypes = [vp, vp, vp, vp]
+    L.nabo_umap_transform_set_positions.argtypes = [vp, vp]
+    L.nabo_umap_transform_get_positions.argtypes = [vp, vp]
+    L.nabo_umap_transform_run.argtypes = [vp, i64, C.POINTER(i64)]
+    L.nabo_umap_transform_rewind.argtypes = [vp]
+    L.nabo_umap_transform_last_run_counts.argtypes = [vp, vp, vp, vp]
+    L.nabo_umap_transform_last_ms.argtypes = [vp, C.POINTER(dbl)]
+    L.nabo_umap_transform_geometry.argtypes = [C.POINTER(i32)]
     L.nabo_community_create.argtypes = [C.POINTER(vp), i32, i64, vp, vp, vp, dbl]
     L.nabo_community_destroy.argtypes = [vp]
     L.nabo_community_set_params.argtypes = [vp, dbl, C.c_uint64, i32, i32, i32]
@@ -206,8 +230,8 @@ def lib():
     L.nabo_potential_last_ms.argtypes = [vp, C.POINTER(dbl)]
     L.nabo_potential_geometry.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     for name in (SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS + UMAP_SYMBOLS
-                 + COMMUNITY_SYMBOLS + POTENTIAL_SYMBOLS):
-        if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy", "nabo_umap_destroy", "nabo_community_destroy",
+                 + UMAP_TRANSFORM_SYMBOLS + COMMUNITY_SYMBOLS + POTENTIAL_SYMBOLS):
+        if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy", "nabo_umap_destroy", "nabo_umap_transform_destroy", "nabo_community_destroy",
                         "nabo_potential_destroy"):
             getattr(L, name).restype = C.c_int
     _lib = L

@@ -6,6 +6,11 @@ index, builds umap's fuzzy graph on the device and runs the optimisation as sync
 the same bits every time.  include/nabo_umap.h holds the definition; umap-learn's own floating-point results and its
 random stream are not pinned.  What stays on the host is small: the fit of the curve's a and b and the
 start positions.
+
+`umap_transform` / `make_target_umap` place a SECOND set of cells, the targets, in a fitted embedding that does not move
+(`nabo_umap_transform_*`, include/nabo_umap_transform.h, nabo_amd/csrc/umap_transform.hip): what
+umap-learn users call `UMAP.transform`.  A target's result depends on its row, its global row number, the reference and
+the parameters only, so any split into batches gives the same bits.
 """
 import ctypes as C
 
@@ -350,3 +355,259 @@ def make_umap(pca_h5, use_comps, umap_dims, n_neighbors, spread, repulsion_stren
         print("UMAP of %d cells in %d dimensions: %d neighbours, %d epochs"
               % (len(cells), int(umap_dims), int(n_neighbors), default_n_epochs(len(cells)) if n_epochs is None else int(n_epochs)))
     return pd.DataFrame(Y, index=[x + index_suffix for x in cells], columns=["Dim" + str(x) for x in range(1, int(umap_dims) + 1)])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# transform: target cells placed in a fitted reference embedding
+
+TRANSFORM_MS = ("graph", "knn", "run")
+
+
+def transform_geometry():
+    """lanes that share one target's list in the optimise kernel (the order of a target's sum); needs no device"""
+    g = C.c_int32()
+    _lib.check(_lib.lib().nabo_umap_transform_geometry(C.byref(g)))
+    return int(g.value)
+
+
+def default_transform_epochs(m):
+    """umap-learn's choice for transform: 100 for up to 10000 targets, 30 above"""
+    return 100 if int(m) <= 10000 else 30
+
+
+def _check_target_lists(idx, val, n_ref, memberships=False):
+    """idx, val [m, k] of a batch: val the ascending distances, or memberships in [0, 1]"""
+    try:
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        val = np.ascontiguousarray(val, dtype=np.float64)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("ERROR: idx must be integers and %s numbers" % ("memb" if memberships else "dist"))
+    if idx.ndim != 2 or idx.shape != val.shape or idx.shape[0] < 1:
+        raise ValueError("ERROR: idx and %s must both be [m, k], m at least 1" % ("memb" if memberships else "dist"))
+    k = idx.shape[1]
+    if k < 2 or k > _lib.MAX_K or k > n_ref:
+        raise ValueError("ERROR: k=%d must be in [2, %d] and not above n_ref=%d" % (k, _lib.MAX_K, n_ref))
+    if idx.min() < 0 or idx.max() >= n_ref:
+        raise ValueError("ERROR: idx holds an entry that is not a reference cell in [0, %d)" % n_ref)
+    if memberships:
+        if not np.isfinite(val).all() or (val < 0).any() or (val > 1).any():
+            raise ValueError("ERROR: memb must be finite and in [0, 1]")
+    elif not np.isfinite(val).all() or (val < 0).any() or (np.diff(val, axis=1) < 0).any():
+        raise ValueError("ERROR: dist must be finite, not negative and ascending along every row")
+    return idx, val
+
+
+def _neighbours(n_neighbors, n_ref):
+    k = _count(n_neighbors, "n_neighbors", 2)
+    if k > _lib.MAX_K or k > n_ref:
+        raise ValueError("ERROR: n_neighbors=%d must be in [2, %d] and not above n_ref=%d" % (k, _lib.MAX_K, n_ref))
+    return k
+
+
+class UmapTransform(Handle):
+    """A fitted reference embedding resident on one device (nabo_umap_transform_create) and one batch of target cells
+    at a time: the handle the tests and tools/bench_umap_transform.py step through; `umap_transform` is the one-call
+    form."""
+    _destroy = "nabo_umap_transform_destroy"
+
+    def __init__(self, n_ref, dims=2, device=0, n_epochs=None, negative_sample_rate=5, repulsion_strength=1.0, a=None, b=None,
+                 seed=0):
+        self.n_ref, self.dims = _count(n_ref, "n_ref", 2), _count(dims, "dims", 2)
+        if self.dims > 3:
+            raise ValueError("ERROR: dims must be 2 or 3")
+        self.m = self.k = self.g = 0
+        p = self._params(n_epochs, negative_sample_rate, repulsion_strength, a, b, seed)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().nabo_umap_transform_create(C.byref(h), int(device), self.n_ref, self.dims))
+        self._h = h
+        self._apply(p)
+
+    def _params(self, n_epochs, negative_sample_rate, repulsion_strength, a, b, seed):
+        if (a is None) != (b is None):
+            raise ValueError("ERROR: give both a and b or neither")
+        if a is None:
+            a, b = find_ab_params(1.0, 0.1)
+        return dict(n_epochs=100 if n_epochs is None else _count(n_epochs, "n_epochs", 1),
+                    negative_sample_rate=_count(negative_sample_rate, "negative_sample_rate", 1),
+                    repulsion_strength=_number(repulsion_strength, "repulsion_strength"), a=_number(a, "a", True),
+                    b=_number(b, "b", True), seed=_count(seed, "seed", 0) & (2 ** 64 - 1))
+
+    def _apply(self, p):
+        _lib.check(_lib.lib().nabo_umap_transform_set_params(self._h, p["n_epochs"], p["negative_sample_rate"],
+                                                             p["repulsion_strength"], p["a"], p["b"], p["seed"]))
+        self.params = p
+
+    def set_params(self, **kw):
+        """any of n_epochs, negative_sample_rate, repulsion_strength, a and b, seed; rewinds a loaded batch's schedule"""
+        unknown = sorted(set(kw) - set(self.params))
+        if unknown:
+            raise ValueError("ERROR: unknown parameter(s): %s" % ", ".join(unknown))
+        p = dict(self.params, **kw)
+        self._apply(self._params(p["n_epochs"], p["negative_sample_rate"], p["repulsion_strength"], p["a"], p["b"], p["seed"]))
+        return self
+
+    def set_embedding(self, Y):
+        """the fitted reference positions [n_ref, dims]"""
+        _lib.check(_lib.lib().nabo_umap_transform_set_embedding(self._h, _positions(Y, self.n_ref, self.dims, "Y").ctypes.data))
+        return self
+
+    def set_cells(self, X, metric=EUCLIDEAN, dist_factor=0.25):
+        """the reference cells [n_ref, n_comps] as a resident k-NN index, kept for every batch that follows"""
+        X = _cells(X, self.n_ref)
+        _lib.check(_lib.lib().nabo_umap_transform_set_cells(self._h, X.ctypes.data, X.shape[1], int(metric), float(dist_factor)))
+        self.g = X.shape[1]
+        return self
+
+    def _first_row(self, first_row):
+        return _count(first_row, "first_row", 0)
+
+    def query(self, Z, n_neighbors, first_row=0):
+        """one batch from its cells Z [m, n_comps]: the lists come from the resident index and never visit the host"""
+        if not self.g:
+            raise ValueError("ERROR: no reference cells: call set_cells first")
+        Z = _cells(Z)
+        if Z.shape[0] < 1 or Z.shape[1] != self.g:
+            raise ValueError("ERROR: Z must be [m, %d] with at least one row" % self.g)
+        k, first_row = _neighbours(n_neighbors, self.n_ref), self._first_row(first_row)
+        _lib.check(_lib.lib().nabo_umap_transform_query(self._h, Z.shape[0], first_row, Z.ctypes.data, k))
+        self.m, self.k = Z.shape[0], k
+        return self
+
+    def set_knn(self, idx, dist, first_row=0):
+        idx, dist = _check_target_lists(idx, dist, self.n_ref)
+        first_row = self._first_row(first_row)
+        _lib.check(_lib.lib().nabo_umap_transform_set_knn(self._h, idx.shape[0], first_row, idx.ctypes.data, dist.ctypes.data, idx.shape[1]))
+        self.m, self.k = idx.shape
+        return self
+
+    def set_graph(self, idx, memb, first_row=0):
+        """memberships [m, k] in [0, 1] in place of the smooth distances (for the tests)"""
+        idx, memb = _check_target_lists(idx, memb, self.n_ref, memberships=True)
+        first_row = self._first_row(first_row)
+        _lib.check(_lib.lib().nabo_umap_transform_set_graph(self._h, idx.shape[0], first_row, idx.ctypes.data, memb.ctypes.data, idx.shape[1]))
+        self.m, self.k = idx.shape
+        return self
+
+    def _batch(self):
+        if not self.m:
+            raise ValueError("ERROR: no batch: call query, set_knn or set_graph first")
+
+    def graph(self):
+        """(sigma [m], memb [m, k], y0 [m, dims]) of the loaded batch"""
+        self._batch()
+        sigma, memb, y0 = np.empty(self.m), np.empty((self.m, self.k)), np.empty((self.m, self.dims))
+        _lib.check(_lib.lib().nabo_umap_transform_get_graph(self._h, sigma.ctypes.data, memb.ctypes.data, y0.ctypes.data))
+        return sigma, memb, y0
+
+    def set_positions(self, y):
+        self._batch()
+        _lib.check(_lib.lib().nabo_umap_transform_set_positions(self._h, _positions(y, self.m, self.dims, "y").ctypes.data))
+        return self
+
+    def get_positions(self):
+        self._batch()
+        y = np.empty((self.m, self.dims), dtype=np.float64)
+        _lib.check(_lib.lib().nabo_umap_transform_get_positions(self._h, y.ctypes.data))
+        return y
+
+    def run(self, n_run=None):
+        """the next n_run epochs (default: all that are left) in one launch, never past n_epochs; returns how many ran"""
+        self._batch()
+        done = C.c_int64()
+        _lib.check(_lib.lib().nabo_umap_transform_run(self._h, self.params["n_epochs"] if n_run is None else int(n_run), C.byref(done)))
+        return int(done.value)
+
+    def rewind(self):
+        self._batch()
+        _lib.check(_lib.lib().nabo_umap_transform_rewind(self._h))
+        return self
+
+    def last_run_counts(self):
+        """{"n_attr", "n_neg": int64 [m], "idx_sum": uint64 [m]} over the epochs of the last run"""
+        self._batch()
+        a, b, s = np.empty(self.m, dtype=np.int64), np.empty(self.m, dtype=np.int64), np.empty(self.m, dtype=np.uint64)
+        _lib.check(_lib.lib().nabo_umap_transform_last_run_counts(self._h, a.ctypes.data, b.ctypes.data, s.ctypes.data))
+        return {"n_attr": a, "n_neg": b, "idx_sum": s}
+
+    def last_ms(self):
+        """{"graph", "knn", "run"}: device ms of the last batch's graph build, its k-NN and the last run"""
+        ms = (C.c_double * 3)()
+        _lib.check(_lib.lib().nabo_umap_transform_last_ms(self._h, ms))
+        return dict(zip(TRANSFORM_MS, ms[:3]))
+
+
+def _positions(y, n, dims, name):
+    try:
+        y = np.ascontiguousarray(y, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("ERROR: %s must be numeric" % name)
+    if y.shape != (n, dims):
+        raise ValueError("ERROR: %s must be [%d, %d]" % (name, n, dims))
+    if not np.isfinite(y).all():
+        raise ValueError("ERROR: %s holds a value that is not finite" % name)
+    return y
+
+
+def umap_transform(Z, X_ref, ref_embedding, n_neighbors=15, n_epochs=None, spread=1.0, min_dist=0.1, repulsion_strength=1.0,
+                   negative_sample_rate=5, seed=0, metric=EUCLIDEAN, dist_factor=0.25, a=None, b=None, device=0, batch=None):
+    """The positions, float64 [m, dims], of the target cells Z [m, n_comps] in the fitted embedding `ref_embedding`
+    [n_ref, dims] of the reference cells X_ref [n_ref, n_comps]; the reference does not move
+    (include/nabo_umap_transform.h).  a and b default to `find_ab_params(spread, min_dist)`; n_epochs=None means umap's
+    100 for up to 10000 targets and 30 above, a given n_epochs is used as given.  The targets go through in batches of
+    `batch` rows (None: all at once) with their global row numbers: every split returns the same bits."""
+    Z, X_ref = _cells(Z), _cells(X_ref)
+    m, n_ref = Z.shape[0], X_ref.shape[0]
+    if m < 1 or n_ref < 2:
+        raise ValueError("ERROR: at least 1 target and 2 reference cells are needed")
+    if Z.shape[1] != X_ref.shape[1]:
+        raise ValueError("ERROR: Z and X_ref must have the same number of components")
+    try:
+        Y = np.ascontiguousarray(ref_embedding, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("ERROR: ref_embedding must be numeric")
+    if Y.ndim != 2 or Y.shape[0] != n_ref or Y.shape[1] not in (2, 3):
+        raise ValueError("ERROR: ref_embedding must be [n_ref, 2] or [n_ref, 3] with n_ref = %d" % n_ref)
+    Y = _positions(Y, n_ref, Y.shape[1], "ref_embedding")
+    k = _neighbours(n_neighbors, n_ref)
+    if a is None and b is None:
+        a, b = find_ab_params(spread, min_dist)
+    seed = _count(seed, "seed", 0)
+    n_epochs = default_transform_epochs(m) if n_epochs is None else _count(n_epochs, "n_epochs", 1)
+    batch = m if batch is None else _count(batch, "batch", 1)
+    out = np.empty((m, Y.shape[1]), dtype=np.float64)
+    with UmapTransform(n_ref, Y.shape[1], device, n_epochs=n_epochs, negative_sample_rate=negative_sample_rate,
+                       repulsion_strength=repulsion_strength, a=a, b=b, seed=seed) as T:
+        T.set_embedding(Y)
+        T.set_cells(X_ref, metric, dist_factor)
+        for r0 in range(0, m, batch):
+            T.query(Z[r0:r0 + batch], k, first_row=r0)
+            T.run()
+            out[r0:r0 + batch] = T.get_positions()
+    return out
+
+
+def make_target_umap(ref_pca_h5, target_pca_h5, ref_umap, use_comps, n_neighbors, spread=1.0, repulsion_strength=1.0, min_dist=0.1,
+                     n_epochs=None, data_group="data", index_suffix="", verbose=True, *, ref_data_group="data", seed=0,
+                     negative_sample_rate=5, device=0, batch=None):
+    """The target cells of a PCA file placed in the reference's UMAP, as a frame of the reference frame's shape: one row
+    per target cell, named cell + index_suffix, with the columns of `ref_umap` -- the frame `make_umap` returned for
+    `ref_pca_h5`, whose row count is checked against that file (its rows are the file's cells in name order).  The
+    reference's vectors are read from `ref_data_group` of `ref_pca_h5`, the targets' from `data_group` of
+    `target_pca_h5`, the first `use_comps` components of each.  pandas and h5py are imported when the function is
+    called."""
+    import pandas as pd
+    try:
+        Y = np.ascontiguousarray(ref_umap.values, dtype=np.float64)
+        columns = list(ref_umap.columns)
+    except (AttributeError, TypeError, ValueError):
+        raise ValueError("ERROR: ref_umap must be the frame make_umap returned")
+    ref_cells, X = _read_cells(ref_pca_h5, ref_data_group, use_comps)
+    if Y.ndim != 2 or Y.shape[0] != len(ref_cells):
+        raise ValueError("ERROR: ref_umap has %d rows, the reference file %d cells" % (Y.shape[0] if Y.ndim else 0, len(ref_cells)))
+    cells, Z = _read_cells(target_pca_h5, data_group, use_comps)
+    P = umap_transform(Z, X, Y, n_neighbors, n_epochs, spread, min_dist, repulsion_strength, negative_sample_rate, seed,
+                       device=device, batch=batch)
+    if verbose:
+        print("UMAP transform of %d cells onto %d reference cells: %d neighbours, %d epochs"
+              % (len(cells), len(ref_cells), int(n_neighbors), default_transform_epochs(len(cells)) if n_epochs is None else int(n_epochs)))
+    return pd.DataFrame(P, index=[x + index_suffix for x in cells], columns=columns)

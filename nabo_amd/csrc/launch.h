@@ -271,6 +271,26 @@ hipError_t umap_epoch_launch(int dims, int64_t n, const int64_t *ptr, const int3
                              double *next, double *nneg, const double *y, double *ynew, const UmapEpoch &P, int32_t *n_attr,
                              int32_t *n_neg, uint64_t *idx_sum, hipStream_t st);
 
+// UMAP transform (umap_transform.hip; include/nabo_umap_transform.h has the definition).  A batch is graph -> schedule;
+// one run is ONE launch of the optimise kernel over the epochs [t0, t1): the reference positions Y are only read.
+struct UmapTransformRun {
+    double a, b, ca, cr;      // the curve; ca = (-2 a) b, cr = (2 gamma) b
+    double n_epochs, nsr;     // as float64
+    int64_t t0, t1;           // the epochs of this run
+    uint64_t seed;
+    int64_t first_row;        // the global number of the batch's row 0: part of the negative-sample hash
+    int64_t n_ref;
+};
+int umap_transform_group();   // lanes per target of the optimise kernel
+// dist NULL: memb [m][k] is given (sigma = 0); else B' and C' from dist.  Then the start y0 and y = y0.
+hipError_t umap_transform_graph_launch(int dims, int64_t m, int k, const int64_t *idx, const double *dist, const double *Y,
+                                       double *sigma, double *memb, double *y0, double *y, hipStream_t st);
+hipError_t umap_transform_schedule_launch(int64_t mk, const double *memb, double n_epochs, double nsr, double *next, double *nneg,
+                                          hipStream_t st);
+hipError_t umap_transform_run_launch(int dims, int64_t m, int k, const int64_t *idx, const double *memb, double *next, double *nneg,
+                                     const double *Y, double *y, const UmapTransformRun &P, int64_t *n_attr, int64_t *n_neg,
+                                     uint64_t *idx_sum, hipStream_t st);
+
 // Communities of the reference graph (community.hip; include/nabo_community.h has the definition).  One sweep is
 // totsize then sweep, which reads comm and writes comm_new; an aggregation is totsize, renumber, part_sums with keys,
 // coarse_sort, key_rowptr, coarse_arcs and compose.

@@ -26,27 +26,13 @@
 
 #include "../../include/nabo_umap.h"
 #include "host_common.h"
+#include "umap_common.h"
 
 namespace nabo {
 
 constexpr int UM_THREADS = 256;
 constexpr int UM_GROUP = 16;    // lanes per node of the epoch kernel: part of the definition (the order of a node's sum)
 constexpr int UM_BATCH = 4;     // negative samples whose gathers are in flight together
-constexpr uint64_t UM_GOLD = 0x9E3779B97F4A7C15ull;
-
-__host__ __device__ __forceinline__ uint64_t umap_mix(uint64_t z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-template <int W> __device__ __forceinline__ double umap_tree(double v)
-{
-#pragma unroll
-    for (int m = 1; m < W; m <<= 1) v += __shfl_xor(v, m, W);
-    return v;
-}
 
 // rowsum[i] = TREE(d), rho[i] = the smallest positive entry
 template <int W>
@@ -190,8 +176,6 @@ __global__ __launch_bounds__(UM_THREADS) void umap_arcs_kernel(const uint64_t *_
     next[e] = s;
     nneg[e] = sn;
 }
-
-__device__ __forceinline__ double umap_clip(double v) { return v > 4.0 ? 4.0 : v < -4.0 ? -4.0 : v; }
 
 template <int DIMS>
 __global__ __launch_bounds__(UM_THREADS) void umap_epoch_kernel(int64_t n, const int64_t *__restrict__ ptr, const int32_t *__restrict__ nbr,
