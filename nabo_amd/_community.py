@@ -6,6 +6,11 @@ and the two cluster writers (`save_clusters_as_json`, `save_clusters_as_csv`, :3
 leidenalg + igraph; here `nabo_community_run` (include/nabo_community.h, nabo_amd/csrc/community.hip) runs on the
 device.  include/nabo_community.h holds the definition; leidenalg's own partitions and random stream are not pinned
 (DESIGN.md 4.15).
+
+`Graph.make_clusters` (:247-264, Newman's greedy agglomeration through `hac`) is here too: `nabo_community_agglomerate`
+(include/nabo_agglom.h, nabo_amd/csrc/agglom.hip) merges a greedy matching of the best cluster pairs per round on the same
+handle and the same integers, keeps the dendrogram, and `nabo_community_cut` reads any number of clusters off it
+(DESIGN.md 4.18); hac's own merge order is not pinned.
 """
 import ctypes as C
 import json
@@ -16,6 +21,7 @@ from . import _lib
 from ._graphio import Handle, check_csr as _check_graph, read_ref_graph as _ref_graph_csr
 
 PHASES = ("sweeps", "aggregate", "finish", "run")
+AGGLOM_PHASES = ("passes", "order", "aggregate", "run")
 
 
 def geometry():
@@ -77,7 +83,8 @@ def _labels(labels, n):
 
 class Community(Handle):
     """A graph resident on one device and the state of its clustering (nabo_community_create): the handle the tests and
-    tools/bench_community.py step through; `louvain_csr` and `modularity_csr` are the one-call forms."""
+    tools/bench_community.py step through; `louvain_csr` and `modularity_csr` are the one-call forms.  The agglomeration
+    (`agglomerate`, `dendrogram`, `cut`; `agglomerate_csr` is its one-call form) runs on the same handle."""
     _destroy = "nabo_community_destroy"
 
     def __init__(self, ptr, nbr, w, resolution=1.0, seed=4466, weight_scale=10000, max_sweeps=128, max_levels=32, split=True,
@@ -168,6 +175,61 @@ class Community(Handle):
         _lib.check(_lib.lib().nabo_community_last_ms(self._h, ms))
         return dict(zip(PHASES, ms[:4]))
 
+    # ---- greedy modularity agglomeration (include/nabo_agglom.h) ----
+    def agglomerate(self, n_min=1):
+        """the whole agglomeration from level 0 until `n_min` clusters are left or no arc is; the info of agglomerate_csr
+        without "q" and "n_clusters", which belong to a cut"""
+        _lib.check(_lib.lib().nabo_community_agglomerate(self._h, _int(n_min, "n_min", 1, self.n)))
+        info = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().nabo_community_agglom_info(self._h, info))
+        rec, q_path = self.dendrogram()
+        return {"rounds": int(info[0]), "passes": int(info[1]), "peak": int(info[2]), "n_end": int(info[3]), "merges": rec, "q_path": q_path,
+                "two_m": self.level_size()[2], "ms": self.agglom_ms()}
+
+    def dendrogram(self):
+        """(merges int64 [M, 6]: rep_a < rep_b, round, a_cd, k_a, k_b per merge in order; q_path float64 [M + 1]: the
+        modularity after 0 .. M merges) of the last agglomeration"""
+        L, nm = _lib.lib(), C.c_int64()
+        _lib.check(L.nabo_community_dendrogram(self._h, C.byref(nm), 0, None, None))
+        rec, q_path = np.zeros((nm.value, 6), dtype=np.int64), np.zeros(nm.value + 1, dtype=np.float64)
+        _lib.check(L.nabo_community_dendrogram(self._h, C.byref(nm), int(nm.value), rec.ctypes.data, q_path.ctypes.data))
+        return rec, q_path
+
+    def cut(self, n_clusters=0):
+        """(labels int32 [n] in 1 .. C by descending size, C, Q) after the first n - n_clusters merges of the last
+        agglomeration; n_clusters = 0: at the peak of Q.  ValueError outside [the clusters at the run's end, n]."""
+        labels, nc, q = np.empty(self.n, dtype=np.int32), C.c_int32(), C.c_double()
+        _lib.check(_lib.lib().nabo_community_cut(self._h, _int(n_clusters, "n_clusters", 0), labels.ctypes.data, C.byref(nc), C.byref(q)))
+        return labels, int(nc.value), q.value
+
+    def match_pass(self, free=None):
+        """one locally dominant pass on the current level: (partner int32 [n], -1 for none; D, the winning gains as Python
+        integers, 0 for none).  free: [n], false = the cluster takes no part (None: all are free)."""
+        n = self.level_size()[0]
+        f = None
+        if free is not None:
+            f = np.ascontiguousarray(np.asarray(free).astype(bool), dtype=np.uint8)
+            if f.shape != (n,):
+                raise ValueError("ERROR: free must be 1-D with %d entries" % n)
+        partner, hi, lo = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.uint64)
+        _lib.check(_lib.lib().nabo_community_match_pass(self._h, None if f is None else f.ctypes.data, partner.ctypes.data, hi.ctypes.data,
+                                                        lo.ctypes.data))
+        return partner, [(h << 64) + x for h, x in zip(hi.tolist(), lo.tolist())]
+
+    def match(self):
+        """one round's matching on the current level: (pairs int32 [m, 2], c < d, in pair order; passes).  comm is left set
+        for them, so that aggregate() follows."""
+        n = self.level_size()[0]
+        pairs, m, p = np.zeros((n // 2 + 1, 2), dtype=np.int32), C.c_int64(), C.c_int64()
+        _lib.check(_lib.lib().nabo_community_match(self._h, C.byref(m), C.byref(p), pairs.ctypes.data))
+        return pairs[:m.value].copy(), int(p.value)
+
+    def agglom_ms(self):
+        """{"passes", "order", "aggregate", "run": device ms of the last agglomeration}"""
+        ms = (C.c_double * 4)()
+        _lib.check(_lib.lib().nabo_community_agglom_ms(self._h, ms))
+        return dict(zip(AGGLOM_PHASES, ms[:4]))
+
 
 def louvain_csr(ptr, nbr, w, resolution=1.0, seed=4466, weight_scale=10000, max_sweeps=128, max_levels=32, split=True, device=0):
     """Clusters of the weighted graph a CSR (ptr, nbr, w) describes -- rows in either arc direction; a pair listed more
@@ -207,6 +269,45 @@ def make_leiden_clusters(mapping_h5_fn, ref_name, resolution=1.0, random_seed=44
     (rint(w * 10000): Nabo's hundredths are exact)."""
     ref_nodes, pos, _, ptr, nbr, w = _ref_graph_csr(mapping_h5_fn, ref_name)
     return _leiden_of_graph(ref_nodes, pos, ptr, nbr, w, resolution, random_seed, device)[0]
+
+
+def agglomerate_csr(ptr, nbr, w, n_clusters=None, weight_scale=10000, device=0):
+    """Clusters of the weighted graph of louvain_csr by the greedy modularity agglomeration of include/nabo_agglom.h:
+    every round merges a greedy matching of the cluster pairs whose merge raises the modularity most, until one cluster
+    per connected component is left; `n_clusters` are then read off the merge list (None: at the peak of Q).  Returns
+    (labels int32 [n] in 1 .. C by descending size, info): info["q"] the modularity of the labels at resolution 1,
+    "n_clusters", "rounds", "passes", "merges" (int64 [M, 6]: rep_a < rep_b, round, a_cd, k_a, k_b), "q_path" (the
+    modularity after 0 .. M merges), "peak" (the number of merges at the largest Q), "n_end", "two_m" and "ms".
+    ValueError if n_clusters is below the clusters at the run's end or above the node count.  Every sum is an integer
+    one: the same call gives the same labels every time."""
+    if n_clusters is not None:
+        n_clusters = _int(n_clusters, "n_clusters", 1)
+    with Community(ptr, nbr, w, 1.0, 0, weight_scale, device=device) as H:
+        info = H.agglomerate()
+        labels, info["n_clusters"], info["q"] = H.cut(0 if n_clusters is None else n_clusters)
+        return labels, info
+
+
+def _clusters_of_graph(ref_nodes, pos, H, n_clusters):
+    """the dict of make_clusters from a handle whose agglomeration has run"""
+    labels = H.cut(_int(n_clusters, "n_clusters", 1))[0]
+    return {x: str(int(labels[pos[x]])) for x in ref_nodes}
+
+
+def make_clusters(mapping_h5_fn, ref_name, n_clusters, device=0):
+    """Graph.make_clusters (nabo/_graph.py:247-264) from the mapping file: {reference node: str(cluster)} in the
+    reference's node order with exactly `n_clusters` clusters, numbered from 1 by descending size; the dict of
+    make_leiden_clusters.  ValueError if `n_clusters` is below the number of clusters at the run's end (one per connected
+    component of the graph) or above the node count.
+
+    What differs from the reference, which hands `refG` to hac.GreedyAgglomerativeClusterer: a round
+    merges a whole greedy matching of the best pairs where Newman's algorithm merges one pair, so hac's merge order is
+    not reproduced; the objective, the gain of a merge and the rule `best first` are the same; the weights are quantised
+    to integers (rint(w * 10000): Nabo's hundredths are exact) and the result is the same bit for bit on every call."""
+    ref_nodes, pos, _, ptr, nbr, w = _ref_graph_csr(mapping_h5_fn, ref_name)
+    with Community(ptr, nbr, w, device=device) as H:
+        H.agglomerate()
+        return _clusters_of_graph(ref_nodes, pos, H, n_clusters)
 
 
 def _modularity_of_graph(ref_nodes, pos, ptr, nbr, w, clusters, device):

@@ -75,6 +75,10 @@ COMMUNITY_SYMBOLS = ["nabo_community_create", "nabo_community_destroy", "nabo_co
                      "nabo_community_sweep", "nabo_community_aggregate", "nabo_community_rewind", "nabo_community_last_ms",
                      "nabo_community_geometry"]
 
+# every symbol include/nabo_agglom.h declares (greedy modularity agglomeration on the handle of nabo_community.h)
+AGGLOM_SYMBOLS = ["nabo_community_agglomerate", "nabo_community_dendrogram", "nabo_community_agglom_info", "nabo_community_cut",
+                  "nabo_community_match_pass", "nabo_community_match", "nabo_community_agglom_ms"]
+
 # every symbol include/nabo_potential.h declares (differentiation potential: a sparse solve by Jacobi PCG)
 POTENTIAL_SYMBOLS = ["nabo_potential_create", "nabo_potential_destroy", "nabo_potential_set_params", "nabo_potential_graph_size",
                      "nabo_potential_prepare", "nabo_potential_get_prepared", "nabo_potential_iterate", "nabo_potential_get_state",
@@ -215,6 +219,13 @@ def lib():
     L.nabo_community_rewind.argtypes = [vp]
     L.nabo_community_last_ms.argtypes = [vp, C.POINTER(dbl)]
     L.nabo_community_geometry.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.nabo_community_agglomerate.argtypes = [vp, i64]
+    L.nabo_community_dendrogram.argtypes = [vp, C.POINTER(i64), i64, vp, vp]
+    L.nabo_community_agglom_info.argtypes = [vp, C.POINTER(i64)]
+    L.nabo_community_cut.argtypes = [vp, i64, vp, C.POINTER(i32), C.POINTER(dbl)]
+    L.nabo_community_match_pass.argtypes = [vp, vp, vp, vp, vp]
+    L.nabo_community_match.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), vp]
+    L.nabo_community_agglom_ms.argtypes = [vp, C.POINTER(dbl)]
     L.nabo_potential_create.argtypes = [C.POINTER(vp), i32, i64, vp, vp]
     L.nabo_potential_destroy.argtypes = [vp]
     L.nabo_potential_set_params.argtypes = [vp, dbl, i64]
@@ -230,7 +241,7 @@ def lib():
     L.nabo_potential_last_ms.argtypes = [vp, C.POINTER(dbl)]
     L.nabo_potential_geometry.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     for name in (SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS + UMAP_SYMBOLS
-                 + UMAP_TRANSFORM_SYMBOLS + COMMUNITY_SYMBOLS + POTENTIAL_SYMBOLS):
+                 + UMAP_TRANSFORM_SYMBOLS + COMMUNITY_SYMBOLS + AGGLOM_SYMBOLS + POTENTIAL_SYMBOLS):
         if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy", "nabo_umap_destroy", "nabo_umap_transform_destroy", "nabo_community_destroy",
                         "nabo_potential_destroy"):
             getattr(L, name).restype = C.c_int

@@ -256,6 +256,9 @@ class RefGraph:
         if getattr(self, "_g", None) is not None:
             self._g.close()
             self._g = None
+        if getattr(self, "_agglom", None) is not None:
+            self._agglom[2].close()
+            self._agglom = None
 
     def last_stats(self):
         return self._g.last_stats()
@@ -328,6 +331,20 @@ class RefGraph:
         through read_graph_csr: the resident graph keeps no weights).  The result is also kept as `self.clusters`."""
         from ._community import make_leiden_clusters
         self.clusters = make_leiden_clusters(self.fn, self.ref_name, resolution, random_seed, self.device)
+        return self.clusters
+
+    def make_clusters(self, n_clusters):
+        """Graph.make_clusters (nabo/_graph.py:247-264): {reference node: str(cluster)} with exactly `n_clusters`
+        clusters, as nabo_amd.make_clusters.  As the reference keeps `_agglomDendrogram`, the first call runs the
+        agglomeration and keeps its handle, so another `n_clusters` runs only the cut.  The result is also kept as
+        `self.clusters`."""
+        from ._community import Community, _clusters_of_graph, _ref_graph_csr
+        if getattr(self, "_agglom", None) is None:
+            ref_nodes, pos, _, ptr, nbr, w = _ref_graph_csr(self.fn, self.ref_name)
+            H = Community(ptr, nbr, w, device=self.device)
+            H.agglomerate()
+            self._agglom = (ref_nodes, pos, H)
+        self.clusters = _clusters_of_graph(*self._agglom, n_clusters)
         return self.clusters
 
     def calc_modularity(self, clusters=None):

@@ -17,6 +17,10 @@
 // becomes a 64-bit key (c_i << 32 | c_j) (inner arcs go to in' by an integer atomic and get the key of a row past the
 // last), one radix sort orders them, a segmented sum by key makes the coarse arcs, and the row pointer is read off the
 // sorted keys.  The split is min-label propagation over inner arcs with pointer jumping.
+//
+// The host side of the greedy agglomeration (include/nabo_agglom.h; its kernels are in agglom.hip) is here as well: it
+// steps rounds of match passes on the levels of this handle and uses the aggregation, the pointer jumping and the
+// numbering by size above.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -30,6 +34,7 @@
 #include <rocprim/device/device_reduce_by_key.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "../../include/nabo_agglom.h"
 #include "../../include/nabo_community.h"
 #include "host_common.h"
 #include "simple_graph.h"
@@ -495,6 +500,12 @@ hipError_t community_hook_launch(int64_t n, int64_t A, const int32_t *src, const
     return hipGetLastError();
 }
 
+hipError_t community_jump_launch(int64_t n, int32_t *lab, hipStream_t st)
+{
+    hipLaunchKernelGGL(cm_jump_kernel, dim3(cm_grid(n)), dim3(CM_THREADS), 0, st, n, lab);
+    return hipGetLastError();
+}
+
 }  // namespace nabo
 
 using nabo::DevBuf;
@@ -522,6 +533,18 @@ double modularity_of(u128 sum_in, u128 sum_d2, int64_t two_m, double gamma)
     return lhs - rhs;
 }
 
+// the state of the agglomeration (include/nabo_agglom.h): the buffers of a round, sized by n0 at the first use, and the
+// dendrogram of the last run
+struct Agglom {
+    DevBuf free, partner, dhi, dlo, wa, sel[2], key[2], rec, pairs, rep[2], counters, count;
+    int rep_cur = 0;
+    bool ran = false;
+    int64_t rounds = 0, passes = 0, peak = 0, n_end = 0;
+    std::vector<int64_t> merges;   // 6 per merge
+    std::vector<double> q_path;
+    double ms[4] = {0, 0, 0, 0};
+};
+
 }  // namespace
 
 struct nabo_community {
@@ -543,6 +566,7 @@ struct nabo_community {
     std::vector<Record> history;
     hipEvent_t ev[2] = {};
     double ms[4] = {0, 0, 0, 0};
+    Agglom ag;
     ~nabo_community()
     {
         for (hipEvent_t e : ev)
@@ -891,6 +915,188 @@ int community_run(nabo_community *H)
     return NABO_OK;
 }
 
+// ---- the agglomeration (include/nabo_agglom.h) ----------------------------------------------------------------------
+
+constexpr int AG_BATCH = 4;   // passes queued between two reads of the pair counters (a pass after an empty one changes nothing)
+
+int agglom_reserve(nabo_community *H)
+{
+    Agglom &G = H->ag;
+    const size_t n = (size_t)H->n0, half = n / 2 + 1;
+    int rc;
+    for (DevBuf *b : {&G.partner, &G.sel[0], &G.sel[1], &G.rep[0], &G.rep[1]})
+        if ((rc = b->reserve(n * 4))) return rc;
+    for (DevBuf *b : {&G.dhi, &G.dlo, &G.wa, &G.key[0], &G.key[1], &G.pairs})
+        if ((rc = b->reserve(n * 8))) return rc;
+    if ((rc = G.free.reserve(n))) return rc;
+    if ((rc = G.rec.reserve(half * 48))) return rc;
+    if ((rc = G.counters.reserve(AG_BATCH * 8))) return rc;
+    return G.count.reserve(8);
+}
+
+int agglom_pass_enqueue(nabo_community *H, bool any_sign, int32_t *partner, int64_t *dhi, uint64_t *dlo, int64_t *wa)
+{
+    Level &lv = H->level();
+    HIP_TRY(nabo::agglom_pass_launch(lv.n, lv.ptr.as<int64_t>(), lv.nbr.as<int32_t>(), lv.a.as<int64_t>(), lv.k.as<int64_t>(),
+                                     H->ag.free.as<uint8_t>(), H->two_m, nabo::CM_LONG, lv.long_rows.as<int32_t>(), lv.n_long, any_sign, partner,
+                                     dhi, dlo, wa, nullptr));
+    return NABO_OK;
+}
+
+// one round's matching on the current level: the lower ends of its pairs in pair order in ag.sel[0], the other ends in
+// ag.partner.  T (may be NULL): the passes go to ms[0], the ordering to ms[1]
+int agglom_round(nabo_community *H, int64_t *n_pairs, int64_t *passes, nabo::PhaseTimer *T)
+{
+    Agglom &G = H->ag;
+    Level &lv = H->level();
+    const int64_t n = lv.n;
+    int rc;
+    *n_pairs = 0;
+    *passes = 0;
+    if (T && (rc = T->start())) return rc;
+    HIP_TRY(hipMemsetAsync(G.free.p, 1, (size_t)n, nullptr));
+    HIP_TRY(hipMemsetAsync(G.partner.p, 0xFF, (size_t)n * 4, nullptr));
+    for (bool done = false; !done;) {
+        if (*passes > n) return nabo::api_fail(NABO_E_HIP, "the matching did not settle in %lld passes", (long long)*passes);
+        HIP_TRY(hipMemsetAsync(G.counters.p, 0, AG_BATCH * 8, nullptr));
+        for (int b = 0; b < AG_BATCH; ++b) {
+            if ((rc = agglom_pass_enqueue(H, false, G.partner.as<int32_t>(), G.dhi.as<int64_t>(), G.dlo.as<uint64_t>(), G.wa.as<int64_t>())))
+                return rc;
+            HIP_TRY(nabo::agglom_mark_launch(n, G.partner.as<int32_t>(), G.free.as<uint8_t>(), G.counters.as<uint64_t>() + b, nullptr));
+        }
+        uint64_t h[AG_BATCH];
+        HIP_TRY(hipMemcpy(h, G.counters.p, AG_BATCH * 8, hipMemcpyDeviceToHost));
+        for (int b = 0; b < AG_BATCH && !done; ++b) {
+            ++*passes;
+            *n_pairs += (int64_t)h[b];
+            done = h[b] == 0;
+        }
+    }
+    if (T && (rc = T->stop(0))) return rc;
+    if (*n_pairs > n / 2) return nabo::api_fail(NABO_E_HIP, "the matching returned %lld pairs for %lld clusters", (long long)*n_pairs, (long long)n);
+    if (T && (rc = T->start())) return rc;
+    if (*n_pairs == 0 && lv.A > 0) {   // no positive gain: the first pair of the order, whatever its sign
+        if ((rc = agglom_pass_enqueue(H, true, G.partner.as<int32_t>(), G.dhi.as<int64_t>(), G.dlo.as<uint64_t>(), G.wa.as<int64_t>()))) return rc;
+        HIP_TRY(nabo::agglom_first_launch(n, G.partner.as<int32_t>(), G.dhi.as<int64_t>(), G.dlo.as<uint64_t>(), G.sel[0].as<int32_t>(), nullptr));
+        *n_pairs = 1;
+    } else if (*n_pairs > 0) {
+        size_t tb = 0;
+        HIP_TRY(nabo::agglom_order_temp_bytes(n, &tb));
+        if ((rc = H->temp.reserve(tb))) return rc;
+        HIP_TRY(nabo::agglom_select_launch(n, G.partner.as<int32_t>(), G.free.as<uint8_t>(), H->flag.as<int32_t>(), G.sel[0].as<int32_t>(),
+                                           G.count.as<size_t>(), H->temp.p, tb, nullptr));
+        size_t cnt = 0;
+        HIP_TRY(hipMemcpy(&cnt, G.count.p, sizeof cnt, hipMemcpyDeviceToHost));
+        if ((int64_t)cnt != *n_pairs)
+            return nabo::api_fail(NABO_E_HIP, "the passes counted %lld pairs, the compaction %lld", (long long)*n_pairs, (long long)cnt);
+        HIP_TRY(nabo::agglom_sort_launch(*n_pairs, G.dhi.as<int64_t>(), G.dlo.as<uint64_t>(), G.sel[0].as<int32_t>(), G.sel[1].as<int32_t>(),
+                                         G.key[0].as<uint64_t>(), G.key[1].as<uint64_t>(), H->temp.p, tb, nullptr));
+    }
+    if (T && (rc = T->stop(1))) return rc;
+    return NABO_OK;
+}
+
+// comm of the current level from the first `take` pairs of the round
+int agglom_set_comm(nabo_community *H, int64_t take)
+{
+    int rc = community_identity(H);
+    if (rc) return rc;
+    HIP_TRY(nabo::agglom_comm_launch(take, H->ag.sel[0].as<int32_t>(), H->ag.partner.as<int32_t>(), H->comm[H->cur].as<int32_t>(), nullptr));
+    return NABO_OK;
+}
+
+int agglom_run(nabo_community *H, int64_t n_min)
+{
+    Agglom &G = H->ag;
+    G.ran = false;
+    G.merges.clear();
+    G.q_path.clear();
+    G.rounds = G.passes = G.peak = 0;
+    for (double &m : G.ms) m = 0;
+    int rc = agglom_reserve(H);
+    if (rc) return rc;
+    if ((rc = community_rewind(H))) return rc;
+    nabo::PhaseTimer T{H->ev, G.ms, 3};
+    G.rep_cur = 0;
+    HIP_TRY(nabo::iota_launch(G.rep[0].as<uint32_t>(), H->n0, nullptr));
+    std::vector<int64_t> rec;
+    for (;;) {
+        Level &lv = H->level();
+        const int64_t n = lv.n;
+        if (n <= n_min || lv.A == 0) break;
+        int64_t n_pairs = 0, passes = 0;
+        if ((rc = agglom_round(H, &n_pairs, &passes, &T))) return rc;
+        G.passes += passes;
+        if (n_pairs < 1) return nabo::api_fail(NABO_E_HIP, "a round on %lld arcs matched no pair", (long long)lv.A);
+        const int64_t take = std::min(n_pairs, n - n_min);
+        if ((rc = T.start())) return rc;
+        HIP_TRY(nabo::agglom_records_launch(take, G.sel[0].as<int32_t>(), G.partner.as<int32_t>(), G.wa.as<int64_t>(), lv.k.as<int64_t>(),
+                                            G.rep[G.rep_cur].as<int32_t>(), G.rounds, G.rec.as<int64_t>(), nullptr, nullptr));
+        rec.resize((size_t)take * 6);
+        HIP_TRY(hipMemcpy(rec.data(), G.rec.p, (size_t)take * 48, hipMemcpyDeviceToHost));
+        G.merges.insert(G.merges.end(), rec.begin(), rec.end());
+        if ((rc = T.stop(1))) return rc;
+        if ((rc = T.start())) return rc;
+        if ((rc = agglom_set_comm(H, take))) return rc;
+        if ((rc = community_aggregate(H, nullptr, nullptr))) return rc;   // lv is gone; flag and newid hold the renumbering
+        HIP_TRY(nabo::agglom_rep_launch(n, H->flag.as<int32_t>(), H->newid.as<int32_t>(), G.rep[G.rep_cur].as<int32_t>(),
+                                        G.rep[G.rep_cur ^ 1].as<int32_t>(), nullptr));
+        G.rep_cur ^= 1;
+        if ((rc = T.stop(2))) return rc;
+        ++G.rounds;
+        if (H->level().n != n - take)
+            return nabo::api_fail(NABO_E_HIP, "%lld merges left %lld of %lld clusters", (long long)take, (long long)H->level().n, (long long)n);
+        if (take < n_pairs) break;
+    }
+    G.n_end = H->level().n;
+    // the path of Q from the exact running sums, and its peak
+    u128 si = 0, sd = 0;
+    for (int64_t i = 0; i < H->n0; ++i) {
+        si += (u128)H->h_in0[(size_t)i];
+        sd += (u128)H->h_k0[(size_t)i] * (u128)H->h_k0[(size_t)i];
+    }
+    const size_t M = G.merges.size() / 6;
+    G.q_path.resize(M + 1);
+    __int128 best = (__int128)(si * (u128)H->two_m) - (__int128)sd;
+    G.q_path[0] = modularity_of(si, sd, H->two_m, 1.0);
+    for (size_t t = 1; t <= M; ++t) {
+        const int64_t *r = &G.merges[6 * (t - 1)];
+        si += 2 * (u128)r[3];
+        sd += 2 * (u128)r[4] * (u128)r[5];
+        G.q_path[t] = modularity_of(si, sd, H->two_m, 1.0);
+        const __int128 x = (__int128)(si * (u128)H->two_m) - (__int128)sd;
+        if (x > best) {
+            best = x;
+            G.peak = (int64_t)t;
+        }
+    }
+    G.ran = true;
+    return NABO_OK;
+}
+
+// the partition after the first t merges: parents from the merge list, pointer jumping, the numbering by size
+int agglom_cut(nabo_community *H, int64_t t, std::vector<int32_t> &labels, int32_t *n_out)
+{
+    const int64_t n = H->n0;
+    std::vector<int32_t> ra((size_t)t), rb((size_t)t);
+    for (int64_t i = 0; i < t; ++i) {
+        ra[(size_t)i] = (int32_t)H->ag.merges[(size_t)(6 * i)];
+        rb[(size_t)i] = (int32_t)H->ag.merges[(size_t)(6 * i + 1)];
+        if (ra[(size_t)i] < 0 || ra[(size_t)i] >= rb[(size_t)i] || rb[(size_t)i] >= n)
+            return nabo::api_fail(NABO_E_HIP, "merge %lld joins %d and %d", (long long)i, (int)ra[(size_t)i], (int)rb[(size_t)i]);
+    }
+    HIP_TRY(nabo::iota_launch(H->lab.as<uint32_t>(), n, nullptr));
+    if (t > 0) {   // flag, newid: the two columns of the prefix (t < n0)
+        HIP_TRY(hipMemcpy(H->flag.p, ra.data(), (size_t)t * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(H->newid.p, rb.data(), (size_t)t * 4, hipMemcpyHostToDevice));
+        HIP_TRY(nabo::agglom_parent_launch(t, H->flag.as<int32_t>(), H->newid.as<int32_t>(), H->lab.as<int32_t>(), nullptr));
+        HIP_TRY(nabo::community_jump_launch(n, H->lab.as<int32_t>(), nullptr));
+    }
+    std::vector<int32_t> comp((size_t)n);
+    HIP_TRY(hipMemcpy(comp.data(), H->lab.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return community_finish(H, comp.data(), 0, labels, n_out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1086,6 +1292,110 @@ int nabo_community_last_ms(nabo_community *H, double ms[4])
 {
     if (!H || !ms) return nabo::api_fail(NABO_E_INVALID, "NULL argument");
     for (int i = 0; i < 4; ++i) ms[i] = H->ms[i];
+    return NABO_OK;
+}
+
+int nabo_community_agglomerate(nabo_community *H, int64_t n_min)
+{
+    if (!H) return nabo::api_fail(NABO_E_INVALID, "community is NULL");
+    if (n_min < 1 || n_min > H->n0) return nabo::api_fail(NABO_E_INVALID, "n_min=%lld must be in [1, %lld]", (long long)n_min, (long long)H->n0);
+    int rc = nabo::use_device(H->device);
+    if (rc) return rc;
+    return agglom_run(H, n_min);
+}
+
+int nabo_community_dendrogram(nabo_community *H, int64_t *n_merges, int64_t cap, int64_t *rec, double *q_path)
+{
+    if (!H) return nabo::api_fail(NABO_E_INVALID, "community is NULL");
+    if (!H->ag.ran) return nabo::api_fail(NABO_E_INVALID, "no agglomeration has finished on this handle");
+    const int64_t M = (int64_t)H->ag.merges.size() / 6, m = std::max<int64_t>(0, std::min(cap, M));
+    if (n_merges) *n_merges = M;
+    if (rec) memcpy(rec, H->ag.merges.data(), (size_t)m * 48);
+    if (q_path) memcpy(q_path, H->ag.q_path.data(), (size_t)(m + 1) * 8);
+    return NABO_OK;
+}
+
+int nabo_community_agglom_info(nabo_community *H, int64_t info[4])
+{
+    if (!H || !info) return nabo::api_fail(NABO_E_INVALID, "NULL argument");
+    if (!H->ag.ran) return nabo::api_fail(NABO_E_INVALID, "no agglomeration has finished on this handle");
+    info[0] = H->ag.rounds;
+    info[1] = H->ag.passes;
+    info[2] = H->ag.peak;
+    info[3] = H->ag.n_end;
+    return NABO_OK;
+}
+
+int nabo_community_cut(nabo_community *H, int64_t n_clusters, int32_t *labels, int32_t *n_out, double *q)
+{
+    if (!H) return nabo::api_fail(NABO_E_INVALID, "community is NULL");
+    if (!H->ag.ran) return nabo::api_fail(NABO_E_INVALID, "no agglomeration has finished on this handle");
+    const int64_t M = (int64_t)H->ag.merges.size() / 6;
+    if (n_clusters != 0 && (n_clusters < H->n0 - M || n_clusters > H->n0))
+        return nabo::api_fail(NABO_E_INVALID, "n_clusters=%lld is outside [%lld, %lld], the clusters at the end of the run and the nodes",
+                              (long long)n_clusters, (long long)(H->n0 - M), (long long)H->n0);
+    const int64_t t = n_clusters == 0 ? H->ag.peak : H->n0 - n_clusters;
+    int rc = nabo::use_device(H->device);
+    if (rc) return rc;
+    std::vector<int32_t> res;
+    int32_t C = 0;
+    if ((rc = agglom_cut(H, t, res, &C))) return rc;
+    if (C != H->n0 - t) return nabo::api_fail(NABO_E_HIP, "%lld merges left %d of %lld clusters", (long long)t, (int)C, (long long)H->n0);
+    if (labels) memcpy(labels, res.data(), (size_t)H->n0 * 4);
+    if (n_out) *n_out = C;
+    if (q) *q = H->ag.q_path[(size_t)t];
+    return NABO_OK;
+}
+
+int nabo_community_match_pass(nabo_community *H, const uint8_t *free, int32_t *partner, int64_t *d_hi, uint64_t *d_lo)
+{
+    if (!H) return nabo::api_fail(NABO_E_INVALID, "community is NULL");
+    int rc = nabo::use_device(H->device);
+    if (rc) return rc;
+    if ((rc = agglom_reserve(H))) return rc;
+    Agglom &G = H->ag;
+    const size_t n = (size_t)H->level().n;
+    if (free) {
+        std::vector<uint8_t> f(n);
+        for (size_t i = 0; i < n; ++i) f[i] = free[i] != 0;
+        HIP_TRY(hipMemcpy(G.free.p, f.data(), n, hipMemcpyHostToDevice));
+    } else
+        HIP_TRY(hipMemset(G.free.p, 1, n));
+    HIP_TRY(hipMemset(G.partner.p, 0xFF, n * 4));   // the pass leaves the rows that are not free alone: -1, D = 0
+    HIP_TRY(hipMemset(G.dhi.p, 0, n * 8));
+    HIP_TRY(hipMemset(G.dlo.p, 0, n * 8));
+    if ((rc = agglom_pass_enqueue(H, false, G.partner.as<int32_t>(), G.dhi.as<int64_t>(), G.dlo.as<uint64_t>(), G.wa.as<int64_t>()))) return rc;
+    if (partner) HIP_TRY(hipMemcpy(partner, G.partner.p, n * 4, hipMemcpyDeviceToHost));
+    if (d_hi) HIP_TRY(hipMemcpy(d_hi, G.dhi.p, n * 8, hipMemcpyDeviceToHost));
+    if (d_lo) HIP_TRY(hipMemcpy(d_lo, G.dlo.p, n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipDeviceSynchronize());
+    return NABO_OK;
+}
+
+int nabo_community_match(nabo_community *H, int64_t *n_pairs, int64_t *passes, int32_t *pairs)
+{
+    if (!H) return nabo::api_fail(NABO_E_INVALID, "community is NULL");
+    int rc = nabo::use_device(H->device);
+    if (rc) return rc;
+    if ((rc = agglom_reserve(H))) return rc;
+    int64_t m = 0, p = 0;
+    if ((rc = agglom_round(H, &m, &p, nullptr))) return rc;
+    if (pairs && m > 0) {
+        HIP_TRY(nabo::agglom_records_launch(m, H->ag.sel[0].as<int32_t>(), H->ag.partner.as<int32_t>(), nullptr, nullptr, nullptr, 0, nullptr,
+                                            H->ag.pairs.as<int32_t>(), nullptr));
+        HIP_TRY(hipMemcpy(pairs, H->ag.pairs.p, (size_t)m * 8, hipMemcpyDeviceToHost));
+    }
+    if ((rc = agglom_set_comm(H, m))) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (n_pairs) *n_pairs = m;
+    if (passes) *passes = p;
+    return NABO_OK;
+}
+
+int nabo_community_agglom_ms(nabo_community *H, double ms[4])
+{
+    if (!H || !ms) return nabo::api_fail(NABO_E_INVALID, "NULL argument");
+    for (int i = 0; i < 4; ++i) ms[i] = H->ag.ms[i];
     return NABO_OK;
 }
 

@@ -323,5 +323,37 @@ hipError_t community_compose_launch(int64_t n, int32_t *map, const int32_t *lab,
 // one round of the component split: hook, then pointer jumping; *changed != 0 if a label fell
 hipError_t community_hook_launch(int64_t n, int64_t A, const int32_t *src, const int32_t *nbr, const int32_t *part, int32_t *lab,
                                  int32_t *changed, hipStream_t st);
+// pointer jumping alone: lab[i] = the end of the chain i -> lab[i] -> ... (every chain must end at a fixed point)
+hipError_t community_jump_launch(int64_t n, int32_t *lab, hipStream_t st);
+
+// Greedy modularity agglomeration (agglom.hip; include/nabo_agglom.h has the definition).  A round is passes of
+// pass + mark until a pass matches nothing, then select + sort (or first, in the round without a positive gain), records,
+// comm, the aggregation of community.hip and rep.
+int agglom_group();                // lanes per row of the pass's short path
+// one pass over the free rows: partner (-1: none), the winning D as (dhi, dlo) and its arc's weight wa, all [n]; rows that
+// are not free are left alone.  long_rows [n_long]: the rows of more than long_threshold arcs.  any_sign: D <= 0 counts too
+hipError_t agglom_pass_launch(int64_t n, const int64_t *ptr, const int32_t *nbr, const int64_t *a, const int64_t *k, const uint8_t *free,
+                              int64_t two_m, int long_threshold, const int32_t *long_rows, int64_t n_long, bool any_sign, int32_t *partner,
+                              int64_t *dhi, uint64_t *dlo, int64_t *wa, hipStream_t st);
+// clears free at mutual picks and adds the number of new pairs to *counter
+hipError_t agglom_mark_launch(int64_t n, const int32_t *partner, uint8_t *free, uint64_t *counter, hipStream_t st);
+// sel[0] = the lower end of the first pair of the order over every row's pick (partner[sel[0]] is its other end)
+hipError_t agglom_first_launch(int64_t n, const int32_t *partner, const int64_t *dhi, const uint64_t *dlo, int32_t *sel, hipStream_t st);
+hipError_t agglom_order_temp_bytes(int64_t n, size_t *bytes);
+// sel = the lower ends of the matched pairs in ascending id, *count (device) how many; flag [n]: scratch
+hipError_t agglom_select_launch(int64_t n, const int32_t *partner, const uint8_t *free, int32_t *flag, int32_t *sel, size_t *count, void *temp,
+                                size_t temp_bytes, hipStream_t st);
+// sel_a [m] in ascending id -> sel_a in pair order (every D > 0); sel_b, key_a, key_b [m]: scratch
+hipError_t agglom_sort_launch(int64_t m, const int64_t *dhi, const uint64_t *dlo, int32_t *sel_a, int32_t *sel_b, uint64_t *key_a,
+                              uint64_t *key_b, void *temp, size_t temp_bytes, hipStream_t st);
+// rec [m][6] = (rep_a, rep_b, round, a_cd, k_a, k_b), pairs [m][2] = (c, d); either may be NULL
+hipError_t agglom_records_launch(int64_t m, const int32_t *sel, const int32_t *partner, const int64_t *wa, const int64_t *k, const int32_t *rep,
+                                 int64_t round, int64_t *rec, int32_t *pairs, hipStream_t st);
+// comm (the identity beforehand): comm[d] = c for the first `take` pairs
+hipError_t agglom_comm_launch(int64_t take, const int32_t *sel, const int32_t *partner, int32_t *comm, hipStream_t st);
+// flag, newid: of the aggregation's renumbering; rep_next[newid[c]] = rep[c] for every surviving c
+hipError_t agglom_rep_launch(int64_t n, const int32_t *flag, const int32_t *newid, const int32_t *rep, int32_t *rep_next, hipStream_t st);
+// parent[rep_b[i]] = rep_a[i], i < t
+hipError_t agglom_parent_launch(int64_t t, const int32_t *rep_a, const int32_t *rep_b, int32_t *parent, hipStream_t st);
 
 }  // namespace nabo
