@@ -108,7 +108,11 @@ int nabo_index_destroy(nabo_index *ix);
  * at most 64, plus "two_level_share" percent of the bucket's tiles so far, 0 = 25 -- and runs the two-step loop to the end of
  * a bucket whose account is spent; "two_level_stretch" > 0 selects the control before that one instead: one account per
  * one-step segment, burst 0 = 8, and blind two-step stretches, the first of that many tiles, doubled while the probes behind
- * them fail; 0, the default, the per-bucket control).  When the two-level stream ran, nabo_index_last_kernel reports its
+ * them fail; 0, the default, the per-bucket control), "two_level_window" and "two_level_check" (the progress window of a
+ * workgroup in the stream's main launch: a wave more than "two_level_window" reference tiles ahead of the slowest wave of
+ * its workgroup that is still running sleeps until it is not, so that the four share their tiles through the cache --
+ * 0 = 8 tiles, at most 4096, -1 = no window; it looks every "two_level_check" tiles, 0 = 16, even, at most 64; results and
+ * tile counters are the same bits at every setting).  When the two-level stream ran, nabo_index_last_kernel reports its
  * tile counters behind the kernel's name: " [two-level tiles: one-step N, refetched N, two-step N]", summed over the waves.
  * Unknown names: NABO_E_INVALID.
  * The library reads TWO environment variables, once, in nabo_index_create: NABO_L2_MODE = f32 | f16x3 (which Euclidean /

@@ -27,7 +27,7 @@ FILE_FLAGS = {"l2_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-na
               "l2c_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
               "canberra_f32.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]}
 HEADERS = [os.path.join(CSRC, "knn_common.h"), os.path.join(CSRC, "topk_lists.h"), os.path.join(CSRC, "launch.h"),
-           os.path.join(CSRC, "host_common.h"), os.path.join(CSRC, "de_exact.h"), os.path.join(CSRC, "comm.h"), os.path.join(CSRC, "index.h"), os.path.join(CSRC, "local_seeds.h"), os.path.join(CSRC, "l2c_slots.h"), os.path.join(CSRC, "simple_graph.h"), os.path.join(CSRC, "row_chunks.h"), os.path.join(CSRC, "umap_common.h"), os.path.join(HERE, "..", "include", "nabo_knn.h"), os.path.join(HERE, "..", "include", "nabo_graph.h"),
+           os.path.join(CSRC, "host_common.h"), os.path.join(CSRC, "de_exact.h"), os.path.join(CSRC, "comm.h"), os.path.join(CSRC, "index.h"), os.path.join(CSRC, "local_seeds.h"), os.path.join(CSRC, "l2c_slots.h"), os.path.join(CSRC, "l2c_window.h"), os.path.join(CSRC, "simple_graph.h"), os.path.join(CSRC, "row_chunks.h"), os.path.join(CSRC, "umap_common.h"), os.path.join(HERE, "..", "include", "nabo_knn.h"), os.path.join(HERE, "..", "include", "nabo_graph.h"),
            os.path.join(HERE, "..", "include", "nabo_cluster.h"), os.path.join(HERE, "..", "include", "nabo_de.h"),
            os.path.join(HERE, "..", "include", "nabo_pca.h"), os.path.join(HERE, "..", "include", "nabo_pca_fit.h"),
            os.path.join(HERE, "..", "include", "nabo_qc.h"), os.path.join(HERE, "..", "include", "nabo_layout.h"),

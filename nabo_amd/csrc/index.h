@@ -46,6 +46,7 @@ struct Options {
     // control's default) of the kernel's mode control pinned for A/B runs; stretch > 0: the control that keeps no account
     // per reference bucket, with that first two-step stretch (tiles)
     int two_level = 1, two_level_share = 0, two_level_stretch = 0, two_level_burst = 0;
+    int two_level_window = 0, two_level_check = 0;       // l2c_window.h: tiles; window -1 = none, 0 = the defaults
 };
 bool option_set(Options &o, const char *name, int64_t value);
 

@@ -38,12 +38,14 @@
 
 #define NABO_DRAIN_CALL 1             // topk_lists.h: this file drains its lists through a real call
 #include "knn_common.h"
+#include "l2c_window.h"
 #include "launch.h"
 #include "topk_lists.h"
 
 namespace nabo {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // Three geometries (claunch_one), by the list length a pass wants:
 //   A  one wave per SIMD: 4 waves x 128 rows, lists of <= 32 kept entries (33-entry rows), 64 staging records;
@@ -331,7 +333,7 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                                                           const uint32_t *__restrict__ ref_map,
                                                           unsigned long long *__restrict__ tl_stats, int tl_share,
                                                           int tl_stretch, const int32_t *__restrict__ tl_bend, int tl_nbend,
-                                                          int tl_burst)
+                                                          int tl_burst, int tl_window, int tl_check)
 {
     // TWO-LEVEL stream (geometry B on two operand steps; row_map != null selects it at run time, every other launch of this
     // instantiation runs the plain loop below): operands in the two-level slot order (l2c_slots.h), targets AND references
@@ -409,11 +411,24 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
             tauv[rb] = r < rows_valid ? ((tau_init && !(dbg & 1)) ? seed_of(r) : tau0) : -__builtin_inff();
         }
     }
+    // PROGRESS WINDOW (l2c_window.h; ordered launches that ask for one, tl_window > 0 tiles): one slot per wave behind the
+    // lists, the tile the wave is at.  Every slot is written before any wave polls -- the barrier stands AHEAD of the early
+    // return, and a wave that leaves there has said so in its slot.
+    // (LDS pointers by name: through a generic volatile pointer hipcc reads the slots with flat loads)
+    typedef __attribute__((address_space(3))) volatile int32_t lds_slot;
+    typedef __attribute__((address_space(3))) volatile i32x4 lds_slots;
+    lds_slot *wslot = (lds_slot *)(smem_raw + (size_t)WAVES * C::BYTES);
+    const bool win_on = ordered && tl_window > 0;
     if (ordered) {      // a wave of padding positions only (every bucket's rows end in some): nothing to find, nothing to emit
         bool live = false;
 #pragma unroll
         for (int rb = 0; rb < NB; ++rb) live = live || tauv[rb] > -__builtin_inff();
-        if (__builtin_amdgcn_ballot_w64(live) == 0) return;
+        const bool dead = __builtin_amdgcn_ballot_w64(live) == 0;
+        if (win_on) {
+            if (lane == 0) wslot[wave] = dead ? L2C_WIN_DONE : split * tiles_per_split;
+            __syncthreads();
+        }
+        if (dead) return;
     }
     uint32_t scnt = 0;
     const int t_begin = split * tiles_per_split;
@@ -613,10 +628,10 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
             int seg_end = 0, seg_t0 = 0, seg_ref = 0;
             int bk_cur = 0, bk_t0 = 0, bk_ref = 0;         // the cursor's bucket: index, first tile, refetches charged to it
             int t2_end = 0;                                // where the next two-step stretch ends
-            // A tile's second step is fetched ON DEMAND, not kept in the ring's idle registers: 16 waves of a CU that load
-            // whole tiles at the one-step loop's rate ask more of the CU's vector cache than it delivers (4 KB per tile and
-            // wave against ~100 SIMD cycles per pair of row-blocks) -- with every tile loaded whole the step took 143 ms
-            // where the parent takes 91 and this loop 83 (1M x 1M, d = 50, 7.7 % of the tiles completed).
+            // A tile's second step is fetched ON DEMAND, not kept in the ring's idle registers: the stream already runs at
+            // the rate the fabric delivers (every wave asks for every tile itself), and whole tiles are
+            // twice the bytes -- with every tile loaded whole the step took 143 ms where the parent takes 91 and this loop
+            // 83 (1M x 1M, d = 50, 7.7 % of the tiles completed).
             auto tile_load1 = [&](f16x8(&a)[2][KS], int ts) {
                 const f16x8 *p = reinterpret_cast<const f16x8 *>(tile_ptr(ts));
                 a[0][0] = p[(0 * KS + 0) * 64 + lane];
@@ -663,6 +678,40 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
             // Segments alternate; each ends with its last tile pending in accO -- bounds after a one-step segment (completed
             // here), scores after a two-step stretch -- and ONE filter site takes it, so that the next segment starts from
             // +inf accumulators like the kernel does.
+            // The window's two halves sit between the statements of a pair of tiles: at its top the wave publishes its tile
+            // (one lane) and, every win_check tiles, asks for all four slots with one broadcast read; behind the pair's first
+            // tile -- the read's latency lies under that tile's MFMAs -- it looks at them and sleeps while it is more than
+            // the window ahead of the slowest live wave.  Wave-uniform, in scalar registers but for the four slots read.
+            static_assert(WAVES == L2C_WIN_SLOTS, "one slot per wave, one 16-byte read for all");
+            const int win_check = l2c_win_check(tl_check);
+            bool win_sync = win_on, win_due = false;
+            int win_next = t_begin;
+            i32x4 wv = i32x4{0, 0, 0, 0};
+            auto win_read = [&]() { wv = *(lds_slots *)wslot; };
+            auto win_slowest = [&]() {
+                return __builtin_amdgcn_readfirstlane(l2c_win_min(wv.x, wv.y, wv.z, wv.w));      // (a broadcast read: every lane holds all four)
+            };
+            auto win_top = [&](int tt) {
+                if (!win_on) return;
+                if (lane == 0) wslot[wave] = tt;
+                win_due = win_sync && tt >= win_next;
+                if (win_due) win_read();
+            };
+            auto win_mid = [&](int tt) {
+                if (!win_due) return;
+                win_due = false;
+                win_next = tt + win_check;
+                for (int polls = 0;; ++polls) {
+                    const L2cWinVerdict v = l2c_win_verdict(tt, win_slowest(), tl_window, polls);
+                    if (v == L2C_WIN_GO) break;
+                    if (v == L2C_WIN_GIVE_UP) {          // unsynchronised from here on; the wave goes on publishing
+                        win_sync = false;
+                        break;
+                    }
+                    __builtin_amdgcn_s_sleep(L2C_WIN_SLEEP);
+                    win_read();
+                }
+            };
             bool one_step = ordered;
             while (t < t_end) {
                 seg_t0 = t;
@@ -671,7 +720,9 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                     seg_end = t_end;
                     tile_load1(a0, t);
                     for (; t < seg_end; t += 2) {
+                        win_top(t);
                         tile_step1(a0, a1, accE, accO, t);
+                        win_mid(t);
                         tile_step1(a1, a0, accO, accE, t + 1);
                     }
                     pad_acc(accO);
@@ -689,7 +740,9 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                     }
                     if (ordered) tile_load(a0, t);      // (a plain launch: its one stretch starts on the preamble's tile)
                     for (; t < t2_end; t += 2) {
+                        win_top(t);
                         tile_step(a0, a1, accE, accO, t);
+                        win_mid(t);
                         tile_step(a1, a0, accO, accE, t + 1);
                     }
                     pad_acc(accO);
@@ -699,6 +752,7 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                 reset(accO);
                 one_step = !one_step;
             }
+            if (win_on && lane == 0) wslot[wave] = L2C_WIN_DONE;        // out of the stream: nobody waits for the flush
             if (tl_stats && lane == 0) {
                 atomicAdd(tl_stats, (unsigned long long)n_one);
                 atomicAdd(tl_stats + 1, (unsigned long long)n_ref);
@@ -913,7 +967,8 @@ static hipError_t claunch_geo(const unsigned char *Xpk, const unsigned char *Ypk
                               int64_t pad_tile, hipStream_t st, int64_t rows_valid, const float *tau_init, int tau_stride,
                               int64_t tau_row0, const L2cOrdered *ord)
 {
-    constexpr size_t lds = (size_t)WAVES * ListCfg<EPL, ROWN, NBv, NRECv, 16, (ROWN >= 64)>::BYTES;
+    // (the two-level instantiation: the progress window's slots behind the lists, l2c_window.h)
+    constexpr size_t lds = (size_t)WAVES * ListCfg<EPL, ROWN, NBv, NRECv, 16, (ROWN >= 64)>::BYTES + (KS == 2 && WPS == 2 ? L2C_WIN_BYTES : 0);
     static_assert(lds <= 163840, "LDS budget");
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&l2c_topk_kernel<KS, EPL, ROWN, NBv, NRECv, WAVES, WPS>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -923,7 +978,8 @@ static hipError_t claunch_geo(const unsigned char *Xpk, const unsigned char *Ypk
                        tiles_per_split, tile_off, lkeep, cand_idx, cand_key, cand_tau, pad_tile, 0, rows_valid, tau_init, tau_stride,
                        tau_row0, ord ? ord->row_map : nullptr, ord ? ord->ref_map : nullptr, ord ? ord->stats : nullptr,
                        ord ? ord->share_pct : 0, ord ? ord->stretch : 0, ord ? ord->bucket_end : nullptr,
-                       ord && ord->bucket_end ? ord->nbucket : 0, ord ? ord->burst : 0);
+                       ord && ord->bucket_end ? ord->nbucket : 0, ord ? ord->burst : 0, ord ? l2c_win_window(ord->window) : 0,
+                       ord ? ord->check : 0);
     return hipGetLastError();
 }
 

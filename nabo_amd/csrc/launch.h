@@ -63,12 +63,15 @@ void l2q_topk_geometry(int kc, int *rows_per_wg, int *wg_per_cu, int *lkeep_max)
 // null): the reference buckets' ends in tiles of the stream, non-decreasing (lseed_bucket_ends) -- the mode control keeps its
 // account per bucket and runs two-step to a bucket's end.  stretch > 0, or no table: the control before that one, one
 // account per one-step segment and blind two-step stretches, the first of `stretch` tiles (0: 64).
+// window / check: the workgroup's progress window (l2c_window.h) -- a wave more than `window` tiles ahead of the slowest
+// live wave of its workgroup waits, looking every `check` tiles (0: the defaults; window < 0: none).
 struct L2cOrdered {
     const uint32_t *row_map, *ref_map;
     unsigned long long *stats;
     int share_pct, stretch;
     const int32_t *bucket_end;
     int nbucket, burst;
+    int window, check;
 };
 int l2c_pick_kc(int g);
 int l2c_geometry(int kc, int lkeep_want, int pin);

@@ -8,6 +8,7 @@
 
 #include "index.h"
 #include "l2c_slots.h"
+#include "l2c_window.h"
 #include "local_seeds.h"
 
 namespace nabo {
@@ -40,16 +41,19 @@ static const OptionName LOCAL_SEED_OPTION_NAMES[] = {
 // The two-level stream's options (l2c_topk.hip): tests/test_two_level_gpu.py runs it on small shapes against the oracle.
 static const OptionName TWO_LEVEL_OPTION_NAMES[] = {
     {"two_level", &Options::two_level}, {"two_level_share", &Options::two_level_share}, {"two_level_stretch", &Options::two_level_stretch},
-    {"two_level_burst", &Options::two_level_burst},
+    {"two_level_burst", &Options::two_level_burst}, {"two_level_window", &Options::two_level_window},
+    {"two_level_check", &Options::two_level_check},
 };
 
 bool option_set(Options &o, const char *name, int64_t value)
 {
     for (const OptionName &e : TWO_LEVEL_OPTION_NAMES)
-        if (strcmp(e.name, name) == 0) {            // clamped: 0 .. 2, percent, refetches, tiles
+        if (strcmp(e.name, name) == 0) {            // clamped: 0 .. 2, percent, refetches, tiles (the window: -1 = none)
             const int64_t hi = e.field == &Options::two_level ? 2 : e.field == &Options::two_level_share ? 100
-                               : e.field == &Options::two_level_burst ? 64 : 1 << 20;
-            o.*(e.field) = (int)(value < 0 ? 0 : value > hi ? hi : value);
+                               : e.field == &Options::two_level_burst ? 64 : e.field == &Options::two_level_window ? L2C_WIN_MAX
+                               : e.field == &Options::two_level_check ? L2C_WIN_CHECK_MAX : 1 << 20;
+            const int64_t lo = e.field == &Options::two_level_window ? -1 : 0;
+            o.*(e.field) = (int)(value < lo ? lo : value > hi ? hi : value);
             return true;
         }
     for (const OptionName &e : OPTION_NAMES)

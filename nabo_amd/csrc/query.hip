@@ -205,7 +205,8 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
         const int64_t prow = ordered ? lseed_columns(p.end(q.m) - p.row0, l2.local_C) * LSEED_COL_ROWS : 0;
         const int64_t gx_ord = (prow + P.rows_per_wg - 1) / P.rows_per_wg;
         L2cOrdered ord = {ws.lmap.as<uint32_t>(), l2.yordmap.as<uint32_t>(), nullptr, sh.opt.two_level_share, sh.opt.two_level_stretch,
-                          l2.yordend.as<int32_t>(), l2.local_C, sh.opt.two_level_burst};
+                          l2.yordend.as<int32_t>(), l2.local_C, sh.opt.two_level_burst, sh.opt.two_level_window,
+                          sh.opt.two_level_check};
         if (i == 0 && ordered) {
             if ((rc = ws.tlstats.reserve(3 * sizeof(unsigned long long)))) return rc;
             ord.stats = ws.tlstats.as<unsigned long long>();
@@ -222,9 +223,11 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
         // Its lists are scratch: the launch proper writes every row again.  One host wait.
         if (i == 0 && ordered && l2.tl_verdict == 0 && sh.opt.two_level == 1 && gx_ord >= 512 && l2.ord_tiles >= 4096) {
             unsigned long long probe[3] = {0, 0, 0};
+            L2cOrdered pord = ord;               // (the probe runs as it always has: no progress window)
+            pord.window = -1;
             HIP_TRY(hipMemsetAsync(ws.tlstats.p, 0, sizeof(probe), st));
             HIP_TRY(l2c_topk_launch(P.kcq, P.geo, ws.xpre.as<unsigned char>(), l2.yord.as<unsigned char>(), 1024, 1, 128, 0, P.lkeep,
-                                    p.idx->as<uint32_t>(), nullptr, p.tau->as<float>(), l2.ord_tiles, st, prow, seed[i], stride[i], 0, &ord));
+                                    p.idx->as<uint32_t>(), nullptr, p.tau->as<float>(), l2.ord_tiles, st, prow, seed[i], stride[i], 0, &pord));
             HIP_TRY(hipMemcpyAsync(probe, ws.tlstats.p, sizeof(probe), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
 #ifdef NABO_TL_TRACE        // (a build of its own, _build.py --out ... -DNABO_TL_TRACE: the probe's counters, for the records)
