@@ -33,12 +33,15 @@ static const OptionName OPTION_NAMES[] = {
 };
 
 // The local tournament seeds' options (local_seeds.hip).  A table of their own: tests/test_local_seeds_gpu.py runs them
-// on and off against the oracle, the randomised option sweep draws from OPTION_NAMES above.
+// on and off against the oracle, the randomised option sweep (tests/test_option_sweep_gpu.py) draws from OPTION_NAMES
+// above, and the stream sweep (tests/test_stream_sweep_gpu.py) draws from this table and the next one.
 static const OptionName LOCAL_SEED_OPTION_NAMES[] = {
     {"local_seeds", &Options::local_seeds}, {"local_anchors", &Options::local_anchors}, {"local_cap", &Options::local_cap},
 };
 
-// The two-level stream's options (l2c_topk.hip): tests/test_two_level_gpu.py runs it on small shapes against the oracle.
+// The two-level stream's options (l2c_topk.hip): tests/test_two_level_gpu.py runs it on small shapes against the oracle,
+// the stream sweep (tests/test_stream_sweep_gpu.py; values: STREAM_OPTION_VALUES of tests/_option_sweep.py) draws them,
+// clamps included, with the main table's options on top.
 static const OptionName TWO_LEVEL_OPTION_NAMES[] = {
     {"two_level", &Options::two_level}, {"two_level_share", &Options::two_level_share}, {"two_level_stretch", &Options::two_level_stretch},
     {"two_level_burst", &Options::two_level_burst}, {"two_level_window", &Options::two_level_window},

@@ -1,9 +1,15 @@
-"""Seeded cases for the option sweep (tests/test_option_sweep_gpu.py, tests/test_option_table.py, tools/stress_sweep3.py).
+"""Seeded cases for the option sweep (tests/test_option_sweep_gpu.py, tests/test_option_table.py, tools/stress_sweep3.py)
+and for the stream sweep (tests/test_stream_sweep_gpu.py, tests/test_option_table.py).
 
 include/nabo_knn.h promises that every index option returns the SAME BITS: an option chooses how a launch is cut or which
 filter pass answers a row, never what the answer is.  The only guard against a subtly wrong pass is oracle parity on inputs
 that actually route rows through that pass, so this module draws index options, L2 / Canberra modes, shapes, data flavours
 and short scripts of calls on one resident index that reach every pass.  Pure Python + numpy: no GPU, no oracle.
+
+Two generators, each with a random stream and value tables of its own.  cases() draws from OPTION_NAMES[] of plan.hip over
+shapes up to 70 000 references -- below the sizes at which the planner takes the two-level stream and the local seeds, so it
+never reaches them.  stream_cases() starts every index ON that path (two_level = 2, one reference split, d = 29..59) and
+draws the nine options of LOCAL_SEED_OPTION_NAMES[] and TWO_LEVEL_OPTION_NAMES[] as well, from STREAM_OPTION_VALUES.
 
 A case is a plain dict; make_ref / make_targets / make_mask rebuild its arrays from the seeds it carries, so a failing
 case is reproduced from (metric, seed, case number) alone."""
@@ -54,10 +60,11 @@ OPTION_VALUES = {
 REFUSED_OPTIONS = ("order_flags",)                     # never drawn into a case; tests check the refusal itself
 
 
-def option_names(path=API_SOURCE):
-    """The names of OPTION_NAMES[] in plan.hip, in table order."""
+def option_names(path=API_SOURCE, table="OPTION_NAMES"):
+    """The names of one option table of plan.hip (OPTION_NAMES[], LOCAL_SEED_OPTION_NAMES[] or TWO_LEVEL_OPTION_NAMES[]),
+    in table order."""
     src = open(path).read()
-    body = re.search(r"OPTION_NAMES\[\]\s*=\s*\{(.*?)\n\};", src, re.S).group(1)
+    body = re.search(r"\b%s\[\]\s*=\s*\{(.*?)\n\};" % re.escape(table), src, re.S).group(1)
     return re.findall(r'\{\s*"([a-z0-9_]+)"\s*,', body)
 
 
@@ -167,6 +174,129 @@ def cases(metric, seed, n_cases=None):
     return out
 
 
+# ---- the stream sweep: the two-level stream and the local seeds (tests/test_stream_sweep_gpu.py) ---------------------
+
+# cases() above never reaches the two-level stream (option two_level = 2 or n >= 2^18) nor the local seeds' buckets, and its
+# draws are pinned by replay lines.  stream_cases() is a generator of its own -- own rng stream, own value tables -- whose
+# cases start ON that path: two_level = 2, one reference split, d in 29..59, k + drop <= 15 in four queries of five.
+STREAM_TAG = 0x2712e
+STREAM_CAP = 2 * 10 ** 7                                # m * n * g of one query
+STREAM_CASES = 24                                       # per (metric, seed)
+STREAM_N = (4, 5, 33, 64, 127, 300, 2000, 4983, 5000, 9000, 20000)
+STREAM_G = (29, 30, 32, 33, 45, 50, 58, 59)
+STREAM_ANCHORS = (1, 2, 3, 4, 16, 64, 256)              # local_anchors, capped at n (above 256: clamped to it)
+STREAM_M = (1, 33, 96, 97, 384, 385, 700, 1500)         # a wave's 96 rows, a workgroup's 384, one either side
+STREAM_MAX_KK = 15                                      # k + drop of the stream's geometry (lkeep <= 23)
+
+# The values drawn for the options of LOCAL_SEED_OPTION_NAMES and TWO_LEVEL_OPTION_NAMES (plan.hip), the clamps included.
+STREAM_OPTION_VALUES = {
+    "local_seeds": (0, 1, 2),
+    "local_anchors": STREAM_ANCHORS,
+    "local_cap": (0, 2048, 32768),
+    "two_level": (0, 1, 2),
+    "two_level_share": (0, 1, 25, 100),
+    "two_level_stretch": (0, 16),
+    "two_level_burst": (0, 1, 3, 64),
+    "two_level_window": (-1, 0, 1, 8, 4096),
+    "two_level_check": (0, 2, 16, 64),
+}
+STREAM_OPTION_DEFAULTS = {"local_seeds": 1, "local_anchors": 0, "local_cap": 0, "two_level": 1, "two_level_share": 0,
+                          "two_level_stretch": 0, "two_level_burst": 0, "two_level_window": 0, "two_level_check": 0}
+# values that appear as set_option steps only: a case's first options keep two_level = 2 and the local seeds on
+STREAM_STEP_ONLY = {"two_level": (0, 1, 2), "local_seeds": (0,)}
+# companion options (OPTION_VALUES) whose values leave the stream: kept out of a case's FIRST options, allowed in later steps
+STREAM_LEAVES = {
+    "splits": lambda v: v != 1,
+    "prepass": lambda v: v == 0,
+    "l2c_geo": lambda v: v in (0, 2),
+    "coarse_kernel_q": lambda v: v == 1,
+    "coarse_slack": lambda v: v >= 6,
+    "split_refs_max": lambda v: v != 0,
+}
+
+
+def _stream_query(rng, n, g):
+    """("query", m, k, drop): k + drop within 1..15 in about four of five, else k in 16..56 (which leaves the stream)."""
+    drop = bool(rng.random() < 0.3)
+    d = 1 if drop else 0
+    top = min(n, STREAM_MAX_KK)
+    if rng.random() < 0.2 and n >= 16 + d:
+        k = int(rng.integers(16, min(n, NABO_MAX_K) - d + 1))
+    elif rng.random() < 0.4:
+        k = int(min(top, _pick(rng, (1 + d, 2 + d, 14, 15)))) - d      # the ends: k = 1, k + drop = 15
+    else:
+        k = int(rng.integers(1 + d, top + 1)) - d
+    m = int(_pick(rng, STREAM_M))
+    m = max(1, min(m, STREAM_CAP // (n * g)))
+    if drop:
+        m = min(m, n)
+    return ("query", m, k, drop)
+
+
+def _stream_step_option(rng, n):
+    """One set_option step from any of the three tables; every value is allowed here, those that leave the stream too."""
+    if rng.random() < 0.5:
+        name = _pick(rng, list(STREAM_OPTION_VALUES))
+        value = int(_pick(rng, STREAM_OPTION_VALUES[name]))
+        if name == "local_anchors":
+            value = min(value, n)
+        return ("set_option", name, value)
+    name = _pick(rng, [o for o in OPTION_VALUES if o not in REFUSED_OPTIONS])
+    return ("set_option", name, resolve(name, _pick(rng, OPTION_VALUES[name]), n, STREAM_MAX_KK))
+
+
+def stream_cases(metric, seed, n_cases=None):
+    """The deterministic case list of the stream sweep for one metric (0 Euclidean, 2 cosine) and seed: cases() in form, but
+    every index starts with two_level = 2 on one reference split, and the shapes, k and options are drawn around that path."""
+    if metric not in (0, 2):
+        raise ValueError("the two-level stream serves the Euclidean and the cosine metric")
+    rng = np.random.default_rng([metric, seed, STREAM_TAG])
+    if n_cases is None:
+        n_cases = STREAM_CASES
+    out = []
+    for i in range(n_cases):
+        n = int(_pick(rng, STREAM_N))
+        g = int(rng.integers(29, 60)) if rng.random() < 0.5 else int(_pick(rng, STREAM_G))
+        case = {
+            "sweep": "stream", "metric": metric, "seed": seed, "case": i, "n": n, "g": g, "flavour": _pick(rng, FLAVOURS),
+            "data_seed": int(rng.integers(1, 1 << 30)),
+            "offset": float(_pick(rng, (10.0, 40.0, 400.0))),
+            "scale": float(10.0 ** int(rng.integers(-15, 16))),
+            "quantum": float(_pick(rng, (0.25, 1.0))),
+            "mask": _pick(rng, MASKS), "mask_seed": int(rng.integers(1, 1 << 30)),
+            "mode": None, "dist_factor": 0.25,
+        }
+        first = _stream_query(rng, n, g)
+        opts = {"two_level": 2, "splits": 1, "local_anchors": min(int(_pick(rng, STREAM_ANCHORS)), n)}
+        for name, vals in STREAM_OPTION_VALUES.items():
+            if name in ("two_level", "local_anchors") or rng.random() >= 0.5:
+                continue
+            opts[name] = int(_pick(rng, [v for v in vals if v not in STREAM_STEP_ONLY.get(name, ())]))
+        for name, value in _draw_options(rng, metric, n, first[2] + first[3], 0.3).items():
+            if name == "splits" or (name in STREAM_LEAVES and STREAM_LEAVES[name](value)):
+                continue
+            opts[name] = value
+        case["options"] = opts
+        steps = [first]
+        for _ in range(int(rng.integers(1, 4))):
+            what = rng.random()
+            if what < 0.3:
+                steps.append(_stream_step_option(rng, n))
+            elif what < 0.5:
+                steps.append(("set_mask", _pick(rng, MASKS), int(rng.integers(1, 1 << 30))))
+            elif what < 0.75:
+                steps.append(("set_ref", {"scale": float(_pick(rng, (1e-3, 0.5, 1.0, 7.0, 1e6))),
+                                          "offset": float(_pick(rng, (0.0, 3.0, -50.0, 1e3))),
+                                          "quantum": _pick(rng, (None, None, 0.5))}))
+            if metric == 2 and rng.random() < 0.25:
+                steps.append(("set_option", "cosine_centre", int(rng.integers(0, 2))))
+                steps.append(("set_ref", {"scale": 1.0, "offset": 0.0, "quantum": None}))
+            steps.append(_stream_query(rng, n, g))
+        case["steps"] = steps
+        out.append(case)
+    return out
+
+
 # ---- the fixed large cases (sampled rows against the oracle) -------------------------------------------------------
 
 def large_cases():
@@ -254,21 +384,35 @@ def mode_env(case):
 def planned_queries(metric, seed):
     """Every query of the cases of (metric, seed) as query_plan arguments: (case, n, g, m, k, drop, mode, options) -- the
     options in force at that step (set_option steps included)."""
+    return _planned(cases(metric, seed))
+
+
+def stream_planned_queries(metric, seed):
+    """planned_queries for stream_cases(metric, seed); the tuple carries the step's number and the mask in force as well:
+    (case, n, g, m, k, drop, mode, options, step, mask)."""
+    return _planned(stream_cases(metric, seed), more=True)
+
+
+def _planned(case_list, more=False):
     out = []
-    for case in cases(metric, seed):
-        opts = dict(case["options"])
-        for st in case["steps"]:
+    for case in case_list:
+        opts, mask = dict(case["options"]), case["mask"]
+        for i, st in enumerate(case["steps"]):
             if st[0] == "set_option":
                 opts[st[1]] = st[2]
+            elif st[0] == "set_mask":
+                mask = st[1]
             elif st[0] == "query":
-                out.append((case, case["n"], case["g"], st[1], st[2], st[3], case["mode"], dict(opts)))
+                q = (case, case["n"], case["g"], st[1], st[2], st[3], case["mode"], dict(opts))
+                out.append(q + (i, mask) if more else q)
     return out
 
 
 def describe(case, step=None):
     """One line that names a case: how to replay it and what it set."""
-    s = "metric=%d seed=%d case=%d (replay: python tests/test_option_sweep_gpu.py %d %d %d) n=%d g=%d flavour=%s mask=%s mode=%s f=%g options=%s" % (
-        case["metric"], case["seed"], case["case"], case["metric"], case["seed"], case["case"], case["n"], case["g"],
+    script = "tests/test_stream_sweep_gpu.py" if case.get("sweep") == "stream" else "tests/test_option_sweep_gpu.py"
+    s = "metric=%d seed=%d case=%d (replay: python %s %d %d %d) n=%d g=%d flavour=%s mask=%s mode=%s f=%g options=%s" % (
+        case["metric"], case["seed"], case["case"], script, case["metric"], case["seed"], case["case"], case["n"], case["g"],
         case["flavour"], case["mask"], case["mode"], case["dist_factor"], case["options"])
     if step is not None:
         s += " step=%d %s" % (step, case["steps"][step])

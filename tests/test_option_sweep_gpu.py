@@ -4,7 +4,10 @@ The cases come from tests/_option_sweep.py: options, NABO_L2_MODE / NABO_CANBERR
 script of calls on one resident index (queries, set_option, set_mask, set_ref with other data).  Every query must equal
 the oracle's bits and a default index's on the same data, and across a metric's cases every pass and filter kernel must
 have answered rows: a sweep that quietly stops reaching a pass fails.  A failure names its case; one line replays it:
-    python tests/test_option_sweep_gpu.py <metric> <seed> <case>"""
+    python tests/test_option_sweep_gpu.py <metric> <seed> <case>
+
+These cases never reach the two-level stream or the local seeds; tests/test_stream_sweep_gpu.py plays _option_sweep's
+stream_cases through run_case below for those."""
 import os
 import sys
 from collections import Counter
@@ -48,8 +51,9 @@ def _index(case, mp, options, with_mode=True):
             mp.delenv(env[0])
 
 
-def run_case(case, mp, tally):
-    """Play the case's script on an index with its options and mode and on a default index; compare every query."""
+def run_case(case, mp, tally, on_query=None):
+    """Play the case's script on an index with its options and mode and on a default index; compare every query.
+    on_query(case, step, options now, plan, last_stats(), last_kernel(), last_row_pass()) sees every query that passed."""
     from nabo_amd import _knn
     metric, n, g, f = case["metric"], case["n"], case["g"], case["dist_factor"]
     opts = dict(case["options"])
@@ -79,6 +83,7 @@ def run_case(case, mp, tally):
                 X = S.make_targets(case, variant, Y, m, drop, 1000 * case["case"] + i)
                 got = ix.query(X, k, drop_first=drop)
                 rp, kern = ix.last_row_pass(m), ix.last_kernel()
+                stats = ix.last_stats() if on_query else None
                 want = oracle.knn(X, Y, k, metric, f, ref_mask=mask, drop_first=drop, nthreads=16)
                 _same(got, want, "oracle: " + where)
                 _same(got, dflt.query(X, k, drop_first=drop), "default index: " + where)
@@ -88,6 +93,9 @@ def run_case(case, mp, tally):
                 if metric != 1 and kern.startswith("l2c_topk_kernel"):
                     plan = _knn.query_plan(n, g, m, k, metric=metric, drop_first=drop, l2_mode=case["mode"], options=opts)
                     tally["geometry"][plan["geometry"]] += 1
+                if on_query:
+                    plan = _knn.query_plan(n, g, m, k, metric=metric, drop_first=drop, l2_mode=case["mode"], options=opts)
+                    on_query(case, i, dict(opts), plan, stats, kern, rp)
     finally:
         ix.close()
         dflt.close()
