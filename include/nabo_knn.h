@@ -112,7 +112,11 @@ int nabo_index_destroy(nabo_index *ix);
  * workgroup in the stream's main launch: a wave more than "two_level_window" reference tiles ahead of the slowest wave of
  * its workgroup that is still running sleeps until it is not, so that the four share their tiles through the cache --
  * 0 = 8 tiles, at most 4096, -1 = no window; it looks every "two_level_check" tiles, 0 = 16, even, at most 64; results and
- * tile counters are the same bits at every setting).  When the two-level stream ran, nabo_index_last_kernel reports its
+ * tile counters are the same bits at every setting), "two_level_sub" and "two_level_sub_rank" (the order of the cells inside
+ * a bucket of the stream's two copies: every bucket of at least "two_level_sub" unmasked references takes that many of them
+ * as sub-anchors and both copies sort its cells by their nearest sub-anchor -- 0 = the default, 1 = caller order, at most
+ * 64; the sub-anchors are ranked along their first principal direction, "two_level_sub_rank" = 1: by index; the results
+ * are the same bits at every setting, the tile counters are not).  When the two-level stream ran, nabo_index_last_kernel reports its
  * tile counters behind the kernel's name: " [two-level tiles: one-step N, refetched N, two-step N]", summed over the waves.
  * Unknown names: NABO_E_INVALID.
  * The library reads TWO environment variables, once, in nabo_index_create: NABO_L2_MODE = f32 | f16x3 (which Euclidean /

@@ -192,6 +192,15 @@ class KnnIndex:
         _lib.check(_lib.lib().nabo_index_last_row_pass(self._h, out.ctypes.data, int(m)))
         return out
 
+    def stream_order(self):
+        """(row_map, ref_map) of the last query, if it took the two-level stream: the target row and the reference at every
+        position of the two bucket-ordered copies, 0xFFFFFFFF for padding (include/nabo_knn_inspect.h)"""
+        nr, ny = C.c_int64(), C.c_int64()
+        _lib.check(_lib.lib().nabo_index_stream_order(self._h, None, C.byref(nr), None, C.byref(ny)))
+        rows, refs = np.empty(nr.value, dtype=np.uint32), np.empty(ny.value, dtype=np.uint32)
+        _lib.check(_lib.lib().nabo_index_stream_order(self._h, rows.ctypes.data, C.byref(nr), refs.ctypes.data, C.byref(ny)))
+        return rows, refs
+
     def last_kernel(self):
         """name of the dominant kernel the last query ran (which filter the launch logic picked)"""
         buf = C.create_string_buffer(256)

@@ -85,6 +85,9 @@ POTENTIAL_SYMBOLS = ["nabo_potential_create", "nabo_potential_destroy", "nabo_po
                      "nabo_potential_set_state", "nabo_potential_finish", "nabo_potential_solve", "nabo_potential_info",
                      "nabo_potential_last_ms", "nabo_potential_geometry"]
 
+# what include/nabo_knn_inspect.h declares (a look into an index, for tests and tools)
+INSPECT_SYMBOLS = ["nabo_index_stream_order"]
+
 
 class NaboError(RuntimeError):
     pass
@@ -119,6 +122,7 @@ def lib():
     L.nabo_index_last_kernel.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.nabo_index_last_passes.argtypes = [vp, C.POINTER(i64)]
     L.nabo_index_last_row_pass.argtypes = [vp, vp, i64]
+    L.nabo_index_stream_order.argtypes = [vp, vp, C.POINTER(i64), vp, C.POINTER(i64)]
     L.nabo_merge_topk.argtypes = [i32, vp, vp, i32, i64, i32, i32, i32, vp, vp]
     L.nabo_snn_counts.argtypes = [i32, vp, i64, vp, i64, i32, vp]
     L.nabo_dev_malloc.argtypes = [i32, C.POINTER(vp), C.c_size_t]
@@ -241,7 +245,7 @@ def lib():
     L.nabo_potential_last_ms.argtypes = [vp, C.POINTER(dbl)]
     L.nabo_potential_geometry.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     for name in (SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS + UMAP_SYMBOLS
-                 + UMAP_TRANSFORM_SYMBOLS + COMMUNITY_SYMBOLS + AGGLOM_SYMBOLS + POTENTIAL_SYMBOLS):
+                 + UMAP_TRANSFORM_SYMBOLS + COMMUNITY_SYMBOLS + AGGLOM_SYMBOLS + POTENTIAL_SYMBOLS + INSPECT_SYMBOLS):
         if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy", "nabo_umap_destroy", "nabo_umap_transform_destroy", "nabo_community_destroy",
                         "nabo_potential_destroy"):
             getattr(L, name).restype = C.c_int

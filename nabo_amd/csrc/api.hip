@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../../include/nabo_knn_inspect.h"
 #include "index.h"
 
 using namespace nabo;
@@ -211,6 +212,23 @@ int nabo_index_last_row_pass(const nabo_index *ix, uint8_t *out, int64_t m)
         return api_fail(NABO_E_INVALID, "the last nabo_index_query on this index had %lld rows, not %lld (candidate queries keep no record)",
                         (long long)ix->last.row_pass.size(), (long long)m);
     if (m > 0) memcpy(out, ix->last.row_pass.data(), (size_t)m);
+    return NABO_OK;
+}
+
+int nabo_index_stream_order(nabo_index *ix, uint32_t *row_map, int64_t *n_row_pos, uint32_t *ref_map, int64_t *n_ref_pos)
+{
+    if (!ix || !n_row_pos || !n_ref_pos) return api_fail(NABO_E_INVALID, "NULL argument");
+    int rc;
+    if ((rc = index_idle(ix)) || (rc = use_device(ix->device))) return rc;
+    const auto &l2 = ix->ref.l2;
+    if (!ix->last.tl_ran || !l2.ord_built || ix->last.tl_row_pos <= 0)
+        return api_fail(NABO_E_INVALID, "the last query on this index did not take the two-level stream");
+    *n_row_pos = ix->last.tl_row_pos;
+    *n_ref_pos = l2.ord_tiles * 32;
+    if (!row_map || !ref_map) return NABO_OK;
+    HIP_TRY(hipMemcpyAsync(row_map, ix->ws.lmap.p, (size_t)*n_row_pos * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipMemcpyAsync(ref_map, l2.yordmap.p, (size_t)*n_ref_pos * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
     return NABO_OK;
 }
 

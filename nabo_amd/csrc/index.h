@@ -47,6 +47,9 @@ struct Options {
     // per reference bucket, with that first two-step stretch (tiles)
     int two_level = 1, two_level_share = 0, two_level_stretch = 0, two_level_burst = 0;
     int two_level_window = 0, two_level_check = 0;       // l2c_window.h: tiles; window -1 = none, 0 = the defaults
+    // the order of the cells INSIDE a bucket of the stream's two copies (local_seeds.h): sub-anchors per bucket (0: the
+    // default, 1: caller order, at most 64) and how they are ranked (0: along their first principal direction, 1: by index)
+    int two_level_sub = 0, two_level_sub_rank = 0;
 };
 bool option_set(Options &o, const char *name, int64_t value);
 
@@ -133,6 +136,7 @@ int plan_l2(const IndexShape &sh, const PassCtx &ctx, int64_t m, int k, int drop
 bool two_level_slots(const IndexShape &sh);
 void shape_refresh(IndexShape &sh);          // kc1 after a change of options (g = 29 under option two_level = 2)
 void lseed_params(const IndexShape &sh, int *C, int *cap);
+int lseed_sub_param(const IndexShape &sh);      // sub-anchors per bucket of the two-level stream's copies (1: no sub-order)
 bool lseed_applies(const IndexShape &sh, const L2Plan &P, int S, int64_t rows);
 
 struct CbPlan {
@@ -199,6 +203,11 @@ struct nabo_index {
             nabo::DevBuf lanchors, lrefcnt;
             int64_t local_room = 0;
             int local_C = 0, local_cap = 0;
+            // the sub-order of the ordered copy (local_seeds.h): built for local_sub sub-anchors per bucket (1: none) ranked by
+            // rule local_sub_rank; their component slots [local_C][local_sub] as chunks, their norms and ranks -- the queries
+            // sort their rows with the same tables
+            nabo::DevBuf lsub, lsubnorm, lsubrank;
+            int local_sub = 1, local_sub_rank = 0;
             bool local_built = false;
             double ymax_sqrt = 0.0, ymax_sqrt_c = 0.0;
             // the largest reference norm of the last pack, on its way to the host (ensure_packed / ymax_resolve): pinned word,
@@ -232,6 +241,9 @@ struct nabo_index {
         // local tournament seeds: the counting sort's keys, block counts, bucket totals and layout (shared by the reference
         // build and the queries: one stream); the bucket-ordered target tiles, their row map and the columns' ranges
         nabo::DevBuf lkey, lblk, ltot, llay, xpre, lmap, lranges;
+        // the sub-order: the bucket-ordered copy before it and its map, the second sort's keys, block counts, class totals
+        // and first positions, the sub-anchors as floats (scratch of the ranking)
+        nabo::DevBuf lsubpk, lsubmap, lkey2, lblk2, ltot2, lsublay, lsubf;
         nabo::DevBuf tlstats;                     // the two-level launch's tile counters [3] (l2c_topk.hip)
     } ws;
 
@@ -246,6 +258,7 @@ struct nabo_index {
         int64_t counters[4] = {0, 0, 0, 0};
         char kernel[256] = "";          // dominant kernel of the last query (nabo_index_last_kernel)
         bool tl_ran = false;
+        int64_t tl_row_pos = 0;         // positions of the bucket-ordered target copy the two-level launch read (nabo_index_stream_order)
     } last;
 
     // nabo_index_query_async: the query runs on a host thread of its own (it synchronises its stream between its passes);

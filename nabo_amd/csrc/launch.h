@@ -102,6 +102,18 @@ hipError_t lseed_layout_launch(int C, const uint32_t *ref_cnt, const uint32_t *r
 hipError_t lseed_ends_launch(int C, const int64_t *lay, int32_t *end, hipStream_t st);
 hipError_t lseed_move_launch(int kc, const unsigned char *src, int64_t ncell, const uint32_t *key, const uint32_t *blockoff, int C,
                              const int64_t *lay, int cap, int64_t pad_cell, unsigned char *dst, uint32_t *row_map, hipStream_t st);
+// the sub-order inside the buckets of the two-level stream's copies (local_seeds.h): S sub-anchors per bucket, a second
+// counting sort over a bucket-ordered copy (map1 [position] = cell, key1 [cell] >> 16 = bucket)
+size_t lseed_sub_anchor_bytes(int kc, int C, int S);
+size_t lseed_sub_float_bytes(int kc, int C, int S);
+hipError_t lseed_sub_build_launch(int kc, const unsigned char *pk, const int64_t *lay, const uint32_t *ref_cnt, int g, int C, int S,
+                                  bool by_index, void *anchors, float *subf, uint8_t *rank, float *norm, hipStream_t st, bool two_level);
+hipError_t lseed_sub_sort_launch(int kc, bool is_ref, const unsigned char *pk, int64_t npos, const uint32_t *map1, const uint32_t *key1,
+                                 const void *anchors, const float *norm, const uint8_t *rank, const uint32_t *ref_cnt, int C, int S,
+                                 const int64_t *lay, uint32_t *key2, uint32_t *blockcnt, uint32_t *tot, int64_t *sublay, hipStream_t st);
+hipError_t lseed_sub_move_launch(int kc, const unsigned char *src, int64_t npos, const uint32_t *map1, const uint32_t *key2,
+                                 const uint32_t *blockoff, const int64_t *sublay, const unsigned char *pad_src, int64_t pad_cell, int C,
+                                 const int64_t *lay, unsigned char *dst, uint32_t *dst_map, hipStream_t st);
 
 // list merges, float64 re-evaluation, exact kernels and row helpers (refine.hip)
 hipError_t merge_lists_launch(const uint32_t *cand_idx, const float *cand_key, const float *cand_tau, int64_t rows, int S, int L,

@@ -48,8 +48,20 @@ static const OptionName TWO_LEVEL_OPTION_NAMES[] = {
     {"two_level_check", &Options::two_level_check},
 };
 
+// The sub-order inside the stream's buckets (local_seeds.h).  A table of its own: tests/test_sub_order_gpu.py runs its
+// values, clamps included, against the oracle.
+static const OptionName SUB_ORDER_OPTION_NAMES[] = {
+    {"two_level_sub", &Options::two_level_sub}, {"two_level_sub_rank", &Options::two_level_sub_rank},
+};
+
 bool option_set(Options &o, const char *name, int64_t value)
 {
+    for (const OptionName &e : SUB_ORDER_OPTION_NAMES)
+        if (strcmp(e.name, name) == 0) {            // clamped: sub-anchors 0 .. LSEED_MAX_SUB, the ranking rule 0 .. 1
+            const int64_t hi = e.field == &Options::two_level_sub ? LSEED_MAX_SUB : 1;
+            o.*(e.field) = (int)(value < 0 ? 0 : value > hi ? hi : value);
+            return true;
+        }
     for (const OptionName &e : TWO_LEVEL_OPTION_NAMES)
         if (strcmp(e.name, name) == 0) {            // clamped: 0 .. 2, percent, refetches, tiles (the window: -1 = none)
             const int64_t hi = e.field == &Options::two_level ? 2 : e.field == &Options::two_level_share ? 100
@@ -108,6 +120,9 @@ void lseed_params(const IndexShape &sh, int *C, int *cap)
     *C = c;
     *cap = k;
 }
+
+// Sub-anchors per bucket of the two-level stream's copies: only where the stream's operands exist
+int lseed_sub_param(const IndexShape &sh) { return two_level_slots(sh) ? lseed_sub_count(sh.opt.two_level_sub) : 1; }
 
 // Local seeds serve a launch of the first one-product pass with ONE reference split (a seed bounds the lkeep-th smallest
 // score over a split's own references only if the sample lies inside it: every bucket does for S = 1), where the tournament

@@ -106,8 +106,9 @@ struct L2Part {
 // packed operands, counting sort, a bucket-ordered copy of their tiles for the tournament alone -- and ONE tournament launch
 // whose columns each run over their bucket's references; rows of buckets too small for one keep the stream's first tiles
 // (pt, gt: l2c_pre_plan's; pt = 0: no tournament there, those rows start from +inf).  No host wait: counts, layout and
-// ranges stay on the device.
-static int local_seeds(nabo_index *ix, const Query &q, const L2Plan &P, L2Part &p, int pt, int gt)
+// ranges stay on the device.  sub: the launch streams the copy (two-level) -- its rows are sorted once more inside their
+// buckets, by the sub-anchors the ordered references were sorted with (local_seeds.h).
+static int local_seeds(nabo_index *ix, const Query &q, const L2Plan &P, L2Part &p, int pt, int gt, bool sub)
 {
     const IndexShape &sh = ix->shape;
     auto &l2 = ix->ref.l2;
@@ -135,6 +136,23 @@ static int local_seeds(nabo_index *ix, const Query &q, const L2Plan &P, L2Part &
                               ws.ltot.as<uint32_t>(), st, l2.slots2));
     HIP_TRY(lseed_layout_launch(C, l2.lrefcnt.as<uint32_t>(), ws.ltot.as<uint32_t>(), cap, P.lkeep, (int)sh.ref_tiles_alloc, rest,
                                 ws.llay.as<int64_t>(), ws.lranges.as<int>(), ncol, st));
+    if (sub) {
+        const int S = l2.local_sub;
+        if ((rc = ws.lsubpk.reserve((size_t)(prow / 32) * tile_bytes + 128)) || (rc = ws.lsubmap.reserve((size_t)prow * sizeof(uint32_t))) ||
+            (rc = ws.lkey2.reserve(lseed_key_bytes(prow))) || (rc = ws.lblk2.reserve(lseed_blockcnt_bytes(prow, C * S))) ||
+            (rc = ws.ltot2.reserve((size_t)C * S * sizeof(uint32_t))) || (rc = ws.lsublay.reserve((size_t)C * S * sizeof(int64_t))))
+            return rc;
+        HIP_TRY(hipMemsetAsync(ws.lsubmap.p, 0xFF, (size_t)prow * sizeof(uint32_t), st));
+        HIP_TRY(lseed_move_launch(kc, xh, nrows, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), 0, 0,
+                                  ws.lsubpk.as<unsigned char>(), ws.lsubmap.as<uint32_t>(), st));
+        HIP_TRY(lseed_sub_sort_launch(kc, false, ws.lsubpk.as<unsigned char>(), prow, ws.lsubmap.as<uint32_t>(), ws.lkey.as<uint32_t>(),
+                                      l2.lsub.p, l2.lsubnorm.as<float>(), l2.lsubrank.as<uint8_t>(), l2.lrefcnt.as<uint32_t>(), C, S,
+                                      ws.llay.as<int64_t>(), ws.lkey2.as<uint32_t>(), ws.lblk2.as<uint32_t>(), ws.ltot2.as<uint32_t>(),
+                                      ws.lsublay.as<int64_t>(), st));
+        HIP_TRY(lseed_sub_move_launch(kc, ws.lsubpk.as<unsigned char>(), prow, ws.lsubmap.as<uint32_t>(), ws.lkey2.as<uint32_t>(),
+                                      ws.lblk2.as<uint32_t>(), ws.lsublay.as<int64_t>(), xh, 0, C, ws.llay.as<int64_t>(),
+                                      ws.xpre.as<unsigned char>(), ws.lmap.as<uint32_t>(), st));
+    } else
     HIP_TRY(lseed_move_launch(kc, xh, nrows, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), 0, 0,
                               ws.xpre.as<unsigned char>(), ws.lmap.as<uint32_t>(), st));
     HIP_TRY(l2c_pre_launch(kc, P.lkeep, ws.xpre.as<unsigned char>(), l2.ycpk1.as<unsigned char>(), (int)p.tps, 1, prow, 0, 0, 2,
@@ -184,11 +202,12 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
         int pt = 0, gt = 2;
         l2c_pre_plan(P.kcq, P.lkeep, (int)p.tps, pre_pct, &pt, &gt);
         if (first && p.gx > 0 && lseed_applies(sh, P, p.S, p.end(q.m) - p.row0)) {
-            if ((rc = local_seeds(ix, q, P, p, pt, gt))) return rc;
+            const bool ord = i == 0 && P.tl_main && l2.ord_built && l2.tl_verdict != 2;
+            if ((rc = local_seeds(ix, q, P, p, pt, gt, ord && l2.local_sub > 1))) return rc;
             seed[i] = p.pre->as<float>();
             stride[i] = p.S;
             if (i == 0 && first) ix->last.pre_tiles_last = pt;
-            if (i == 0 && P.tl_main && l2.ord_built && l2.tl_verdict != 2) ordered = true;
+            if (ord) ordered = true;
             continue;
         }
         if (pt <= 0 || p.gx == 0) continue;
@@ -246,6 +265,7 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
                                     p.merge ? p.key->as<float>() : nullptr, p.tau->as<float>(), l2.ord_tiles, st, prow, seed[i],
                                     stride[i], 0, &ord));
             ix->last.tl_ran = true;
+            ix->last.tl_row_pos = prow;
         } else
         // (rows beyond the part's are padding to it: the main part of a plan cut on whole rounds of positions, run in
         // caller order after all, ends inside a workgroup and the tail launch takes over there)

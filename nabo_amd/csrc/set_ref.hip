@@ -95,6 +95,9 @@ int ensure_local_seeds(nabo_index *ix)
     lseed_params(sh, &C, &cap);
     if (C == 0) return NABO_OK;
     if (l2.packed_c1 && l2.slots2 != two_level_slots(sh)) l2.packed_c1 = false;
+    const int S = lseed_sub_param(sh), srank = sh.opt.two_level_sub_rank;
+    // (a sub-order asked for since the copy was built, or another one: the ordered copy is built again)
+    if (l2.ord_built && (l2.local_sub != S || (S > 1 && l2.local_sub_rank != srank))) l2.ord_built = false;
     if (l2.local_built && l2.local_C == C && l2.local_cap == cap && l2.packed_c1 && (l2.ord_built || !l2.slots2 || l2.tl_verdict == 2)) return NABO_OK;
     if (!l2.packed_c1 || l2.local_room < (int64_t)C * (cap / 32)) {           // (options changed since the pack: room for the runs)
         l2.packed_c1 = false;
@@ -126,8 +129,35 @@ int ensure_local_seeds(nabo_index *ix)
         HIP_TRY(hipMemsetAsync(l2.yordmap.p, 0xFF, (size_t)(ot + 2) * 32 * sizeof(uint32_t), st));
         HIP_TRY(lseed_layout_launch(C, l2.lrefcnt.as<uint32_t>(), nullptr, 0, 1, 0, rest, ws.llay.as<int64_t>(), nullptr, 0, st));
         HIP_TRY(lseed_ends_launch(C, ws.llay.as<int64_t>(), l2.yordend.as<int32_t>(), st));      // (the query reuses llay: the ends are kept)
+        if (S > 1) {
+            // The sub-order (local_seeds.h): the bucket-ordered copy goes to scratch first -- its buckets in caller order are
+            // where the sub-anchors are drawn from --, a second sort inside the buckets makes the copy the stream reads.  The
+            // runs of the tournament above were drawn before it: a spread sample of their buckets, as they always were.
+            const int64_t npos = ot * 32;
+            if ((rc = ws.lsubpk.reserve((size_t)ot * sh.kc1 * 1024 + 128)) || (rc = ws.lsubmap.reserve((size_t)npos * sizeof(uint32_t))) ||
+                (rc = l2.lsub.reserve(lseed_sub_anchor_bytes(sh.kc1, C, S))) || (rc = ws.lsubf.reserve(lseed_sub_float_bytes(sh.kc1, C, S))) ||
+                (rc = l2.lsubnorm.reserve((size_t)C * S * sizeof(float))) || (rc = l2.lsubrank.reserve((size_t)C * S)) ||
+                (rc = ws.lkey2.reserve(lseed_key_bytes(npos))) || (rc = ws.lblk2.reserve(lseed_blockcnt_bytes(npos, C * S))) ||
+                (rc = ws.ltot2.reserve((size_t)C * S * sizeof(uint32_t))) || (rc = ws.lsublay.reserve((size_t)C * S * sizeof(int64_t))))
+                return rc;
+            HIP_TRY(hipMemsetAsync(ws.lsubmap.p, 0xFF, (size_t)npos * sizeof(uint32_t), st));
+            HIP_TRY(lseed_move_launch(sh.kc1, ypk, sh.n, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), 0,
+                                      (sh.ref_tiles_alloc - 1) * 32, ws.lsubpk.as<unsigned char>(), ws.lsubmap.as<uint32_t>(), st));
+            HIP_TRY(lseed_sub_build_launch(sh.kc1, ws.lsubpk.as<unsigned char>(), ws.llay.as<int64_t>(), l2.lrefcnt.as<uint32_t>(), sh.g, C, S,
+                                           srank != 0, l2.lsub.p, ws.lsubf.as<float>(), l2.lsubrank.as<uint8_t>(), l2.lsubnorm.as<float>(), st,
+                                           l2.slots2));
+            HIP_TRY(lseed_sub_sort_launch(sh.kc1, true, ws.lsubpk.as<unsigned char>(), npos, ws.lsubmap.as<uint32_t>(), ws.lkey.as<uint32_t>(),
+                                          l2.lsub.p, l2.lsubnorm.as<float>(), l2.lsubrank.as<uint8_t>(), l2.lrefcnt.as<uint32_t>(), C, S,
+                                          ws.llay.as<int64_t>(), ws.lkey2.as<uint32_t>(), ws.lblk2.as<uint32_t>(), ws.ltot2.as<uint32_t>(),
+                                          ws.lsublay.as<int64_t>(), st));
+            HIP_TRY(lseed_sub_move_launch(sh.kc1, ws.lsubpk.as<unsigned char>(), npos, ws.lsubmap.as<uint32_t>(), ws.lkey2.as<uint32_t>(),
+                                          ws.lblk2.as<uint32_t>(), ws.lsublay.as<int64_t>(), ypk, (sh.ref_tiles_alloc - 1) * 32, C,
+                                          ws.llay.as<int64_t>(), l2.yord.as<unsigned char>(), l2.yordmap.as<uint32_t>(), st));
+        } else
         HIP_TRY(lseed_move_launch(sh.kc1, ypk, sh.n, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), 0,
                                   (sh.ref_tiles_alloc - 1) * 32, l2.yord.as<unsigned char>(), l2.yordmap.as<uint32_t>(), st));
+        l2.local_sub = S;
+        l2.local_sub_rank = srank;
         l2.ord_tiles = ot;
         l2.ord_built = true;
     }
