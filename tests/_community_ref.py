@@ -259,6 +259,70 @@ def tiny_graphs():
     return g
 
 
+def hubs_graph(lengths, pool=200, seed=3):
+    """one hub per entry of `lengths` with exactly that many neighbours, drawn from a weighted ring of `pool` leaves"""
+    rng = np.random.default_rng(seed)
+    n = pool + len(lengths)
+    edges = [(i, (i + 1) % pool, round(float(rng.integers(1, 101)) / 100, 2)) for i in range(pool)]
+    for h, L in enumerate(lengths):
+        for j in rng.choice(pool, size=L, replace=False).tolist():
+            edges.append((n - len(lengths) + h, j, round(float(rng.integers(1, 101)) / 100, 2)))
+    return csr_of_edges(n, edges)
+
+
+def many_hubs_graph(hubs, leaves, seed=3):
+    """`hubs` hubs, each joined to every one of `leaves` leaves; the leaves sit on a ring; every weight is
+    integers(1, 101) / 100.  The hubs are the last nodes"""
+    rng = np.random.default_rng(seed)
+    edges = [(i, (i + 1) % leaves, round(float(rng.integers(1, 101)) / 100, 2)) for i in range(leaves)]
+    edges += [(leaves + h, j, round(float(rng.integers(1, 101)) / 100, 2)) for h in range(hubs) for j in range(leaves)]
+    return csr_of_edges(leaves + hubs, edges)
+
+
+def capacity_graphs(cap):
+    """name -> (ptr, nbr, w): the graphs made for the sweep's table of `cap` distinct neighbour communities
+    (tests/test_community_gpu.py runs them, tests/test_community_cpu.py asserts what their rows hold)"""
+    return {"many_over_capacity": many_hubs_graph(20, cap + 40),
+            "hubs_capacity": hubs_graph([cap - 1, cap, cap + 1], pool=cap + 40),
+            "hubs_long_fit": hubs_graph([257, 600, 1500], pool=1600)}
+
+
+CAPACITY_GRAPHS = ("many_over_capacity", "hubs_capacity", "hubs_long_fit")
+
+
+def distinct_neighbour_communities(lv, comm, rows):
+    """per row of `rows` the number of distinct communities among its neighbours j != i"""
+    comm = np.asarray(comm)
+    return [len(set(comm[lv.dst[lv.src == i]].tolist())) for i in rows]
+
+
+def check_capacity_graph(name, lv, two_m, long_threshold, cap, seed, workgroup=256):
+    """asserts that a graph of capacity_graphs meets the path it was made for: the hubs' row lengths and, from the
+    yardstick's own trace, how many distinct neighbour communities they have in the sweeps that matter.  `workgroup`:
+    the lanes of the long path's workgroup (CM_THREADS in nabo_amd/csrc/community.hip)"""
+    rows = np.bincount(lv.src, minlength=lv.n)
+    if name == "many_over_capacity":
+        hubs = list(range(lv.n - 20, lv.n))
+        assert rows[-20:].tolist() == [cap + 40] * 20 and rows[:-20].max() <= long_threshold
+        trace = []
+        phase(lv, 1.0, two_m, seed, 0, trace=trace)
+        assert len(trace) >= 2
+        # sweep 0: 20 rows beyond the table, on 8 workgroups: every dense table is used two or three times
+        assert distinct_neighbour_communities(lv, trace[0][0], hubs) == [cap + 40] * 20
+        # sweep 1: the same rows fit the table, at 91 % load
+        d1 = distinct_neighbour_communities(lv, trace[1][0], hubs)
+        assert d1 == [1862] * 20 and 0.9 * cap < d1[0] <= cap
+    elif name == "hubs_capacity":                            # from singletons: one under, at and one over a full table
+        want = [cap - 1, cap, cap + 1]
+        assert rows[-3:].tolist() == want and rows[:-3].max() <= long_threshold
+        assert distinct_neighbour_communities(lv, np.arange(lv.n), [lv.n - 3, lv.n - 2, lv.n - 1]) == want
+    elif name == "hubs_long_fit":                            # more arcs than the workgroup has lanes, and they fit the table
+        assert rows[-3:].tolist() == [257, 600, 1500] and rows[:-3].max() <= long_threshold
+        assert workgroup < 257 and 2 * workgroup < 600 and 1500 < cap
+    else:
+        raise KeyError(name)
+
+
 def blob_snn_graph(n=3000, centres=8, dims=10, k=11, seed=0):
     """Nabo's SNN graph of Gaussian blobs: every cell lists its k nearest cells (itself included), an edge weighs
     round(s / (2 (k - 1) - s), 2), s the neighbours both ends share (nabo/_mapping.py:185-198)"""

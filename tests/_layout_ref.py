@@ -36,31 +36,49 @@ class Graph:
         self.w = np.array([a[2] for a in arcs], dtype=np.float64)
 
 
+def simple_graph(n, lo, hi, w):
+    """the same Graph from pairs lo < hi that are distinct already, with numpy alone"""
+    lo, hi, w = np.asarray(lo, dtype=np.int64), np.asarray(hi, dtype=np.int64), np.asarray(w, dtype=np.float64)
+    assert (lo < hi).all() and len(np.unique(lo * n + hi)) == len(lo)
+    src, dst, ww = np.concatenate([lo, hi]), np.concatenate([hi, lo]), np.concatenate([w, w])
+    o = np.lexsort((dst, src))
+    g = Graph.__new__(Graph)
+    g.n, g.mass = n, 1.0 + np.bincount(src, minlength=n).astype(np.float64)
+    g.src, g.dst, g.w = src[o], dst[o], ww[o]
+    return g
+
+
 def start_state(pos0):
     pos0 = np.asarray(pos0, dtype=np.float64)
     z = np.zeros(len(pos0))
     return dict(x=pos0[:, 0].copy(), y=pos0[:, 1].copy(), dx=z.copy(), dy=z.copy(), speed=1.0, eff=1.0)
 
 
-def step(g, s, **params):
-    """One iteration from the state s (x, y, dx, dy, speed, eff); returns the new state plus
-    rep, grav, attr [n, 2] with rep_abs, grav_abs, attr_abs (sums of |term|), S, T, swing, stopped, and the margins
-    m_half = |S/T - 2| / 2 and m_jt = |S / (jt T) - 1| of step 6's two comparisons."""
+def repulsion_rows(g, x, y, rows, scaling_ratio, chunk=None):
+    """step 2 for the nodes `rows` alone, each against every j: (rep, rep_abs) [len(rows), 2], float64 pair terms on the
+    float32-rounded positions, rep_abs the sums of the absolute terms.  Rows are independent, so a sample of them costs
+    len(rows) * n; `chunk` rows are in flight at a time (all of them by default)"""
+    rows = np.asarray(rows, dtype=np.int64)
+    xf, yf = x.astype(np.float32).astype(np.float64), y.astype(np.float32).astype(np.float64)
+    rep, rep_abs = np.empty((len(rows), 2)), np.empty((len(rows), 2))
+    step_ = len(rows) if not chunk else int(chunk)
+    for a in range(0, len(rows), max(step_, 1)):
+        r = rows[a:a + step_]
+        ddx, ddy = xf[r, None] - xf[None, :], yf[r, None] - yf[None, :]
+        c = (scaling_ratio * g.mass[r])[:, None] * g.mass[None, :] / np.maximum(ddx * ddx + ddy * ddy, D2_MIN)
+        tx, ty = c * ddx, c * ddy
+        rep[a:a + step_] = np.stack([tx.sum(axis=1), ty.sum(axis=1)], axis=1)
+        rep_abs[a:a + step_] = np.stack([np.abs(tx).sum(axis=1), np.abs(ty).sum(axis=1)], axis=1)
+    return rep, rep_abs
+
+
+def local_forces(g, x, y, **params):
+    """steps 3 and 4 for every node, O(n + arcs): (grav, attr, attr_abs) [n, 2]; |grav| is its own sum of absolute terms"""
     p = dict(DEFAULTS, **params)
     n, mass = g.n, g.mass
-    x, y = s["x"], s["y"]
     sr, grav_c = float(p["scaling_ratio"]), float(p["gravity"])
     oad = bool(p["outbound_attraction_distribution"])
     comp = float(np.mean(mass)) if oad else 1.0
-    old = np.stack([s["dx"], s["dy"]], axis=1)
-    # 2. repulsion
-    xf, yf = x.astype(np.float32).astype(np.float64), y.astype(np.float32).astype(np.float64)
-    ddx, ddy = xf[:, None] - xf[None, :], yf[:, None] - yf[None, :]
-    c = (sr * mass)[:, None] * mass[None, :] / np.maximum(ddx * ddx + ddy * ddy, D2_MIN)
-    tx, ty = c * ddx, c * ddy
-    rep = np.stack([tx.sum(axis=1), ty.sum(axis=1)], axis=1)
-    rep_abs = np.stack([np.abs(tx).sum(axis=1), np.abs(ty).sum(axis=1)], axis=1)
-    del ddx, ddy, c, tx, ty
     # 3. gravity
     r = np.sqrt(x * x + y * y)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -79,6 +97,44 @@ def step(g, s, **params):
     np.add.at(attr[:, 1], g.src, ay)
     np.add.at(attr_abs[:, 0], g.src, np.abs(ax))
     np.add.at(attr_abs[:, 1], g.src, np.abs(ay))
+    return grav, attr, attr_abs
+
+
+def speed_step(n, S, T, speed, eff, jitter_tolerance):
+    """step 6 from S, T > 0: (speed, eff, m_half, m_jt, target), the margins m_half = |S/T - 2| / 2 and
+    m_jt = |S / (jt T) - 1| of its two comparisons"""
+    speed, eff, jtol = float(speed), float(eff), float(jitter_tolerance)
+    est = 0.05 * np.sqrt(float(n))
+    jt = jtol * max(np.sqrt(est), min(10.0, est * T / (float(n) * float(n))))
+    m_half = abs(S / T - 2.0) / 2.0
+    if S / T > 2.0:
+        if eff > 0.05:
+            eff *= 0.5
+        jt = max(jt, jtol)
+    target = jt * eff * T / S
+    m_jt = abs(S / (jt * T) - 1.0) if jt * T != 0 else np.inf
+    if S > jt * T:
+        if eff > 0.05:
+            eff *= 0.7
+    elif speed < 1000:
+        eff *= 1.3
+    speed += min(target - speed, 0.5 * speed)
+    return float(speed), float(eff), m_half, m_jt, float(target)
+
+
+def step(g, s, **params):
+    """One iteration from the state s (x, y, dx, dy, speed, eff); returns the new state plus
+    rep, grav, attr [n, 2] with rep_abs, grav_abs, attr_abs (sums of |term|), S, T, swing, stopped, and the margins
+    m_half = |S/T - 2| / 2 and m_jt = |S / (jt T) - 1| of step 6's two comparisons."""
+    p = dict(DEFAULTS, **params)
+    n, mass = g.n, g.mass
+    x, y = s["x"], s["y"]
+    sr = float(p["scaling_ratio"])
+    old = np.stack([s["dx"], s["dy"]], axis=1)
+    # 2. repulsion
+    rep, rep_abs = repulsion_rows(g, x, y, np.arange(n), sr)
+    # 3. gravity, 4. attraction
+    grav, attr, attr_abs = local_forces(g, x, y, **p)
     d = (rep + grav) + attr
     # 5. sums
     swing = mass * np.sqrt(((old - d) ** 2).sum(axis=1))
@@ -91,22 +147,7 @@ def step(g, s, **params):
     if S == 0 or T == 0:
         out["stopped"] = True
         return out
-    speed, eff, jtol = float(s["speed"]), float(s["eff"]), float(p["jitter_tolerance"])
-    est = 0.05 * np.sqrt(float(n))
-    jt = jtol * max(np.sqrt(est), min(10.0, est * T / (float(n) * float(n))))
-    out["m_half"] = abs(S / T - 2.0) / 2.0
-    if S / T > 2.0:
-        if eff > 0.05:
-            eff *= 0.5
-        jt = max(jt, jtol)
-    target = jt * eff * T / S
-    out["m_jt"] = abs(S / (jt * T) - 1.0) if jt * T != 0 else np.inf
-    if S > jt * T:
-        if eff > 0.05:
-            eff *= 0.7
-    elif speed < 1000:
-        eff *= 1.3
-    speed += min(target - speed, 0.5 * speed)
+    speed, eff, out["m_half"], out["m_jt"], _ = speed_step(n, S, T, s["speed"], s["eff"], p["jitter_tolerance"])
     # 7. move
     f = speed / (1.0 + np.sqrt(speed * swing))
     out.update(x=x + d[:, 0] * f, y=y + d[:, 1] * f, speed=float(speed), eff=float(eff), move=np.abs(d) * f[:, None])
@@ -188,3 +229,64 @@ def cases(i_block, j_tile):
         if name == "coincident":
             c["pos0"][9] = c["pos0"][4]        # nodes 4 and 9 start at the same point: the pair contributes exactly 0
     return out
+
+
+# ---- the large graphs: the paths only more than 64 tiles, or more than 256 node blocks, take ---------------------------
+LARGE_STEPS = 2        # iterations a large case is stepped through
+START_SPACING = 8.0    # mean distance between neighbouring nodes of a large case's start
+NODE_BLOCK = 256       # nodes per workgroup of the node kernel, and partial sums the speed kernel takes per pass
+
+
+def ring_chords(n, seed, chords=3):
+    """(ptr, nbr, w, Graph) with numpy alone: the ring i -- i + 1 plus `chords` seeded random partners per node, each
+    distinct pair once, listed from its lower end; weights round(U(0.05, 1), 2).  The graph is not the subject: it
+    gives every node a mass of its own and an attraction"""
+    rng = np.random.default_rng(seed)
+    i = np.arange(n, dtype=np.int64)
+    a = np.concatenate([i, np.repeat(i, chords)])
+    b = np.concatenate([(i + 1) % n, rng.integers(0, n, size=n * chords)])
+    lo, hi = np.minimum(a, b), np.maximum(a, b)
+    key = np.unique((lo * n + hi)[lo != hi])
+    lo, hi = key // n, key % n
+    w = np.round(rng.uniform(0.05, 1.0, len(key)), 2)
+    ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(lo, minlength=n), out=ptr[1:])
+    return ptr, hi, w, simple_graph(n, lo, hi, w)
+
+
+def split_geometry(n, j_tile, n_splits):
+    """(tiles, tiles per split, tiles of the last split) of the repulsion of n nodes in n_splits splits"""
+    ntiles = -(-n // j_tile)
+    per = -(-ntiles // n_splits)
+    return ntiles, per, ntiles - per * (n_splits - 1)
+
+
+def large_cases(j_tile):
+    """{name: dict(ptr, nbr, w, graph, pos0, seed, params)}: one node more than 64 tiles -- the first n whose splits
+    hold two tiles, the last split one tile of one node -- and one node more than NODE_BLOCK blocks of NODE_BLOCK nodes,
+    where the speed kernel's loop over the block sums comes round a second time.  Kept apart from cases(), whose names
+    tests/golden/layout.npz pins.  Start positions START_SPACING sqrt(n) default_rng(100 + seed).random((n, 2)): on the
+    unit square so many nodes start so close that their first move throws them far apart, the second iteration's forces
+    have nothing to do with the first's and S / T comes out as 2 (1 + 5e-4) at n = 65537 whatever the seed, inside MARGIN
+    of step 6's threshold.  With a mean spacing of 8 the repulsion and the attraction are of one size, the second
+    iteration has S / T near 0.1 and S / (jt T) stays 0.2 and more from 1 (measured with the float64 restatement of
+    every pair; the GPU test asserts the margins from the device's S and T)."""
+    out = {}
+    for n, seed in ((64 * j_tile + 1, 21), (NODE_BLOCK * NODE_BLOCK + 1, 22)):
+        ptr, nbr, w, g = ring_chords(n, seed)
+        out["ring_%d" % n] = dict(ptr=ptr, nbr=nbr, w=w, graph=g, seed=seed, params={},
+                                  pos0=START_SPACING * np.sqrt(float(n)) * np.random.default_rng(100 + seed).random((n, 2)))
+    return out
+
+
+def sample_rows(n, i_block, j_tile, seed, n_random=256):
+    """the rows whose repulsion the large cases check: node 0, node n - 1, the first and last node of every i block and of
+    every tile (a lane's four nodes lie a tile apart), every node of the last tile, and n_random seeded random ones;
+    ascending"""
+    rows = {0, n - 1}
+    for width in (i_block, j_tile):
+        for b in range(0, n, width):
+            rows |= {b, min(b + width, n) - 1}
+    rows |= set(range((n - 1) // j_tile * j_tile, n))
+    rows |= set(np.random.default_rng(seed).choice(n, size=min(n_random, n), replace=False).tolist())
+    return np.array(sorted(rows), dtype=np.int64)

@@ -357,4 +357,18 @@ def graph_cases():
     return cases
 
 
+WIDTH_K = (8, 9, 16, 17, 30, 32, 33)
+
+
+def width_cases():
+    """name -> (idx, dist): lists that fill a width of the graph kernels (8, 16, 32), sit one above one (9, 17, 33), and
+    the usual k = 30.  Kept apart from graph_cases(), whose names tests/golden/umap.npz pins"""
+    return {"knn_%dx%d" % (200 + 10 * at, k): _points_case(200 + 10 * at, k, 11 + at, g=6) for at, k in enumerate(WIDTH_K)}
+
+
+def width_of(k):
+    """the lanes a row of k entries takes in the graph kernels (umap_width in nabo_amd/csrc/umap.hip)"""
+    return 8 if k <= 8 else 16 if k <= 16 else 32 if k <= 32 else 64
+
+
 N_EPOCHS_PRUNING, N_EPOCHS_KEEPING = 8, 10 ** 9

@@ -264,8 +264,13 @@ def _case(n_ref, m, k, seed, g=3, dims=2, on_cell=(), dup=None):
     return dict(idx=idx, dist=dist, Y=Y, X=X, Z=Z)
 
 
+GROUP_K = (8, 9, 16, 32, 33, 48)
+
+
 def list_cases():
-    """name -> dict(idx, dist, Y, X, Z): the batches the graph tests run on.  k = 2, 5, 15, 17 and 56; m = 1, 17 and 333"""
+    """name -> dict(idx, dist, Y, X, Z): the batches the graph tests run on.  k = 2, 5, 15, 17 and 56; m = 1, 17 and 333;
+    then k = 8, 9, 16, 32, 33 and 48 (GROUP_K): a graph kernel's width filled and one over, and list lengths that are a
+    multiple of the run kernel's group of 16 lanes or one over, 33 and 48 being three arcs to a lane"""
     cases = {}
     cases["k2_m17"] = _case(40, 17, 2, 101, dims=3)
     cases["k5_m1"] = _case(40, 1, 5, 102)
@@ -280,4 +285,7 @@ def list_cases():
     c = _case(40, 17, 5, 107)
     c["dist"][9, 1:4] = c["dist"][9, 1]
     cases["ties_k5_m17"] = c
+    for at, k in enumerate(GROUP_K):
+        # k = 48: target 4 sits on reference cell 9, d_0 = 0 in the kernel of three arcs to a lane
+        cases["k%d_m17" % k] = _case(200, 17, k, 110 + at, g=5, dims=2 + at % 2, on_cell=[(4, 9)] if k == 48 else ())
     return cases

@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 
 GROUP, LONG, CAP = _community.geometry()
 TINY = cr.tiny_graphs()
+LONG_ROWS = [255, 256, 257, 600]                             # AG_THREADS = 256 (nabo_amd/csrc/agglom.hip)
 
 
 def bits(x):
@@ -40,6 +41,8 @@ def graphs():
     g["unit_ring"] = cr.csr_of_edges(30, [(i, (i + 1) % 30, 1.0) for i in range(30)])
     g["unit_clique"] = cr.csr_of_edges(9, cr.clique(0, 9))
     g["star70"] = cr.csr_of_edges(71, [(0, i, 1.0) for i in range(1, 71)])
+    # long rows around and beyond one round of the long path's workgroup (256 lanes, an arc each per round)
+    g["hubs_long"] = hubs_graph(LONG_ROWS, pool=700)
     g["two_parts"] = cr.csr_of_edges(11, cr.clique(0, 5, 0.3) + cr.clique(5, 6, 0.7))
     g["one_node"] = cr.csr_of_edges(1, [])
     g["no_arcs"] = cr.csr_of_edges(5, [(1, 1, 1.0)])
@@ -81,6 +84,8 @@ def test_one_pass_on_the_constructed_graphs(gpu_lib, name):
         assert rows[-5:].tolist() == [GROUP - 1, GROUP, GROUP + 1, LONG, LONG + 1] == [15, 16, 17, 64, 65]
     if name == "star70":
         assert rows[0] == 70 > LONG
+    if name == "hubs_long":                                  # one below, at, one above and beyond two rounds of 256 lanes
+        assert rows[-4:].tolist() == LONG_ROWS and rows[:-4].max() <= LONG
     rng = np.random.default_rng(1)
     with _community.Community(ptr, nbr, w) as H:
         rp = same_pass(H, lv, two_m)
@@ -223,7 +228,7 @@ def test_round_by_round_on_the_blob_graph(gpu_lib, gold, gold_run):
         assert got.shape == (0, 2) and p == 1
 
 
-@pytest.mark.parametrize("name", ["unit_ring", "unit_clique", "star70", "two_k4_bridge", "k55", "heavy_loops", "hubs_edges"])
+@pytest.mark.parametrize("name", ["unit_ring", "unit_clique", "star70", "two_k4_bridge", "k55", "heavy_loops", "hubs_edges", "hubs_long"])
 def test_rounds_on_the_constructed_graphs(gpu_lib, name):
     ptr, nbr, w = GRAPHS[name]
     levels = []

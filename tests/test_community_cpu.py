@@ -164,6 +164,20 @@ def test_yardstick_on_graphs_whose_answer_is_known():
         assert np.array_equal(l2, res[name][0]) and i2["q"] == res[name][1]["q"]
 
 
+@pytest.mark.parametrize("name", cr.CAPACITY_GRAPHS)
+def test_capacity_graphs_meet_the_paths_they_were_made_for(name):
+    """what tests/test_community_gpu.py relies on: 20 rows beyond the sweep's table in sweep 0 of many_over_capacity and
+    the same rows at 1862 distinct communities in sweep 1, rows one under, at and one over the table, and rows longer
+    than the long path's workgroup that fit -- from the yardstick alone"""
+    _, long_threshold, cap = _community.geometry()
+    hip = open(os.path.join(REPO, "nabo_amd", "csrc", "community.hip")).read()
+    threads, blocks = (int(re.search(r"%s = (\d+);" % c, hip).group(1)) for c in ("CM_THREADS", "CM_HUGE_BLOCKS"))
+    assert 20 > 2 * blocks                                   # every workgroup of the huge path takes more than one row
+    ptr, nbr, w = cr.capacity_graphs(cap)[name]
+    lv, two_m = cr.level0(ptr, nbr, w)
+    cr.check_capacity_graph(name, lv, two_m, long_threshold, cap, 4466, workgroup=threads)
+
+
 def test_split_takes_a_disconnected_community_apart():
     ptr, nbr, w = cr.csr_of_edges(9, cr.clique(0, 4) + cr.clique(4, 4))     # two cliques and an isolated node
     lv0, two_m = cr.level0(ptr, nbr, w)

@@ -24,15 +24,7 @@ def bits(x):
     return struct.pack("<d", float(x))
 
 
-def hubs_graph(lengths, pool=200, seed=3):
-    """one hub per entry of `lengths` with exactly that many neighbours, drawn from a weighted ring of `pool` leaves"""
-    rng = np.random.default_rng(seed)
-    n = pool + len(lengths)
-    edges = [(i, (i + 1) % pool, round(float(rng.integers(1, 101)) / 100, 2)) for i in range(pool)]
-    for h, L in enumerate(lengths):
-        for j in rng.choice(pool, size=L, replace=False).tolist():
-            edges.append((pool + h, j, round(float(rng.integers(1, 101)) / 100, 2)))
-    return cr.csr_of_edges(n, edges)
+hubs_graph = cr.hubs_graph
 
 
 def odds_graph():
@@ -64,6 +56,7 @@ def graphs():
     g["hubs_group"] = hubs_graph([GROUP - 1, GROUP, GROUP + 1])
     g["hubs_threshold"] = hubs_graph([LONG - 1, LONG, LONG + 1, 3 * LONG])
     g["star_over_capacity"] = cr.csr_of_edges(CAP + 2, [(0, i, round((1 + i % 7) / 100, 2)) for i in range(1, CAP + 2)])
+    g.update(cr.capacity_graphs(CAP))                          # many overflow rows, the table's edge, long rows that fit
     g["odds"] = odds_graph()
     g["unit_clique"] = cr.csr_of_edges(7, cr.clique(0, 7))
     g["one_node"] = cr.csr_of_edges(1, [])
@@ -152,7 +145,7 @@ def test_golden_graph_one_step_at_a_time(gpu_lib, gold, gamma):
 @pytest.mark.parametrize("name", list(GRAPHS))
 def test_constructed_graphs_one_step_at_a_time(gpu_lib, name):
     ptr, nbr, w = GRAPHS[name]
-    lv, _ = cr.level0(ptr, nbr, w)
+    lv, two_m = cr.level0(ptr, nbr, w)
     rows = np.bincount(lv.src, minlength=lv.n) if len(lv.src) else np.zeros(lv.n, dtype=np.int64)
     # the graphs meet the paths they were made for
     if name == "hubs_group":
@@ -163,6 +156,9 @@ def test_constructed_graphs_one_step_at_a_time(gpu_lib, name):
         assert rows[0] == CAP + 1 and rows[1:].max() == 1
     if name == "dense_planted":
         assert rows.min() > LONG
+    if name in cr.CAPACITY_GRAPHS:
+        cr.check_capacity_graph(name, lv, two_m, LONG, CAP, SEED)
+        assert N_SWEEPS >= 2                                 # many_over_capacity: sweep 0 overflows, sweep 1 fits at 91 % load
     if name == "odds":
         assert rows[[5, 6, 7, 8]].tolist() == [0, 0, 0, 0] and lv.inn[[5, 6]].tolist() == [5000, 12200] and rows[15] == 0
         assert (11, 12, 2500) in lv.arc_set()

@@ -156,6 +156,53 @@ def test_cases_keep_clear_of_the_branch_thresholds(all_cases):
     print("smallest margins: S/T from 2: %.3g, S/(jt T) from 1: %.3g" % tuple(worst))
 
 
+def test_large_cases_reach_the_paths_they_were_made_for():
+    """what keeps the large GPU cases from passing vacuously if the kernel's geometry changes: every split of the
+    repulsion holds at least two tiles and the last split fewer than the others, and the larger case has more than 256
+    node blocks, so that the speed kernel's strided loop over the block sums comes round a second time.  (Their margins
+    from step 6's thresholds are asserted on the GPU, from the device's S and T: the float64 restatement of all n^2
+    pairs takes minutes.)"""
+    i_block, j_tile, _ = _layout.geometry()
+    hip = open(os.path.join(REPO, "nabo_amd", "csrc", "layout.hip")).read()
+    assert int(re.search(r"LAY_THREADS = (\d+);", hip).group(1)) == lref.NODE_BLOCK
+    large = lref.large_cases(j_tile)
+    assert len(large) == 2 and not set(large) & set(lref.cases(i_block, j_tile))
+    most_blocks = 0
+    for name, c in large.items():
+        g, n = c["graph"], c["graph"].n
+        n_splits = _layout.geometry(n)[2]
+        ntiles, per_split, last = lref.split_geometry(n, j_tile, n_splits)
+        assert ntiles == math.ceil(n / j_tile) and math.ceil(ntiles / n_splits) >= 2, name
+        assert ntiles % per_split != 0 and last == ntiles % per_split and (n_splits - 1) * per_split + last == ntiles, name
+        most_blocks = max(most_blocks, math.ceil(n / lref.NODE_BLOCK))
+        # the graph: simple, every node on the ring, masses that differ, the arrays the device gets name the same pairs
+        assert name == "ring_%d" % n and c["pos0"].shape == (n, 2) and len(c["ptr"]) == n + 1
+        assert g.mass.min() >= 3 and len(np.unique(g.mass)) > 4 and len(g.src) == 2 * len(c["nbr"]) == 2 * c["ptr"][-1]
+        rows = lref.sample_rows(n, i_block, j_tile, c["seed"])
+        assert rows[0] == 0 and rows[-1] == n - 1 and (np.diff(rows) > 0).all() and len(rows) < 1200
+        assert set(range((ntiles - 1) * j_tile, n)) <= set(rows.tolist()) and {i_block - 1, i_block, j_tile - 1, j_tile} <= set(rows.tolist())
+    assert most_blocks > lref.NODE_BLOCK
+    n16 = large["ring_%d" % (64 * j_tile + 1)]["graph"].n     # the smaller case: the last split is one tile of one node
+    assert lref.split_geometry(n16, j_tile, _layout.geometry(n16)[2])[2] == 1 and n16 % j_tile == 1
+
+
+def test_vectorised_graph_and_sampled_repulsion_equal_the_plain_ones():
+    """the large cases' graph builder against Graph's Python loop, and repulsion_rows on a sample, in chunks, against the
+    rows of the whole restatement"""
+    ptr, nbr, w, g = lref.ring_chords(300, 5)
+    plain = lref.Graph(ptr, nbr, w)
+    for k in ("mass", "src", "dst", "w"):
+        assert np.array_equal(getattr(g, k), getattr(plain, k)), k
+    assert g.n == plain.n == 300
+    s = lref.start_state(np.random.default_rng(6).random((300, 2)))
+    o = lref.step(plain, s, scaling_ratio=2.5)
+    rows = lref.sample_rows(300, 128, 32, 7, n_random=20)
+    rep, rep_abs = lref.repulsion_rows(g, s["x"], s["y"], rows, 2.5, chunk=7)
+    assert np.array_equal(rep, o["rep"][rows]) and np.array_equal(rep_abs, o["rep_abs"][rows])
+    speed, eff, m_half, m_jt, _ = lref.speed_step(300, o["S"], o["T"], s["speed"], s["eff"], 1.0)
+    assert (speed, eff, m_half, m_jt) == (o["speed"], o["eff"], o["m_half"], o["m_jt"])
+
+
 GOOD = dict(ptr=[0, 1, 2, 2], nbr=[1, 0], w=[0.5, 0.25], pos0=[[0.0, 0.0], [1.0, 0.0], [0.0, 1.0]], niter=2)
 
 

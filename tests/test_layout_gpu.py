@@ -13,6 +13,10 @@ iteration, the restatement runs one iteration from the downloaded state, and the
               S/(jt T) at least 1e-3 away from their thresholds (tests/test_layout_cpu.py asserts it on the CPU);
   x, y, speed within 4 x the largest deviation measured once on the MI355X, |x_gpu - x_ref| / max(1, the node's step
               length) over all cases (tests/golden/layout.npz, written by tools/gen_golden_layout.py), and never above 1e-3.
+
+Two large graphs (tests/_layout_ref.large_cases; test_large_graphs_one_iteration_at_a_time states their bounds) reach what
+only more than 64 tiles or more than 256 node blocks reach: several tiles in a split, a shorter last split, a second pass
+over the block sums.  There the repulsion is checked on a sample of rows and everything else from the device's own forces.
 """
 import numpy as np
 import pytest
@@ -86,6 +90,87 @@ def test_one_iteration_at_a_time(gpu_lib, golden, name):
     assert 0.0 < bound <= POS_BOUND_MAX, "the measured deviation would need a bound above 1e-3: the kernel is wrong, not the tolerance"
     dev = step_case(CASES[name])
     assert dev <= bound, (dev, bound)
+
+
+LARGE = lref.large_cases(J_TILE)
+SPEED_ULPS = 10
+POS_ULPS = 12
+
+
+@pytest.mark.parametrize("name", list(LARGE))
+def test_large_graphs_one_iteration_at_a_time(gpu_lib, name):
+    """More than 64 tiles, so that a split holds several tiles and the last split fewer (the tile loop of the repulsion
+    kernel comes round again, with its prefetch, its barrier and the float64 sum over tiles), and at the larger size more
+    than 256 block sums (the speed kernel's strided loop comes round again); tests/test_layout_cpu.py asserts that the
+    geometry makes it so.  LARGE_STEPS iterations from a seeded uniform start, one at a time.  The whole float64
+    restatement is O(n^2), so:
+
+      repulsion   a sample of rows (tests/_layout_ref.sample_rows), each against every j.  Componentwise
+                  |F_gpu - F_ref| <= (j_tile + 16) 2^-24 sum_j |term_ij|: the header sums float32 within a tile only, so
+                  8 roundings of 2^-23 per term and j_tile float32 additions of 2^-24 each; across tiles and splits the
+                  sum is float64.  (The small cases' (n + 16) 2^-24 would be 3.9e-3 at n = 65537, the size of one tile
+                  missed among 257.)
+      gravity, attraction   every row, 64 n 2^-53 of the sums of the absolute terms, as for the small cases.
+      dx, dy      (rep + grav) + attr of the downloaded parts, bit for bit.
+      S, T        float64 sums over the device's own forces and the previous dx, dy: 64 n 2^-53.  S == 2 T in the first
+                  iteration.
+      eff         equal to step 6 restated from the device's S and T, which keep MARGIN from both thresholds.
+      speed       within SPEED_ULPS = 10 ulp (2^-52) of max(old speed, |target|, new speed), step 6 restated from the
+                  device's S and T: sqrt(n), * 0.05, then sqrt(est) or est * T / (n n), * jitter_tolerance, * eff, * T,
+                  / S, - speed, + speed are at most 10 operations that round, each once on either side.
+      x, y        within POS_ULPS = 12 ulp of max(|x|, |move|, |new x|), step 7 restated from the device's speed, dx, dy
+                  and the swing of its dx, dy: the sum of two squares (2), sqrt, * mass, * speed, sqrt, 1 +, speed /,
+                  dx *, x + are 10 operations that round once on either side (a fused multiply-add drops a rounding),
+                  and 2 more for a sqrt within 1 ulp."""
+    c = LARGE[name]
+    g, n, p = c["graph"], c["graph"].n, dict(lref.DEFAULTS, **c["params"])
+    ntiles, per_split, last = lref.split_geometry(n, J_TILE, _layout.geometry(n)[2])
+    assert per_split >= 2 and 0 < last < per_split, "the case was meant to put several tiles in a split and fewer in the last"
+    rows = lref.sample_rows(n, I_BLOCK, J_TILE, c["seed"])
+    f32_tol, f64_tol, ulp = (J_TILE + 16) * 2.0 ** -24, 64 * n * 2.0 ** -53, 2.0 ** -52
+    worst = dict(rep=0.0, grav=0.0, attr=0.0, st=0.0, speed=0.0, pos=0.0)
+
+    def rel(err, scale):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return float(np.max(np.where(err == 0, 0.0, err / scale)))
+
+    with _layout.Layout(c["ptr"], c["nbr"], c["w"], **c["params"]) as L:
+        L.set_state(c["pos0"][:, 0], c["pos0"][:, 1])
+        for it in range(lref.LARGE_STEPS):
+            s = L.get_state()
+            assert L.run(1) == 1
+            f, a = L.last_forces(), L.get_state()
+            rep, rep_abs = lref.repulsion_rows(g, s["x"], s["y"], rows, float(p["scaling_ratio"]), chunk=64)
+            grav, attr, attr_abs = lref.local_forces(g, s["x"], s["y"], **p)
+            worst["rep"] = max(worst["rep"], rel(np.abs(f["repulsion"][rows] - rep), rep_abs) / f32_tol)
+            worst["grav"] = max(worst["grav"], rel(np.abs(f["gravity"] - grav), np.abs(grav)) / f64_tol)
+            worst["attr"] = max(worst["attr"], rel(np.abs(f["attraction"] - attr), attr_abs) / f64_tol)
+            d = (f["repulsion"] + f["gravity"]) + f["attraction"]
+            assert np.array_equal(a["dx"], d[:, 0]) and np.array_equal(a["dy"], d[:, 1]), it
+            old = np.stack([s["dx"], s["dy"]], axis=1)
+            swing = g.mass * np.sqrt(((old - d) ** 2).sum(axis=1))
+            S, T = float(swing.sum()), float((0.5 * g.mass * np.sqrt(((old + d) ** 2).sum(axis=1))).sum())
+            worst["st"] = max(worst["st"], abs(f["S"] - S) / S / f64_tol, abs(f["T"] - T) / T / f64_tol)
+            # step 6 from the device's S and T
+            speed, eff, m_half, m_jt, target = lref.speed_step(n, f["S"], f["T"], s["speed"], s["eff"], p["jitter_tolerance"])
+            if it == 0:
+                assert f["S"] == 2.0 * f["T"], "the first iteration must sit exactly on the tie"
+            else:
+                assert m_half >= lref.MARGIN, (it, m_half)
+            assert m_jt >= lref.MARGIN, (it, m_jt)
+            assert a["eff"] == eff, (it, a["eff"], eff, m_half, m_jt)
+            worst["speed"] = max(worst["speed"], abs(a["speed"] - speed) / (ulp * max(s["speed"], abs(target), speed)) / SPEED_ULPS)
+            # step 7 from the device's speed, forces and their swing
+            fac = a["speed"] / (1.0 + np.sqrt(a["speed"] * swing))
+            for k, (new, was) in enumerate(((a["x"], s["x"]), (a["y"], s["y"]))):
+                move = d[:, k] * fac
+                scale = np.maximum(np.maximum(np.abs(was), np.abs(move)), np.abs(was + move))
+                worst["pos"] = max(worst["pos"], rel(np.abs(new - (was + move)), scale) / ulp / POS_ULPS)
+            assert np.isfinite(a["x"]).all() and np.isfinite(a["y"]).all()
+    print("n=%d, %d tiles, %d per split, %d in the last, %d rows sampled: error / bound: repulsion %.3g, gravity %.3g, attraction %.3g, "
+          "S and T %.3g, speed %.3g, positions %.3g" % (n, ntiles, per_split, last, len(rows), worst["rep"], worst["grav"], worst["attr"],
+                                                        worst["st"], worst["speed"], worst["pos"]))
+    assert max(worst.values()) <= 1.0, worst
 
 
 def test_stops_when_the_forces_vanish(gpu_lib):

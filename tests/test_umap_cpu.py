@@ -55,17 +55,12 @@ def test_header_is_plain_c_and_links(tmp_path):
     assert r.returncode == 0 and "%d entry points" % len(_lib.UMAP_SYMBOLS) in r.stdout, r.stdout
 
 
-@pytest.mark.parametrize("n_epochs", N_EPOCHS)
-@pytest.mark.parametrize("name", list(CASES))
-def test_restated_graph_keeps_its_invariants(gold, name, n_epochs):
-    idx, dist = CASES[name]
+def graph_invariants(idx, dist, n_epochs):
+    """the restated graph of one list case, after the assertions every case must pass"""
     n, k = idx.shape
     g = ur.fuzzy_graph(idx, dist, n_epochs)
     # the cases are chosen so that nothing sits on a threshold: the GPU test may then demand equality
     assert not g["flagged"].any() and not g["near"].any()
-    at = gold["graph_names"].tolist().index("%s/%d" % (name, n_epochs))
-    assert int(gold["graph_n_arcs"][at]) == len(g["w"]) and int(gold["graph_flagged"][at]) == 0
-    assert abs(float(gold["graph_w_sum"][at]) - g["w"].sum()) <= 1e-12 * g["w"].sum()
     # w is symmetric bit for bit, rows ascend, no self arc, everything within (0, 1]
     w = {(int(s), int(d)): x for s, d, x in zip(np.repeat(np.arange(n), np.diff(g["ptr"])), g["nbr"], g["w"])}
     assert len(w) == len(g["w"]) and all(w[(j, i)] == x and i != j for (i, j), x in w.items())
@@ -81,7 +76,38 @@ def test_restated_graph_keeps_its_invariants(gold, name, n_epochs):
         assert g["rho"][i] == (pos.min() if len(pos) else 0.0)
     if n_epochs == ur.N_EPOCHS_KEEPING:
         assert len(g["w"]) == g["n_unpruned"]
-    elif name not in ("knn_50x2", "floor_40x5"):           # (their weights all lie above wmax / 8)
+    return g
+
+
+@pytest.mark.parametrize("n_epochs", N_EPOCHS)
+@pytest.mark.parametrize("name", list(ur.width_cases()))
+def test_width_cases_keep_the_invariants_and_reach_every_width(name, n_epochs):
+    """the lists that fill a width of the graph kernels or sit one above it: no row on a threshold (another seed is chosen,
+    never a row excused), and between them every width, full and one over"""
+    cases = ur.width_cases()
+    idx, dist = cases[name]
+    n, k = idx.shape
+    g = graph_invariants(idx, dist, n_epochs)
+    assert 200 <= n <= 300 and name == "knn_%dx%d" % (n, k) and not g["floored"].any()
+    if n_epochs == ur.N_EPOCHS_PRUNING:
+        assert len(g["w"]) < g["n_unpruned"], "n_epochs = %d was meant to prune" % n_epochs
+    ks = sorted(c[0].shape[1] for c in cases.values())
+    assert ks == [8, 9, 16, 17, 30, 32, 33] == sorted(ur.WIDTH_K)
+    assert [ur.width_of(k) for k in ks] == [8, 16, 16, 32, 32, 32, 64]
+    hip = open(os.path.join(REPO, "nabo_amd", "csrc", "umap.hip")).read()
+    assert "return k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64;" in hip      # width_of restates umap_width
+
+
+@pytest.mark.parametrize("n_epochs", N_EPOCHS)
+@pytest.mark.parametrize("name", list(CASES))
+def test_restated_graph_keeps_its_invariants(gold, name, n_epochs):
+    idx, dist = CASES[name]
+    n, k = idx.shape
+    g = graph_invariants(idx, dist, n_epochs)
+    at = gold["graph_names"].tolist().index("%s/%d" % (name, n_epochs))
+    assert int(gold["graph_n_arcs"][at]) == len(g["w"]) and int(gold["graph_flagged"][at]) == 0
+    assert abs(float(gold["graph_w_sum"][at]) - g["w"].sum()) <= 1e-12 * g["w"].sum()
+    if n_epochs != ur.N_EPOCHS_KEEPING and name not in ("knn_50x2", "floor_40x5"):   # (their weights all lie above wmax / 8)
         assert len(g["w"]) < g["n_unpruned"], "n_epochs = %d was meant to prune" % n_epochs
     if name == "duplicates_60x5":
         assert (dist[:, 1] == 0).any() and (g["rho"] == 0).sum() == 5 and g["floored"][g["rho"] == 0].all()

@@ -26,7 +26,7 @@ import _umap_ref as ur
 pytestmark = pytest.mark.gpu
 
 GROUP = _umap.geometry()
-CASES = ur.graph_cases()
+CASES = dict(ur.graph_cases(), **ur.width_cases())          # (width_cases: every width of the graph kernels, full and one over)
 AB = (1.5769436135065888, 0.8950607193577038)      # spread 1, min_dist 0.1; any positive pair would do here
 
 
@@ -96,7 +96,8 @@ def _check_epoch(U, ep, y, tag):
 # for a start in which the clip acts on most terms.
 EPOCH_CASES = [("knn_333x15", 2, 5, "plain"), ("knn_333x15", 3, 1, "plain"), ("hub_600x4", 2, 5, "plain"), ("hub_600x4", 3, 5, "far"),
                ("knn_333x15", 2, 1, "coincident"), ("knn_333x15", 3, 5, "far"), ("knn_120x56", 3, 5, "coincident"),
-               ("hub_600x4", 2, 5, "crowded"), ("knn_333x15", 3, 5, "crowded")]
+               ("hub_600x4", 2, 5, "crowded"), ("knn_333x15", 3, 5, "crowded"),
+               ("knn_250x32", 2, 5, "plain"), ("knn_250x32", 3, 5, "crowded")]      # rows of 32 arcs and more: two full rounds of the group
 
 
 @pytest.mark.parametrize("name,dims,nsr,start", EPOCH_CASES)

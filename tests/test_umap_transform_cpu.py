@@ -68,7 +68,11 @@ def test_no_list_case_sits_on_a_threshold(golden, name):
     assert not g["flagged"].any()
     assert int(golden("umap_transform")["list_flagged"]) == 0
     m, k = c["idx"].shape
-    assert k in (2, 5, 15, 17, 56) and m in (1, 17, 333)
+    assert k in (2, 5, 15, 17, 56) + tr.GROUP_K and m in (1, 17, 333)
+    if name == "k%d_m17" % k and k in tr.GROUP_K:
+        # the width of the graph kernel and the arcs a lane of the run kernel holds, as the launchers choose them
+        width, arcs = (8 if k <= 8 else 16 if k <= 16 else 32 if k <= 32 else 64), -(-k // _umap.transform_geometry())
+        assert (k, width, arcs) in ((8, 8, 1), (9, 16, 1), (16, 16, 1), (32, 32, 2), (33, 64, 3), (48, 64, 3)) and len(c["Y"]) == 200
     # the search met its target wherever the floor did not act and the row is not all zeros
     ok = np.abs(g["psum_at"] - math.log2(k)) < 1e-5
     assert ok[~g["floored"] & (c["dist"][:, -1] > 0) & (k > 2)].all()
@@ -83,6 +87,8 @@ def test_no_list_case_sits_on_a_threshold(golden, name):
         assert (c["dist"][5, :2] == 0).all() and c["dist"][5, 2] > 0
     if name == "ties_k5_m17":
         assert c["dist"][9, 1] == c["dist"][9, 2] == c["dist"][9, 3]
+    if name == "k48_m17":
+        assert c["dist"][4, 0] == 0 and c["idx"][4, 0] == 9 and g["memb"][4, 0] == 1 and c["dist"][4, 1] > 0
 
 
 def scalar_graph(idx, dist, Y):

@@ -62,6 +62,8 @@ def test_graph_from_given_lists(gpu_lib, graphs, name):
         assert (memb[2] == 1).all() and memb[5, 0] == 1 and memb[5, 1] == 1
     if name == "k15_m333":
         assert memb[3, 0] == 1
+    if name == "k48_m17":
+        assert memb[4, 0] == 1
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -87,9 +89,12 @@ def _check_epoch(T, ep, y, tag):
 
 
 # The clip acts where cells are CLOSE, on the repulsion; a start spread FAR apart clips nothing but feeds pow large
-# arguments.  k56_m17 puts four arcs on a lane, k17_m17 two, k2_m17 leaves most lanes without one.
+# arguments.  k56_m17 puts four arcs on a lane, k17_m17 two, k2_m17 leaves most lanes without one; k33_m17 and
+# k48_m17 put three (the third round one lane wide, and full); k16_m17 and k32_m17 fill one round and two.
 EPOCH_CASES = [("k15_m333", 2, 5, "plain"), ("k15_m333", 3, 1, "plain"), ("k56_m17", 3, 5, "neighbour"), ("k17_m17", 2, 1, "neighbour"),
-               ("k15_m333", 3, 5, "far"), ("k2_m17", 2, 5, "far"), ("k15_m333", 2, 5, "crowded"), ("k56_m17", 2, 1, "crowded")]
+               ("k15_m333", 3, 5, "far"), ("k2_m17", 2, 5, "far"), ("k15_m333", 2, 5, "crowded"), ("k56_m17", 2, 1, "crowded"),
+               ("k33_m17", 2, 5, "plain"), ("k33_m17", 3, 1, "crowded"), ("k48_m17", 3, 5, "neighbour"), ("k16_m17", 2, 5, "far"),
+               ("k32_m17", 3, 5, "plain")]
 
 
 @pytest.mark.parametrize("name,dims,nsr,start", EPOCH_CASES)
@@ -140,6 +145,8 @@ def test_one_epoch_at_a_time(gpu_lib, graphs, name, dims, nsr, start):
         assert zero_d2 > 0
     if name == "k56_m17":
         assert not ep.live.all(), "some arc was meant to lie below 1 / n_epochs"
+    if name in ("k33_m17", "k48_m17"):                         # umap_transform_run_launch: three arcs to a lane
+        assert -(-idx.shape[1] // GROUP) == 3
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -183,7 +190,7 @@ def test_runs_split_and_repeat_to_the_same_bits(gpu_lib, name):
         assert T.get_positions().tobytes() != whole.tobytes()
 
 
-@pytest.mark.parametrize("name,rows", [("k15_m333", 60), ("k56_m17", 17)])
+@pytest.mark.parametrize("name,rows", [("k15_m333", 60), ("k56_m17", 17), ("k48_m17", 17)])
 def test_batches_give_the_bits_of_the_whole(gpu_lib, name, rows):
     c = CASES[name]
     idx, dist = c["idx"], c["dist"]
