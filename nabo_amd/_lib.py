@@ -85,6 +85,12 @@ POTENTIAL_SYMBOLS = ["nabo_potential_create", "nabo_potential_destroy", "nabo_po
                      "nabo_potential_set_state", "nabo_potential_finish", "nabo_potential_solve", "nabo_potential_info",
                      "nabo_potential_last_ms", "nabo_potential_geometry"]
 
+# every symbol include/nabo_bundle.h declares (edge bundling: density-guided advection of the laid-out graph's edges)
+BUNDLE_SYMBOLS = ["nabo_bundle_create", "nabo_bundle_destroy", "nabo_bundle_set_params", "nabo_bundle_set_option",
+                  "nabo_bundle_get_points", "nabo_bundle_set_points", "nabo_bundle_resample", "nabo_bundle_density",
+                  "nabo_bundle_field", "nabo_bundle_advect", "nabo_bundle_smooth", "nabo_bundle_run", "nabo_bundle_result",
+                  "nabo_bundle_last_ms", "nabo_bundle_geometry", "nabo_bundle_blur_weights"]
+
 # what include/nabo_knn_inspect.h declares (a look into an index, for tests and tools)
 INSPECT_SYMBOLS = ["nabo_index_stream_order"]
 
@@ -244,10 +250,26 @@ def lib():
     L.nabo_potential_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(i64)]
     L.nabo_potential_last_ms.argtypes = [vp, C.POINTER(dbl)]
     L.nabo_potential_geometry.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.nabo_bundle_create.argtypes = [C.POINTER(vp), i32, i64, vp, vp, i64, vp, vp]
+    L.nabo_bundle_destroy.argtypes = [vp]
+    L.nabo_bundle_set_params.argtypes = [vp, dbl, dbl, i32, i32, i32, i32, dbl, dbl, dbl, i32, i64]
+    L.nabo_bundle_set_option.argtypes = [vp, C.c_char_p, i64]
+    L.nabo_bundle_get_points.argtypes = [vp, C.POINTER(i64), vp, vp]
+    L.nabo_bundle_set_points.argtypes = [vp, vp, vp]
+    L.nabo_bundle_resample.argtypes = [vp]
+    L.nabo_bundle_density.argtypes = [vp, vp]
+    L.nabo_bundle_field.argtypes = [vp, dbl, vp, vp, vp]
+    L.nabo_bundle_advect.argtypes = [vp, i64]
+    L.nabo_bundle_smooth.argtypes = [vp, i64]
+    L.nabo_bundle_run.argtypes = [vp]
+    L.nabo_bundle_result.argtypes = [vp, vp, vp]
+    L.nabo_bundle_last_ms.argtypes = [vp, C.POINTER(dbl)]
+    L.nabo_bundle_geometry.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.nabo_bundle_blur_weights.argtypes = [dbl, C.POINTER(i32), vp, i64]
     for name in (SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS + UMAP_SYMBOLS
-                 + UMAP_TRANSFORM_SYMBOLS + COMMUNITY_SYMBOLS + AGGLOM_SYMBOLS + POTENTIAL_SYMBOLS + INSPECT_SYMBOLS):
+                 + UMAP_TRANSFORM_SYMBOLS + COMMUNITY_SYMBOLS + AGGLOM_SYMBOLS + POTENTIAL_SYMBOLS + BUNDLE_SYMBOLS + INSPECT_SYMBOLS):
         if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy", "nabo_umap_destroy", "nabo_umap_transform_destroy", "nabo_community_destroy",
-                        "nabo_potential_destroy"):
+                        "nabo_potential_destroy", "nabo_bundle_destroy"):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L

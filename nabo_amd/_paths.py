@@ -325,6 +325,17 @@ class RefGraph:
         self.layout = _set_ref_layout(self.fn, self.ref_name, niter, init_pos, seed, disable_rescaling, verbose, self.device, params)
         return self.layout
 
+    def bundle_edges(self, layout=None, edge_min_weight=0, bundle_bw=0.1, bundle_decay=0.7, **params):
+        """The bundled edges of the reference graph as `GraphPlot(draw_edges='ref', bundle_edges=True)` draws them:
+        (points, offsets), as nabo_amd.bundle_edges, which this calls on the object's file and device.  `layout`: as
+        there; None takes `self.layout`, which `set_ref_layout` keeps."""
+        from ._bundle import bundle_edges
+        if layout is None:
+            layout = self.layout
+        if layout is None:
+            raise ValueError("ERROR: no layout: call set_ref_layout first or give one")
+        return bundle_edges(self.fn, self.ref_name, layout, edge_min_weight, bundle_bw, bundle_decay, self.device, **params)
+
     def make_leiden_clusters(self, resolution=1.0, random_seed=4466):
         """Graph.make_leiden_clusters (nabo/_graph.py:266-292): {reference node: str(cluster)}, as
         nabo_amd.make_leiden_clusters, which this calls on the object's file and device (the weighted graph is read again
