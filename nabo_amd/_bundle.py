@@ -4,8 +4,9 @@ their own density.
 Array / HDF5 restatement of the bundling of `GraphPlot(..., bundle_edges=True)` (nabo/_graphplot.py:192-220), which hands
 positions and edges to `datashader.bundling.hammer_bundle`.  include/nabo_bundle.h holds the definition and says where it
 departs from datashader, whose own floating-point results are not pinned; nabo_amd/csrc/bundle.hip runs
-it.  Only the reference graph is drawn: target nodes have no position in a reference layout.  Drawing itself stays with
-matplotlib: `ax.plot(points[:, 0], points[:, 1])` for the polylines, `imshow(Bundle.density())` for graphs too large for that.
+it.  Only the reference graph is drawn: target nodes have no position in a reference layout.  Drawing: `ax.plot(points[:, 0], points[:, 1])`
+for the polylines of a small graph; for graphs too large for that, `Canvas.add_bundle` (nabo_amd/_render.py) rasterises a
+resident bundle's polylines on the device.
 """
 import ctypes as C
 import json
@@ -89,8 +90,8 @@ def _check_graph(pos, src, dst):
 
 class Bundle(Handle):
     """Nodes, edges and the edges' polylines resident on one device (nabo_bundle_create): the handle the tests and
-    tools/bench_bundle.py step through; `hammer_bundle` is the one-call form.  `density()` is also the way to show a graph
-    of millions of edges: the count image of the (bundled) edges, for `imshow`."""
+    tools/bench_bundle.py step through; `hammer_bundle` is the one-call form.  To show a graph of millions of edges, hand the
+    handle to `Canvas.add_bundle`, which draws the polylines as lines; `density()` counts their sample points only."""
     _destroy = "nabo_bundle_destroy"
 
     def __init__(self, pos, src, dst, device=0, **params):

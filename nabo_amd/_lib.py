@@ -91,6 +91,12 @@ BUNDLE_SYMBOLS = ["nabo_bundle_create", "nabo_bundle_destroy", "nabo_bundle_set_
                   "nabo_bundle_field", "nabo_bundle_advect", "nabo_bundle_smooth", "nabo_bundle_run", "nabo_bundle_result",
                   "nabo_bundle_last_ms", "nabo_bundle_geometry", "nabo_bundle_blur_weights"]
 
+# every symbol include/nabo_render.h declares (the rasteriser: nodes and edges to integer images and an RGBA picture)
+RENDER_SYMBOLS = ["nabo_render_create", "nabo_render_destroy", "nabo_render_clear", "nabo_render_set_option",
+                  "nabo_render_add_polylines", "nabo_render_add_edges", "nabo_render_add_bundle", "nabo_render_add_nodes",
+                  "nabo_render_edge_counts", "nabo_render_node_counts", "nabo_render_node_sums", "nabo_render_compose",
+                  "nabo_render_last_ms", "nabo_render_alpha_lut", "nabo_render_geometry"]
+
 # what include/nabo_knn_inspect.h declares (a look into an index, for tests and tools)
 INSPECT_SYMBOLS = ["nabo_index_stream_order"]
 
@@ -266,10 +272,26 @@ def lib():
     L.nabo_bundle_last_ms.argtypes = [vp, C.POINTER(dbl)]
     L.nabo_bundle_geometry.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.nabo_bundle_blur_weights.argtypes = [dbl, C.POINTER(i32), vp, i64]
+    L.nabo_render_create.argtypes = [C.POINTER(vp), i32, i32, i32, dbl, dbl, dbl, dbl]
+    L.nabo_render_destroy.argtypes = [vp]
+    L.nabo_render_clear.argtypes = [vp]
+    L.nabo_render_set_option.argtypes = [vp, C.c_char_p, i64]
+    L.nabo_render_add_polylines.argtypes = [vp, i64, vp, vp]
+    L.nabo_render_add_edges.argtypes = [vp, i64, vp, vp, i64, vp, vp]
+    L.nabo_render_add_bundle.argtypes = [vp, vp]
+    L.nabo_render_add_nodes.argtypes = [vp, i64, vp, vp, vp, vp]
+    L.nabo_render_edge_counts.argtypes = [vp, vp]
+    L.nabo_render_node_counts.argtypes = [vp, vp]
+    L.nabo_render_node_sums.argtypes = [vp, vp]
+    L.nabo_render_compose.argtypes = [vp, vp, vp, i32, vp, i32, vp]
+    L.nabo_render_last_ms.argtypes = [vp, C.POINTER(dbl)]
+    L.nabo_render_alpha_lut.argtypes = [dbl, i32, vp]
+    L.nabo_render_geometry.argtypes = [C.POINTER(i32)] * 6
     for name in (SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS + UMAP_SYMBOLS
-                 + UMAP_TRANSFORM_SYMBOLS + COMMUNITY_SYMBOLS + AGGLOM_SYMBOLS + POTENTIAL_SYMBOLS + BUNDLE_SYMBOLS + INSPECT_SYMBOLS):
+                 + UMAP_TRANSFORM_SYMBOLS + COMMUNITY_SYMBOLS + AGGLOM_SYMBOLS + POTENTIAL_SYMBOLS + BUNDLE_SYMBOLS + RENDER_SYMBOLS
+                 + INSPECT_SYMBOLS):
         if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy", "nabo_umap_destroy", "nabo_umap_transform_destroy", "nabo_community_destroy",
-                        "nabo_potential_destroy", "nabo_bundle_destroy"):
+                        "nabo_potential_destroy", "nabo_bundle_destroy", "nabo_render_destroy"):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L

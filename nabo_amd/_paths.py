@@ -336,6 +336,20 @@ class RefGraph:
             raise ValueError("ERROR: no layout: call set_ref_layout first or give one")
         return bundle_edges(self.fn, self.ref_name, layout, edge_min_weight, bundle_bw, bundle_decay, self.device, **params)
 
+    def render(self, layout=None, clusters=None, **kwargs):
+        """The picture of the reference graph `GraphPlot` draws, rasterised on the device: (image uint8 [H, W, 4], extent),
+        as nabo_amd.plot_graph, which this calls on the object's file and device with GraphPlot's arguments in `kwargs`.
+        `layout`: as there; None takes `self.layout`, which `set_ref_layout` keeps.  `clusters`: None takes
+        `self.clusters` if `make_leiden_clusters` has set it; pass {} to colour by `vc` alone."""
+        from ._render import plot_graph
+        if layout is None:
+            layout = self.layout
+        if layout is None:
+            raise ValueError("ERROR: no layout: call set_ref_layout first or give one")
+        if clusters is None:
+            clusters = getattr(self, "clusters", None)
+        return plot_graph(self.fn, self.ref_name, layout, clusters or None, device=self.device, **kwargs)
+
     def make_leiden_clusters(self, resolution=1.0, random_seed=4466):
         """Graph.make_leiden_clusters (nabo/_graph.py:266-292): {reference node: str(cluster)}, as
         nabo_amd.make_leiden_clusters, which this calls on the object's file and device (the weighted graph is read again

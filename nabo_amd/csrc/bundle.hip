@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/nabo_bundle.h"
+#include "bundle_view.h"
 #include "host_common.h"
 
 #pragma clang fp contract(off)
@@ -547,6 +548,12 @@ int bundle_enter(nabo_bundle *B)
 }
 
 }  // namespace
+
+nabo::BundleView nabo::bundle_view(const nabo_bundle *B)
+{
+    return {B->device, B->E, B->npts, B->off[B->cur].as<int64_t>(), B->pts[B->cur].as<double>(),
+            {B->lo[0], B->lo[1]}, {B->span[0], B->span[1]}};
+}
 
 extern "C" {
 
