@@ -140,7 +140,7 @@ static int query_top(nabo_index *ix, const double *X, int32_t x_on_device, int64
     if (!ix) return api_fail(NABO_E_INVALID, "NULL argument");
     PassCtx top;
     top.coarse_weak = ix->ref.l2.coarse_weak;
-    top.tl_no = ix->ref.l2.tl_verdict == 2;
+    top.tl_no = !ix->ref.l2.stream_verdict.streams();
     PassResult res;
     return query_impl(ix, top, X, x_on_device, m, k, drop_first, out_idx, out_dist, out_on_device, cand_mode, out_bound, &res);
 }
@@ -220,14 +220,15 @@ int nabo_index_stream_order(nabo_index *ix, uint32_t *row_map, int64_t *n_row_po
     if (!ix || !n_row_pos || !n_ref_pos) return api_fail(NABO_E_INVALID, "NULL argument");
     int rc;
     if ((rc = index_idle(ix)) || (rc = use_device(ix->device))) return rc;
-    const auto &l2 = ix->ref.l2;
-    if (!ix->last.tl_ran || !l2.ord_built || ix->last.tl_row_pos <= 0)
+    const auto &refs = ix->ref.l2.buckets;
+    const auto &rows = ix->ws.buckets.rows;
+    if (!rows.streamed || !refs.ordered_built || rows.positions <= 0)
         return api_fail(NABO_E_INVALID, "the last query on this index did not take the two-level stream");
-    *n_row_pos = ix->last.tl_row_pos;
-    *n_ref_pos = l2.ord_tiles * 32;
+    *n_row_pos = rows.positions;
+    *n_ref_pos = refs.ordered_tiles * 32;
     if (!row_map || !ref_map) return NABO_OK;
-    HIP_TRY(hipMemcpyAsync(row_map, ix->ws.lmap.p, (size_t)*n_row_pos * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
-    HIP_TRY(hipMemcpyAsync(ref_map, l2.yordmap.p, (size_t)*n_ref_pos * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipMemcpyAsync(row_map, rows.map.p, (size_t)*n_row_pos * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipMemcpyAsync(ref_map, refs.ordered_map.p, (size_t)*n_ref_pos * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
     HIP_TRY(hipStreamSynchronize(ix->stream));
     return NABO_OK;
 }

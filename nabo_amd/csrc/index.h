@@ -1,5 +1,6 @@
 // index.h -- the k-NN index behind the C ABI (include/nabo_knn.h) and what its host files share: plan.hip (launch plans
-// from shapes alone), set_ref.hip (the resident references), query.hip (the pass chain), api.hip (the entry points).
+// from shapes alone), set_ref.hip (the resident references), bucket_order.hip (cells sorted into bucket order), query.hip (the
+// pass chain), api.hip (the entry points).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,8 +9,10 @@
 #include <vector>
 
 #include "../../include/nabo_knn.h"
+#include "bucket_order.h"
 #include "host_common.h"
 #include "knn_common.h"
+#include "two_level_verdict.h"
 
 namespace nabo {
 
@@ -95,7 +98,7 @@ struct PassCtx {
     const std::vector<uint32_t> *row_map = nullptr;      // rows of this batch -> rows of the top-level query (null at the top)
     bool top = true;               // the top-level call: the per-row pass record starts over
     bool coarse_weak = false;      // nabo_index::Refs::L2::coarse_weak when the query started
-    bool tl_no = false;            // nabo_index::Refs::L2::tl_verdict was "no" when the query started: the caller-order stream
+    bool tl_no = false;            // nabo_index::Refs::L2::stream_verdict said no when the query started: the caller-order stream
     bool first() const { return pass_level == 0 && !wide_retry; }
 };
 
@@ -186,29 +189,11 @@ struct nabo_index {
             nabo::DevBuf centre, ypk, ycpk, ycpk1, normmax;
             bool packed_f32 = false, packed_c16 = false, packed_c1 = false;
             bool slots2 = false;             // the slot order ycpk1 was packed in (two_level_slots when it was packed)
-            // the two-level stream (ensure_local_seeds): ALL unmasked references in bucket order, ord_tiles tiles and two
-            // all-padding tiles behind them; yordmap [position] = reference index (0xFFFFFFFF: a padding cell).
-            // tl_verdict: whether this index's data takes the stream -- 0 not known (the next long query probes), 1 yes,
-            // 2 no (a probe said so, or the waves of a launch proper ran most of their tiles two-step): the queries stream
-            // the caller-order operands and the ordered copy is not built.  A HEURISTIC, and remembered across set_ref /
-            // set_mask -- the usual caller refreshes the same kind of data -- for TL_VERDICT_REPACKS repacks (tl_age)
-            // yordend [local_C] (int32): the buckets' ends in tiles of the copy (lseed_bucket_ends), the mode control's table.
-            nabo::DevBuf yord, yordmap, yordend;
-            int64_t ord_tiles = 0;
-            bool ord_built = false;
-            int tl_verdict = 0, tl_age = 0;
-            // local tournament seeds (local_seeds.hip): the buckets' runs live BEHIND the one-product operands in ycpk1, from
-            // tile ref_tiles_alloc on (local_room tiles: one address space for l2c_pre_kernel's tile ranges); anchors and the
-            // unmasked references per bucket; built by ensure_local_seeds for (local_C, local_cap), stale after every repack
-            nabo::DevBuf lanchors, lrefcnt;
-            int64_t local_room = 0;
-            int local_C = 0, local_cap = 0;
-            // the sub-order of the ordered copy (local_seeds.h): built for local_sub sub-anchors per bucket (1: none) ranked by
-            // rule local_sub_rank; their component slots [local_C][local_sub] as chunks, their norms and ranks -- the queries
-            // sort their rows with the same tables
-            nabo::DevBuf lsub, lsubnorm, lsubrank;
-            int local_sub = 1, local_sub_rank = 0;
-            bool local_built = false;
+            // the bucket order (bucket_order.h; ensure_local_seeds): anchors, the runs' room behind ycpk1, the ordered copy
+            // the two-level stream reads and its sub-order; and whether this index's DATA takes that stream at all --
+            // remembered across repacks, unlike everything else here (two_level_verdict.h)
+            nabo::BucketRefs buckets;
+            nabo::TwoLevelVerdict stream_verdict;
             double ymax_sqrt = 0.0, ymax_sqrt_c = 0.0;
             // the largest reference norm of the last pack, on its way to the host (ensure_packed / ymax_resolve): pinned word,
             // the event behind its copy, which of the two values it becomes and the scale it was packed with
@@ -238,13 +223,7 @@ struct nabo_index {
         nabo::DevBuf cand_key, cand_key2, cand_mi, cand_mt, cand_mi2, cand_mt2;   // filter keys of the lists; merged lists (merge_lists_kernel)
         nabo::DevBuf xbuf, xnbuf, xpk, xnorm, cand_idx, cand_tau, cand_idx2, cand_tau2, cand_d, fails, failcnt, oidx, odist, nfound;
         nabo::DevBuf xh, cbrow;                   // modified Canberra: 7-bit target operands; target row numbers of the bitmap pass
-        // local tournament seeds: the counting sort's keys, block counts, bucket totals and layout (shared by the reference
-        // build and the queries: one stream); the bucket-ordered target tiles, their row map and the columns' ranges
-        nabo::DevBuf lkey, lblk, ltot, llay, xpre, lmap, lranges;
-        // the sub-order: the bucket-ordered copy before it and its map, the second sort's keys, block counts, class totals
-        // and first positions, the sub-anchors as floats (scratch of the ranking)
-        nabo::DevBuf lsubpk, lsubmap, lkey2, lblk2, ltot2, lsublay, lsubf;
-        nabo::DevBuf tlstats;                     // the two-level launch's tile counters [3] (l2c_topk.hip)
+        nabo::BucketScratch buckets;              // the sorts into bucket order, and what a launch's sort hands to its filter (bucket_order.h)
     } ws;
 
     // ---- the last query's record (the nabo_index_last_* getters) ----
@@ -257,8 +236,6 @@ struct nabo_index {
         double ms[5] = {0, 0, 0, 0, 0};
         int64_t counters[4] = {0, 0, 0, 0};
         char kernel[256] = "";          // dominant kernel of the last query (nabo_index_last_kernel)
-        bool tl_ran = false;
-        int64_t tl_row_pos = 0;         // positions of the bucket-ordered target copy the two-level launch read (nabo_index_stream_order)
     } last;
 
     // nabo_index_query_async: the query runs on a host thread of its own (it synchronises its stream between its passes);
@@ -271,7 +248,6 @@ struct nabo_index {
 
 namespace nabo {
 
-constexpr int TL_VERDICT_REPACKS = 16;       // repacks of the references a two-level verdict outlives (nabo_index::Refs::L2::tl_verdict)
 constexpr int RERUN_WIDE = 2;     // nabo_index::Workspace::rerun: the set of the frame that sends rows to the 64-entry lists
 
 // api.hip: NABO_OK, or the refusal while an asynchronous query is in flight on the index
@@ -280,6 +256,7 @@ int index_idle(const nabo_index *ix);
 int ensure_packed(nabo_index *ix, int want);
 int ymax_resolve(nabo_index *ix);
 int ensure_local_seeds(nabo_index *ix);
+// bucket_order.hip: bucket_sort (bucket_order.h)
 // query.hip
 int query_impl(nabo_index *ix, const PassCtx &ctx, const double *X, int32_t x_on_device, int64_t m, int32_t k, int32_t drop_first,
                int64_t *out_idx, double *out_dist, int32_t out_on_device, bool cand_mode, double *out_bound, PassResult *res);

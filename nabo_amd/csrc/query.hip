@@ -102,8 +102,11 @@ struct L2Part {
     int64_t wgs(int rows_per_wg) const { return (rows + rows_per_wg - 1) / rows_per_wg; }     // of a plain launch (gx, or fewer: a main part cut on whole rounds of positions)
 };
 
-// LOCAL tournament seeds of a one-split launch (local_seeds.hip): the launch's rows sorted by bucket -- assignment on the
-// packed operands, counting sort, a bucket-ordered copy of their tiles for the tournament alone -- and ONE tournament launch
+// positions of the bucket-ordered copy of `rows` target rows: whole columns (local_seeds.h)
+static int64_t ordered_positions(const nabo_index *ix, int64_t rows) { return lseed_columns(rows, ix->ref.l2.buckets.buckets) * LSEED_COL_ROWS; }
+
+// LOCAL tournament seeds of a one-split launch (local_seeds.hip): the launch's rows sorted by bucket (bucket_sort: a
+// bucket-ordered copy of their tiles, for the tournament alone unless the launch streams it) and ONE tournament launch
 // whose columns each run over their bucket's references; rows of buckets too small for one keep the stream's first tiles
 // (pt, gt: l2c_pre_plan's; pt = 0: no tournament there, those rows start from +inf).  No host wait: counts, layout and
 // ranges stay on the device.  sub: the launch streams the copy (two-level) -- its rows are sorted once more inside their
@@ -112,53 +115,150 @@ static int local_seeds(nabo_index *ix, const Query &q, const L2Plan &P, L2Part &
 {
     const IndexShape &sh = ix->shape;
     auto &l2 = ix->ref.l2;
-    auto &ws = ix->ws;
+    auto &out = ix->ws.buckets.rows;
     hipStream_t st = ix->stream;
     int rc;
-    const int C = l2.local_C, cap = l2.local_cap, kc = P.kcq;
+    const int kc = P.kcq;
     const int64_t nrows = p.end(q.m) - p.row0;
-    const int64_t ncol = lseed_columns(nrows, C), prow = ncol * LSEED_COL_ROWS;
+    const int64_t prow = ordered_positions(ix, nrows), ncol = prow / LSEED_COL_ROWS;
     // (a two-level launch reads the copy in whole workgroups: positions up to prow_wg, the ones past prow padding)
     const int64_t prow_wg = (prow + P.rows_per_wg - 1) / P.rows_per_wg * P.rows_per_wg;
     const size_t tile_bytes = (size_t)kc * 1024;
-    if ((rc = p.pre->reserve((size_t)p.rows * sizeof(float))) || (rc = ws.lkey.reserve(lseed_key_bytes(nrows))) ||
-        (rc = ws.lblk.reserve(lseed_blockcnt_bytes(nrows, C))) || (rc = ws.ltot.reserve((size_t)C * sizeof(uint32_t))) ||
-        (rc = ws.llay.reserve(lseed_layout_bytes(C))) || (rc = ws.xpre.reserve((size_t)(prow_wg / 32) * tile_bytes)) ||
-        (rc = ws.lmap.reserve((size_t)prow_wg * sizeof(uint32_t))) || (rc = ws.lranges.reserve((size_t)ncol * 4 * sizeof(int))))
+    if ((rc = p.pre->reserve((size_t)p.rows * sizeof(float))) || (rc = out.ordered.reserve((size_t)(prow_wg / 32) * tile_bytes)) ||
+        (rc = out.map.reserve((size_t)prow_wg * sizeof(uint32_t))) || (rc = out.column_ranges.reserve((size_t)ncol * 4 * sizeof(int))))
         return rc;
-    const unsigned char *xh = ws.xpk.as<unsigned char>() + (size_t)(p.row0 / 32) * tile_bytes;
-    const int rest[4] = {0, (int)p.tps, pt, pt > 0 ? gt : 0};
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.pre->p), 0x7F800000, (size_t)p.rows, st));      // +inf: rows without a tournament
-    HIP_TRY(hipMemsetAsync(ws.lmap.p, 0xFF, (size_t)prow_wg * sizeof(uint32_t), st));
-    if (prow_wg > prow) HIP_TRY(hipMemsetAsync(ws.xpre.as<unsigned char>() + (size_t)(prow / 32) * tile_bytes, 0, (size_t)((prow_wg - prow) / 32) * tile_bytes, st));
-    HIP_TRY(hipMemsetAsync(ws.lranges.p, 0, (size_t)ncol * 4 * sizeof(int), st));
-    HIP_TRY(lseed_sort_launch(kc, false, xh, nrows, sh.g, l2.lanchors.p, C, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(),
-                              ws.ltot.as<uint32_t>(), st, l2.slots2));
-    HIP_TRY(lseed_layout_launch(C, l2.lrefcnt.as<uint32_t>(), ws.ltot.as<uint32_t>(), cap, P.lkeep, (int)sh.ref_tiles_alloc, rest,
-                                ws.llay.as<int64_t>(), ws.lranges.as<int>(), ncol, st));
-    if (sub) {
-        const int S = l2.local_sub;
-        if ((rc = ws.lsubpk.reserve((size_t)(prow / 32) * tile_bytes + 128)) || (rc = ws.lsubmap.reserve((size_t)prow * sizeof(uint32_t))) ||
-            (rc = ws.lkey2.reserve(lseed_key_bytes(prow))) || (rc = ws.lblk2.reserve(lseed_blockcnt_bytes(prow, C * S))) ||
-            (rc = ws.ltot2.reserve((size_t)C * S * sizeof(uint32_t))) || (rc = ws.lsublay.reserve((size_t)C * S * sizeof(int64_t))))
-            return rc;
-        HIP_TRY(hipMemsetAsync(ws.lsubmap.p, 0xFF, (size_t)prow * sizeof(uint32_t), st));
-        HIP_TRY(lseed_move_launch(kc, xh, nrows, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), 0, 0,
-                                  ws.lsubpk.as<unsigned char>(), ws.lsubmap.as<uint32_t>(), st));
-        HIP_TRY(lseed_sub_sort_launch(kc, false, ws.lsubpk.as<unsigned char>(), prow, ws.lsubmap.as<uint32_t>(), ws.lkey.as<uint32_t>(),
-                                      l2.lsub.p, l2.lsubnorm.as<float>(), l2.lsubrank.as<uint8_t>(), l2.lrefcnt.as<uint32_t>(), C, S,
-                                      ws.llay.as<int64_t>(), ws.lkey2.as<uint32_t>(), ws.lblk2.as<uint32_t>(), ws.ltot2.as<uint32_t>(),
-                                      ws.lsublay.as<int64_t>(), st));
-        HIP_TRY(lseed_sub_move_launch(kc, ws.lsubpk.as<unsigned char>(), prow, ws.lsubmap.as<uint32_t>(), ws.lkey2.as<uint32_t>(),
-                                      ws.lblk2.as<uint32_t>(), ws.lsublay.as<int64_t>(), xh, 0, C, ws.llay.as<int64_t>(),
-                                      ws.xpre.as<unsigned char>(), ws.lmap.as<uint32_t>(), st));
-    } else
-    HIP_TRY(lseed_move_launch(kc, xh, nrows, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), 0, 0,
-                              ws.xpre.as<unsigned char>(), ws.lmap.as<uint32_t>(), st));
-    HIP_TRY(l2c_pre_launch(kc, P.lkeep, ws.xpre.as<unsigned char>(), l2.ycpk1.as<unsigned char>(), (int)p.tps, 1, prow, 0, 0, 2,
-                           sh.ref_tiles_alloc - 1, st, prow, p.pre->as<float>(), ws.lranges.as<int>(), LSEED_COL_ROWS,
-                           ws.lmap.as<uint32_t>()));
+    HIP_TRY(hipMemsetAsync(out.map.p, 0xFF, (size_t)prow_wg * sizeof(uint32_t), st));
+    if (prow_wg > prow) HIP_TRY(hipMemsetAsync(out.ordered.as<unsigned char>() + (size_t)(prow / 32) * tile_bytes, 0, (size_t)((prow_wg - prow) / 32) * tile_bytes, st));
+    HIP_TRY(hipMemsetAsync(out.column_ranges.p, 0, (size_t)ncol * 4 * sizeof(int), st));
+    BucketSort sort;
+    sort.rows = true;
+    sort.kc = kc;
+    sort.cells = ix->ws.xpk.as<unsigned char>() + (size_t)(p.row0 / 32) * tile_bytes;
+    sort.ncell = nrows;
+    sort.cap = l2.buckets.cap;
+    sort.lkeep = P.lkeep;
+    sort.tile0 = (int)sh.ref_tiles_alloc;
+    sort.rest[1] = (int)p.tps;
+    sort.rest[2] = pt;
+    sort.rest[3] = pt > 0 ? gt : 0;
+    sort.column_ranges = out.column_ranges.as<int>();
+    sort.columns = ncol;
+    sort.sub = sub ? BucketSort::USE_SUB_ANCHORS : BucketSort::CALLER_ORDER;
+    sort.positions = prow;
+    sort.dst = out.ordered.as<unsigned char>();
+    sort.dst_map = out.map.as<uint32_t>();
+    if ((rc = bucket_sort(ix, sort))) return rc;
+    HIP_TRY(l2c_pre_launch(kc, P.lkeep, out.ordered.as<unsigned char>(), l2.ycpk1.as<unsigned char>(), (int)p.tps, 1, prow, 0, 0, 2,
+                           sh.ref_tiles_alloc - 1, st, prow, p.pre->as<float>(), out.column_ranges.as<int>(), LSEED_COL_ROWS,
+                           out.map.as<uint32_t>()));
     return NABO_OK;
+}
+
+// What the lists of one launch of the one-product pass start from: one threshold per (row, split) at `stride` per row
+// (0: one per row), the reference tiles its tournament looked at, and whether its rows now lie in bucket order for the stream.
+struct L2Seeds {
+    const float *tau = nullptr;
+    int stride = 0, pre_tiles = 0;
+    bool ordered = false;
+};
+
+// Tournament seeds of one part (l2c_topk.hip: l2c_pre_kernel): every (row, split) list starts from an upper bound of its
+// lkeep-th smallest score among some references instead of +inf -- the row's own bucket (local_seeds) where the planner
+// takes local seeds, otherwise the split's first references.  stream: a part with local seeds is sorted for the two-level
+// stream (the main launch of a plan with tl_main, where the ordered references exist and the verdict allows).
+static int part_seeds(nabo_index *ix, const PassCtx &ctx, const Query &q, const L2Plan &P, L2Part &p, int pre_pct, bool stream, L2Seeds *s)
+{
+    const IndexShape &sh = ix->shape;
+    auto &l2 = ix->ref.l2;
+    int rc, pt = 0, gt = 2;
+    l2c_pre_plan(P.kcq, P.lkeep, (int)p.tps, pre_pct, &pt, &gt);
+    if (ctx.first() && p.gx > 0 && lseed_applies(sh, P, p.S, p.end(q.m) - p.row0)) {
+        if ((rc = local_seeds(ix, q, P, p, pt, gt, stream && l2.buckets.sub_count > 1))) return rc;
+        s->ordered = stream;
+    } else {
+        if (pt <= 0 || p.gx == 0) return NABO_OK;
+        if ((rc = p.pre->reserve((size_t)p.rows * p.S * sizeof(float)))) return rc;
+        HIP_TRY(l2c_pre_launch(P.kcq, P.lkeep, ix->ws.xpk.as<unsigned char>(), l2.ycpk1.as<unsigned char>(), (int)p.tps, p.S, p.rows,
+                               p.row0 / 32, pt, gt, sh.ref_tiles_alloc - 1, ix->stream, q.m, p.pre->as<float>()));
+    }
+    s->tau = p.pre->as<float>();
+    s->stride = p.S;
+    s->pre_tiles = pt;
+    return NABO_OK;
+}
+
+// The PROBE of an unknown verdict (two_level_verdict.h: when it is due, and what its counters mean): the ordered main
+// launch's first workgroups over the stream's first tiles, as it always ran -- no progress window.  Its lists are scratch:
+// the launch proper writes every row again.  One host wait.
+static int probe_stream(nabo_index *ix, const L2Plan &P, L2Part &p, const L2Seeds &seed, int64_t prow, const L2cOrdered &ord)
+{
+    auto &l2 = ix->ref.l2;
+    auto &in = ix->ws.buckets.rows;
+    hipStream_t st = ix->stream;
+    unsigned long long probe[3] = {0, 0, 0};
+    L2cOrdered pord = ord;
+    pord.window = -1;
+    HIP_TRY(hipMemsetAsync(in.tile_counters.p, 0, sizeof(probe), st));
+    HIP_TRY(l2c_topk_launch(P.kcq, P.geo, in.ordered.as<unsigned char>(), l2.buckets.ordered.as<unsigned char>(), TL_PROBE_TILES, 1,
+                            TL_PROBE_WORKGROUPS, 0, P.lkeep, p.idx->as<uint32_t>(), nullptr, p.tau->as<float>(), l2.buckets.ordered_tiles, st,
+                            prow, seed.tau, seed.stride, 0, &pord));
+    HIP_TRY(hipMemcpyAsync(probe, in.tile_counters.p, sizeof(probe), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+#ifdef NABO_TL_TRACE        // (a build of its own, _build.py --out ... -DNABO_TL_TRACE: the probe's counters, for the records)
+    fprintf(stderr, "two-level probe: one-step %llu, refetched %llu, two-step %llu\n", probe[0], probe[1], probe[2]);
+#endif
+    l2.stream_verdict.give(tl_probe_verdict(probe[0], probe[2]));
+    return NABO_OK;
+}
+
+// The ordered main launch of the two-level stream.  Targets: the bucket-ordered copy local_seeds made (whole workgroups of
+// positions); references: the ordered copy and its two padding tiles; lists and seeds by the launch's rows, candidates as
+// reference indices.
+static int stream_launch(nabo_index *ix, const L2Plan &P, L2Part &p, const L2Seeds &seed, int64_t prow, const L2cOrdered &ord)
+{
+    auto &l2 = ix->ref.l2;
+    auto &in = ix->ws.buckets.rows;
+    hipStream_t st = ix->stream;
+    HIP_TRY(hipMemsetAsync(in.tile_counters.p, 0, 3 * sizeof(unsigned long long), st));
+    HIP_TRY(l2c_topk_launch(P.kcq, P.geo, in.ordered.as<unsigned char>(), l2.buckets.ordered.as<unsigned char>(), (int)l2.buckets.ordered_tiles, 1,
+                            (int)((prow + P.rows_per_wg - 1) / P.rows_per_wg), 0, P.lkeep, p.idx->as<uint32_t>(),
+                            p.merge ? p.key->as<float>() : nullptr, p.tau->as<float>(), l2.buckets.ordered_tiles, st, prow, seed.tau,
+                            seed.stride, 0, &ord));
+    in.streamed = true;
+    in.positions = prow;
+    return NABO_OK;
+}
+
+// A launch of the one-product kernel over the caller-order operands.  (Rows beyond the part's are padding to it: the main
+// part of a plan cut on whole rounds of positions, run in caller order after all, ends inside a workgroup and the tail
+// launch takes over there.)
+static int plain_launch(nabo_index *ix, const Query &q, const L2Plan &P, L2Part &p, const L2Seeds &seed)
+{
+    const IndexShape &sh = ix->shape;
+    HIP_TRY(l2c_topk_launch(P.kcq, P.geo, ix->ws.xpk.as<unsigned char>(), ix->ref.l2.ycpk1.as<unsigned char>(), (int)p.tps, p.S,
+                            (int)p.wgs(P.rows_per_wg), p.row0 / 32, P.lkeep, p.idx->as<uint32_t>(), p.merge ? p.key->as<float>() : nullptr,
+                            p.tau->as<float>(), sh.ref_tiles_alloc - 1, ix->stream, p.end(q.m), seed.tau, seed.stride, p.row0));
+    return NABO_OK;
+}
+
+// The main launch of a part whose rows local_seeds sorted for the stream: behind a probe where one is due, and in caller
+// order after all where the probe says no.
+static int main_launch_ordered(nabo_index *ix, const Query &q, const L2Plan &P, L2Part &p, const L2Seeds &seed)
+{
+    const IndexShape &sh = ix->shape;
+    auto &l2 = ix->ref.l2;
+    auto &in = ix->ws.buckets.rows;
+    int rc;
+    const int64_t prow = ordered_positions(ix, p.end(q.m) - p.row0);
+    if ((rc = in.tile_counters.reserve(3 * sizeof(unsigned long long)))) return rc;
+    const L2cOrdered ord = {in.map.as<uint32_t>(), l2.buckets.ordered_map.as<uint32_t>(), in.tile_counters.as<unsigned long long>(),
+                            sh.opt.two_level_share, sh.opt.two_level_stretch, l2.buckets.bucket_ends.as<int32_t>(), l2.buckets.buckets,
+                            sh.opt.two_level_burst, sh.opt.two_level_window, sh.opt.two_level_check};
+    if (tl_probe_due(l2.stream_verdict, sh.opt.two_level, (prow + P.rows_per_wg - 1) / P.rows_per_wg, l2.buckets.ordered_tiles) &&
+        (rc = probe_stream(ix, P, p, seed, prow, ord)))
+        return rc;
+    return l2.stream_verdict.streams() ? stream_launch(ix, P, p, seed, prow, ord) : plain_launch(ix, q, P, p, seed);
 }
 
 // The filter kernels of a pass, main launch then tail: the one-product kernel behind its tournament seeds (l2c_topk.hip),
@@ -171,17 +271,15 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
     auto &ws = ix->ws;
     hipStream_t st = ix->stream;
     int rc;
-    const int64_t pad_tile = sh.ref_tiles_alloc - 1;
-    const bool first = ctx.first();
-    const unsigned char *xh = ws.xpk.as<unsigned char>();
-    const unsigned char *yh = P.use_1 ? l2.ycpk1.as<unsigned char>() : l2.ycpk.as<unsigned char>();
     *beside = false;
     if (!P.on_l2c) {
+        const int64_t pad_tile = sh.ref_tiles_alloc - 1;
         for (L2Part &p : part) {
             if (p.gx == 0) continue;
             if (P.use_h)
-                HIP_TRY(l2q_topk_launch(P.kcq, xh, yh, (int)p.tps, p.S, (int)p.gx, p.row0 / 32, P.lkeep, p.idx->as<uint32_t>(),
-                                        nullptr, p.tau->as<float>(), pad_tile, st));
+                HIP_TRY(l2q_topk_launch(P.kcq, ws.xpk.as<unsigned char>(), P.use_1 ? l2.ycpk1.as<unsigned char>() : l2.ycpk.as<unsigned char>(),
+                                        (int)p.tps, p.S, (int)p.gx, p.row0 / 32, P.lkeep, p.idx->as<uint32_t>(), nullptr, p.tau->as<float>(),
+                                        pad_tile, st));
             else
                 HIP_TRY(l2_topk_launch(sh.ksteps, P.r1 ? -1 : q.epl, ws.xpk.as<float>(), l2.ypk.as<float>(), (int)p.tps,
                                        p.S, (int)p.gx, p.row0 / 32, P.lkeep, p.idx->as<uint32_t>(), nullptr,
@@ -189,96 +287,27 @@ static int l2_filter(nabo_index *ix, const PassCtx &ctx, const Query &q, const L
         }
         return NABO_OK;
     }
-    // Tournament seeds (l2c_topk.hip: l2c_pre_kernel): every (row, split) list starts from an upper bound of its
-    // lkeep-th smallest score among the split's first references instead of +inf -- not for a pass that has its
-    // seeds already.  Option prepass: 0 off, otherwise percent of the planned length (same bits always).
+    L2Part &pmain = part[0], &ptail = part[1];
+    // Tournament seeds of both launches first -- not for a pass that has its seeds already.  Option prepass: 0 off,
+    // otherwise percent of the planned length (same bits always).
+    L2Seeds seed_main, seed_tail;
+    seed_main.tau = seed_tail.tau = seeds;
     const int pre_pct = seeds ? 0 : sh.opt.prepass;
-    const float *seed[2] = {seeds, seeds};
-    int stride[2] = {0, 0};
-    if (first) ix->last.pre_tiles_last = 0;
-    bool ordered = false;                // the main launch streams the bucket-ordered operands (two-level, l2c_topk.hip)
-    for (int i = 0; i < 2 && pre_pct > 0; ++i) {
-        L2Part &p = part[i];
-        int pt = 0, gt = 2;
-        l2c_pre_plan(P.kcq, P.lkeep, (int)p.tps, pre_pct, &pt, &gt);
-        if (first && p.gx > 0 && lseed_applies(sh, P, p.S, p.end(q.m) - p.row0)) {
-            const bool ord = i == 0 && P.tl_main && l2.ord_built && l2.tl_verdict != 2;
-            if ((rc = local_seeds(ix, q, P, p, pt, gt, ord && l2.local_sub > 1))) return rc;
-            seed[i] = p.pre->as<float>();
-            stride[i] = p.S;
-            if (i == 0 && first) ix->last.pre_tiles_last = pt;
-            if (ord) ordered = true;
-            continue;
-        }
-        if (pt <= 0 || p.gx == 0) continue;
-        if ((rc = p.pre->reserve((size_t)p.rows * p.S * sizeof(float)))) return rc;
-        HIP_TRY(l2c_pre_launch(P.kcq, P.lkeep, xh, yh, (int)p.tps, p.S, p.rows, p.row0 / 32, pt, gt, pad_tile, st, q.m,
-                               p.pre->as<float>()));
-        seed[i] = p.pre->as<float>();
-        stride[i] = p.S;
-        if (i == 0 && first) ix->last.pre_tiles_last = pt;
-    }
-    for (int i = 0; i < 2; ++i) {
-        L2Part &p = part[i];
-        if (p.gx == 0) continue;
-        const int64_t prow = ordered ? lseed_columns(p.end(q.m) - p.row0, l2.local_C) * LSEED_COL_ROWS : 0;
-        const int64_t gx_ord = (prow + P.rows_per_wg - 1) / P.rows_per_wg;
-        L2cOrdered ord = {ws.lmap.as<uint32_t>(), l2.yordmap.as<uint32_t>(), nullptr, sh.opt.two_level_share, sh.opt.two_level_stretch,
-                          l2.yordend.as<int32_t>(), l2.local_C, sh.opt.two_level_burst, sh.opt.two_level_window,
-                          sh.opt.two_level_check};
-        if (i == 0 && ordered) {
-            if ((rc = ws.tlstats.reserve(3 * sizeof(unsigned long long)))) return rc;
-            ord.stats = ws.tlstats.as<unsigned long long>();
-        }
-        // PROBE (long launches, default setting): on data without clusters the bounds of the first step reject nothing, the
-        // waves run the two-step loop anyway, and the bucket-ordered stream is the worst order for their lists (every row
-        // of a wave meets its neighbours at once: one broad Gaussian cloud, 1M x 1M: 119 ms per step against 89).  The
-        // kernel's own counters tell the two apart in a few hundred microseconds: the first 128 workgroups (rows of the
-        // first buckets) over the first 1024 tiles (the same buckets' references, own and foreign).  Fewer than 30 % of
-        // those tiles run one-step: this query and the next ones take the caller-order stream.  The verdict, yes or no,
-        // is remembered (tl_verdict, index.h): the probe runs once per TL_VERDICT_REPACKS repacks of the references, not
-        // per query.  A HEURISTIC -- two or three buckets stand for all, the threshold was set on two kinds of data; a
-        // wrong "yes" is corrected by the launch's own counters, a wrong "no" costs the gain until the verdict expires.
-        // Its lists are scratch: the launch proper writes every row again.  One host wait.
-        if (i == 0 && ordered && l2.tl_verdict == 0 && sh.opt.two_level == 1 && gx_ord >= 512 && l2.ord_tiles >= 4096) {
-            unsigned long long probe[3] = {0, 0, 0};
-            L2cOrdered pord = ord;               // (the probe runs as it always has: no progress window)
-            pord.window = -1;
-            HIP_TRY(hipMemsetAsync(ws.tlstats.p, 0, sizeof(probe), st));
-            HIP_TRY(l2c_topk_launch(P.kcq, P.geo, ws.xpre.as<unsigned char>(), l2.yord.as<unsigned char>(), 1024, 1, 128, 0, P.lkeep,
-                                    p.idx->as<uint32_t>(), nullptr, p.tau->as<float>(), l2.ord_tiles, st, prow, seed[i], stride[i], 0, &pord));
-            HIP_TRY(hipMemcpyAsync(probe, ws.tlstats.p, sizeof(probe), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-#ifdef NABO_TL_TRACE        // (a build of its own, _build.py --out ... -DNABO_TL_TRACE: the probe's counters, for the records)
-            fprintf(stderr, "two-level probe: one-step %llu, refetched %llu, two-step %llu\n", probe[0], probe[1], probe[2]);
-#endif
-            l2.tl_verdict = probe[0] * 10 < (probe[0] + probe[2]) * 3 ? 2 : 1;
-            l2.tl_age = 0;
-            if (l2.tl_verdict == 2) ordered = false;
-        }
-        if (i == 0 && ordered) {
-            // targets: the bucket-ordered copy local_seeds made (whole workgroups of positions); references: the ordered
-            // copy and its two padding tiles; lists and seeds by the launch's rows, candidates as reference indices
-            HIP_TRY(hipMemsetAsync(ws.tlstats.p, 0, 3 * sizeof(unsigned long long), st));
-            HIP_TRY(l2c_topk_launch(P.kcq, P.geo, ws.xpre.as<unsigned char>(), l2.yord.as<unsigned char>(), (int)l2.ord_tiles, 1,
-                                    (int)((prow + P.rows_per_wg - 1) / P.rows_per_wg), 0, P.lkeep, p.idx->as<uint32_t>(),
-                                    p.merge ? p.key->as<float>() : nullptr, p.tau->as<float>(), l2.ord_tiles, st, prow, seed[i],
-                                    stride[i], 0, &ord));
-            ix->last.tl_ran = true;
-            ix->last.tl_row_pos = prow;
-        } else
-        // (rows beyond the part's are padding to it: the main part of a plan cut on whole rounds of positions, run in
-        // caller order after all, ends inside a workgroup and the tail launch takes over there)
-        HIP_TRY(l2c_topk_launch(P.kcq, P.geo, xh, yh, (int)p.tps, p.S, (int)p.wgs(P.rows_per_wg), p.row0 / 32, P.lkeep,
-                                p.idx->as<uint32_t>(), p.merge ? p.key->as<float>() : nullptr, p.tau->as<float>(),
-                                pad_tile, st, p.end(q.m), seed[i], stride[i], p.row0));
+    if (pre_pct > 0 &&
+        ((rc = part_seeds(ix, ctx, q, P, pmain, pre_pct, P.tl_main && l2.buckets.ordered_built && l2.stream_verdict.streams(), &seed_main)) ||
+         (rc = part_seeds(ix, ctx, q, P, ptail, pre_pct, false, &seed_tail))))
+        return rc;
+    if (ctx.first()) ix->last.pre_tiles_last = seed_main.pre_tiles;
+    if (pmain.gx > 0) {
+        if ((rc = seed_main.ordered ? main_launch_ordered(ix, q, P, pmain, seed_main) : plain_launch(ix, q, P, pmain, seed_main))) return rc;
         // the tail launch (a fraction of a round, reference splits) leaves most CUs idle: the refine of the main
         // launch's rows (an HBM gather) runs beside it on the second stream
-        if (i == 0 && part[1].gx > 0 && !q.cand_mode && sh.opt.refine_overlap != 0) {
+        if (ptail.gx > 0 && !q.cand_mode && sh.opt.refine_overlap != 0) {
             HIP_TRY(hipEventRecord(ix->ev_main, st));
             *beside = true;
         }
     }
+    if (ptail.gx > 0 && (rc = plain_launch(ix, q, P, ptail, seed_tail))) return rc;
     return NABO_OK;
 }
 
@@ -410,7 +439,7 @@ static int query_l2(nabo_index *ix, const PassCtx &ctx, Query &q)
     if (ctx.first()) {
         ix->last.pass_rows[0] = ix->last.pass_rows[1] = ix->last.pass_rows[2] = 0;
         snprintf(ix->last.kernel, sizeof(ix->last.kernel), "%s", P.kernel);
-        ix->last.tl_ran = false;
+        ws.buckets.rows.streamed = false;
     }
     if ((rc = ensure_packed(ix, P.use_1 ? 2 : P.use_h ? 1 : 0))) return rc;
     // (before anything takes the operands' address: a change of options since the pack moves them)
@@ -484,20 +513,16 @@ static int query_l2(nabo_index *ix, const PassCtx &ctx, Query &q)
     }
     HIP_TRY(hipMemcpyAsync(&q.n_fail, ws.failcnt.p, sizeof(q.n_fail), hipMemcpyDeviceToHost, st));
     unsigned long long tl_tiles[3] = {0, 0, 0};
-    const bool tl_ran = ctx.first() && ix->last.tl_ran;
-    if (tl_ran) HIP_TRY(hipMemcpyAsync(tl_tiles, ws.tlstats.p, sizeof(tl_tiles), hipMemcpyDeviceToHost, st));
+    const bool tl_ran = ctx.first() && ws.buckets.rows.streamed;
+    if (tl_ran) HIP_TRY(hipMemcpyAsync(tl_tiles, ws.buckets.rows.tile_counters.p, sizeof(tl_tiles), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (tl_ran) {
         // the two-level launch's tile counters: into the record (the kernel string carries them to nabo_index_last_kernel),
-        // and the memory of a poor outcome -- waves that ran fewer than a quarter of their tiles one-step paid the
-        // bucket-ordered stream for nothing: the next queries take the caller-order stream (tl_verdict)
+        // and the memory of a poor outcome: the next queries take the caller-order stream (two_level_verdict.h)
         const size_t len = strlen(ix->last.kernel);
         snprintf(ix->last.kernel + len, sizeof(ix->last.kernel) - len, " [two-level tiles: one-step %lld, refetched %lld, two-step %lld]",
                  (long long)tl_tiles[0], (long long)tl_tiles[1], (long long)tl_tiles[2]);
-        if (sh.opt.coarse_adapt != 0 && m >= 1024 && tl_tiles[0] * 3 < tl_tiles[2]) {
-            l2.tl_verdict = 2;
-            l2.tl_age = 0;
-        }
+        if (tl_launch_says_no(m, sh.opt.coarse_adapt, tl_tiles[0], tl_tiles[2])) l2.stream_verdict.give(TwoLevelVerdict::CALLER_ORDER);
     }
     if (P.use_1 && q.n_fail > 0) {
         // Rows this one-product pass could not certify: from level 0 on the l2c kernel to the SEEDED one-product pass

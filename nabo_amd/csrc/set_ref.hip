@@ -44,10 +44,10 @@ int ensure_packed(nabo_index *ix, int want)
         // (behind the stream: the runs of the local tournament seeds, ensure_local_seeds)
         int lc = 0, lcap = 0;
         lseed_params(sh, &lc, &lcap);
-        l2.local_room = (int64_t)lc * (lcap / 32);
-        l2.local_built = l2.ord_built = false;
+        l2.buckets.runs_room = (int64_t)lc * (lcap / 32);
+        l2.buckets.runs_built = l2.buckets.ordered_built = false;
         l2.slots2 = two_level_slots(sh);
-        if ((rc = l2.ycpk1.reserve((size_t)(sh.ref_tiles_alloc + l2.local_room) * sh.kc1 * 1024 + 128))) return rc;
+        if ((rc = l2.ycpk1.reserve((size_t)(sh.ref_tiles_alloc + l2.buckets.runs_room) * sh.kc1 * 1024 + 128))) return rc;
         l2.hscale = scale = std::ldexp(1.0, e2 + 12);
         HIP_TRY(pack_cref_launch(l2.dYp, sh.n, sh.g, l2.centre.as<double>(), l2.hscale, sh.kc1,
                                  sh.ref_tiles_alloc, ref.dmask, l2.ycpk1.as<unsigned char>(),
@@ -81,15 +81,15 @@ int ensure_packed(nabo_index *ix, int want)
     return NABO_OK;
 }
 
-// The runs of the local tournament seeds (local_seeds.hip) for the index's current options: anchors, the references sorted
-// by bucket, the first `cap` unmasked cells of every bucket copied behind the one-product operands.  Enqueued on the
-// stream behind the pack; a query that takes local seeds calls this first (the runs are stale after every repack, and an
-// option may have changed C or the cap since).
+// The bucket order of the references (bucket_order.h) for the index's current options: anchors, the first `cap` unmasked
+// cells of every bucket copied behind the one-product operands (the runs of the local tournament seeds) and, for the
+// two-level stream, ALL unmasked references in bucket order.  Enqueued on the stream behind the pack; a query that takes
+// local seeds calls this first (everything is stale after every repack, and an option may have changed since).
 int ensure_local_seeds(nabo_index *ix)
 {
     const IndexShape &sh = ix->shape;
     auto &l2 = ix->ref.l2;
-    auto &ws = ix->ws;
+    BucketRefs &b = l2.buckets;
     hipStream_t st = ix->stream;
     int rc, C = 0, cap = 0;
     lseed_params(sh, &C, &cap);
@@ -97,73 +97,56 @@ int ensure_local_seeds(nabo_index *ix)
     if (l2.packed_c1 && l2.slots2 != two_level_slots(sh)) l2.packed_c1 = false;
     const int S = lseed_sub_param(sh), srank = sh.opt.two_level_sub_rank;
     // (a sub-order asked for since the copy was built, or another one: the ordered copy is built again)
-    if (l2.ord_built && (l2.local_sub != S || (S > 1 && l2.local_sub_rank != srank))) l2.ord_built = false;
-    if (l2.local_built && l2.local_C == C && l2.local_cap == cap && l2.packed_c1 && (l2.ord_built || !l2.slots2 || l2.tl_verdict == 2)) return NABO_OK;
-    if (!l2.packed_c1 || l2.local_room < (int64_t)C * (cap / 32)) {           // (options changed since the pack: room for the runs)
+    if (b.ordered_built && (b.sub_count != S || (S > 1 && b.sub_rank_rule != srank))) b.ordered_built = false;
+    if (b.runs_built && b.buckets == C && b.cap == cap && l2.packed_c1 && (b.ordered_built || !l2.slots2 || !l2.stream_verdict.streams()))
+        return NABO_OK;
+    if (!l2.packed_c1 || b.runs_room < (int64_t)C * (cap / 32)) {           // (options changed since the pack: room for the runs)
         l2.packed_c1 = false;
         if ((rc = ensure_packed(ix, 2))) return rc;
     }
-    const int64_t nblk_bytes = (int64_t)lseed_blockcnt_bytes(sh.n, C);
-    if ((rc = l2.lanchors.reserve(lseed_anchor_bytes(sh.kc1, C))) || (rc = l2.lrefcnt.reserve((size_t)C * sizeof(uint32_t))) ||
-        (rc = ws.lkey.reserve(lseed_key_bytes(sh.n))) || (rc = ws.lblk.reserve((size_t)nblk_bytes)) ||
-        (rc = ws.llay.reserve(lseed_layout_bytes(C))))
-        return rc;
+    b.runs_built = b.ordered_built = false;
+    b.buckets = C;
+    b.cap = cap;
+    if ((rc = b.anchors.reserve(lseed_anchor_bytes(sh.kc1, C))) || (rc = b.bucket_count.reserve((size_t)C * sizeof(uint32_t)))) return rc;
     unsigned char *ypk = l2.ycpk1.as<unsigned char>();
-    const int rest[4] = {0, 0, 0, 0};
-    HIP_TRY(lseed_anchors_launch(sh.kc1, ypk, sh.n, sh.g, C, l2.lanchors.p, st, l2.slots2));
-    HIP_TRY(lseed_sort_launch(sh.kc1, true, ypk, sh.n, sh.g, l2.lanchors.p, C, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(),
-                              l2.lrefcnt.as<uint32_t>(), st, l2.slots2));
-    HIP_TRY(lseed_layout_launch(C, l2.lrefcnt.as<uint32_t>(), nullptr, cap, 1, 0, rest, ws.llay.as<int64_t>(), nullptr, 0, st));
+    HIP_TRY(lseed_anchors_launch(sh.kc1, ypk, sh.n, sh.g, C, b.anchors.p, st, l2.slots2));
+    BucketSort sort;
+    sort.kc = sh.kc1;
+    sort.cells = ypk;
+    sort.ncell = sh.n;
     // (padding positions: a cell of the stream's last tile, which lies beyond the references -- +inf norm)
-    HIP_TRY(lseed_move_launch(sh.kc1, ypk, sh.n, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), cap,
-                              (sh.ref_tiles_alloc - 1) * 32, ypk + (size_t)sh.ref_tiles_alloc * sh.kc1 * 1024, nullptr, st));
-    if (l2.slots2 && l2.tl_verdict != 2) {
-        // The two-level stream (not for data that is known not to take it): ALL unmasked references in bucket order (the same keys and block offsets, no cap), every
-        // bucket in whole tiles, and the map from position to reference index.  The copy starts as padding cells (+inf
-        // norm): what the buckets leave of its ref_tiles + C tiles, and the two tiles behind them the filter's ring reads.
-        const int64_t ot = lseed_ordered_tiles(sh.ref_tiles, C);
-        if ((rc = l2.yord.reserve((size_t)(ot + 2) * sh.kc1 * 1024 + 128)) || (rc = l2.yordmap.reserve((size_t)(ot + 2) * 32 * sizeof(uint32_t))) ||
-            (rc = l2.yordend.reserve((size_t)C * sizeof(int32_t))))
-            return rc;
-        HIP_TRY(lseed_fill_launch(sh.kc1, ypk, (sh.ref_tiles_alloc - 1) * 32, l2.yord.as<unsigned char>(), (ot + 2) * 32, st));
-        HIP_TRY(hipMemsetAsync(l2.yordmap.p, 0xFF, (size_t)(ot + 2) * 32 * sizeof(uint32_t), st));
-        HIP_TRY(lseed_layout_launch(C, l2.lrefcnt.as<uint32_t>(), nullptr, 0, 1, 0, rest, ws.llay.as<int64_t>(), nullptr, 0, st));
-        HIP_TRY(lseed_ends_launch(C, ws.llay.as<int64_t>(), l2.yordend.as<int32_t>(), st));      // (the query reuses llay: the ends are kept)
-        if (S > 1) {
-            // The sub-order (local_seeds.h): the bucket-ordered copy goes to scratch first -- its buckets in caller order are
-            // where the sub-anchors are drawn from --, a second sort inside the buckets makes the copy the stream reads.  The
-            // runs of the tournament above were drawn before it: a spread sample of their buckets, as they always were.
-            const int64_t npos = ot * 32;
-            if ((rc = ws.lsubpk.reserve((size_t)ot * sh.kc1 * 1024 + 128)) || (rc = ws.lsubmap.reserve((size_t)npos * sizeof(uint32_t))) ||
-                (rc = l2.lsub.reserve(lseed_sub_anchor_bytes(sh.kc1, C, S))) || (rc = ws.lsubf.reserve(lseed_sub_float_bytes(sh.kc1, C, S))) ||
-                (rc = l2.lsubnorm.reserve((size_t)C * S * sizeof(float))) || (rc = l2.lsubrank.reserve((size_t)C * S)) ||
-                (rc = ws.lkey2.reserve(lseed_key_bytes(npos))) || (rc = ws.lblk2.reserve(lseed_blockcnt_bytes(npos, C * S))) ||
-                (rc = ws.ltot2.reserve((size_t)C * S * sizeof(uint32_t))) || (rc = ws.lsublay.reserve((size_t)C * S * sizeof(int64_t))))
-                return rc;
-            HIP_TRY(hipMemsetAsync(ws.lsubmap.p, 0xFF, (size_t)npos * sizeof(uint32_t), st));
-            HIP_TRY(lseed_move_launch(sh.kc1, ypk, sh.n, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), 0,
-                                      (sh.ref_tiles_alloc - 1) * 32, ws.lsubpk.as<unsigned char>(), ws.lsubmap.as<uint32_t>(), st));
-            HIP_TRY(lseed_sub_build_launch(sh.kc1, ws.lsubpk.as<unsigned char>(), ws.llay.as<int64_t>(), l2.lrefcnt.as<uint32_t>(), sh.g, C, S,
-                                           srank != 0, l2.lsub.p, ws.lsubf.as<float>(), l2.lsubrank.as<uint8_t>(), l2.lsubnorm.as<float>(), st,
-                                           l2.slots2));
-            HIP_TRY(lseed_sub_sort_launch(sh.kc1, true, ws.lsubpk.as<unsigned char>(), npos, ws.lsubmap.as<uint32_t>(), ws.lkey.as<uint32_t>(),
-                                          l2.lsub.p, l2.lsubnorm.as<float>(), l2.lsubrank.as<uint8_t>(), l2.lrefcnt.as<uint32_t>(), C, S,
-                                          ws.llay.as<int64_t>(), ws.lkey2.as<uint32_t>(), ws.lblk2.as<uint32_t>(), ws.ltot2.as<uint32_t>(),
-                                          ws.lsublay.as<int64_t>(), st));
-            HIP_TRY(lseed_sub_move_launch(sh.kc1, ws.lsubpk.as<unsigned char>(), npos, ws.lsubmap.as<uint32_t>(), ws.lkey2.as<uint32_t>(),
-                                          ws.lblk2.as<uint32_t>(), ws.lsublay.as<int64_t>(), ypk, (sh.ref_tiles_alloc - 1) * 32, C,
-                                          ws.llay.as<int64_t>(), l2.yord.as<unsigned char>(), l2.yordmap.as<uint32_t>(), st));
-        } else
-        HIP_TRY(lseed_move_launch(sh.kc1, ypk, sh.n, ws.lkey.as<uint32_t>(), ws.lblk.as<uint32_t>(), C, ws.llay.as<int64_t>(), 0,
-                                  (sh.ref_tiles_alloc - 1) * 32, l2.yord.as<unsigned char>(), l2.yordmap.as<uint32_t>(), st));
-        l2.local_sub = S;
-        l2.local_sub_rank = srank;
-        l2.ord_tiles = ot;
-        l2.ord_built = true;
-    }
-    l2.local_C = C;
-    l2.local_cap = cap;
-    l2.local_built = true;
+    sort.pad_cell = (sh.ref_tiles_alloc - 1) * 32;
+    sort.cap = cap;
+    sort.dst = ypk + (size_t)sh.ref_tiles_alloc * sh.kc1 * 1024;
+    if ((rc = bucket_sort(ix, sort))) return rc;
+    b.runs_built = true;
+    if (!l2.slots2 || !l2.stream_verdict.streams()) return NABO_OK;
+    // The two-level stream (not for data that is known not to take it): ALL unmasked references in bucket order (the same
+    // keys and block offsets, no cap), every bucket in whole tiles, and the map from position to reference index.  The copy
+    // starts as padding cells (+inf norm): what the buckets leave of its ref_tiles + C tiles, and the two tiles behind them
+    // the filter's ring reads.  With a sub-order the sub-anchors are drawn from this copy's buckets; the runs of the
+    // tournament above were drawn before it: a spread sample of their buckets, as they always were.
+    const int64_t ot = lseed_ordered_tiles(sh.ref_tiles, C);
+    b.sub_count = S;
+    b.sub_rank_rule = srank;
+    if ((rc = b.ordered.reserve((size_t)(ot + 2) * sh.kc1 * 1024 + 128)) || (rc = b.ordered_map.reserve((size_t)(ot + 2) * 32 * sizeof(uint32_t))) ||
+        (rc = b.bucket_ends.reserve((size_t)C * sizeof(int32_t))))
+        return rc;
+    if (S > 1 && ((rc = b.sub_anchors.reserve(lseed_sub_anchor_bytes(sh.kc1, C, S))) || (rc = b.sub_norms.reserve((size_t)C * S * sizeof(float))) ||
+                  (rc = b.sub_ranks.reserve((size_t)C * S))))
+        return rc;
+    HIP_TRY(lseed_fill_launch(sh.kc1, ypk, sort.pad_cell, b.ordered.as<unsigned char>(), (ot + 2) * 32, st));
+    HIP_TRY(hipMemsetAsync(b.ordered_map.p, 0xFF, (size_t)(ot + 2) * 32 * sizeof(uint32_t), st));
+    sort.assign = false;
+    sort.cap = 0;
+    sort.bucket_ends = b.bucket_ends.as<int32_t>();
+    sort.sub = S > 1 ? BucketSort::BUILD_SUB_ANCHORS : BucketSort::CALLER_ORDER;
+    sort.positions = ot * 32;
+    sort.dst = b.ordered.as<unsigned char>();
+    sort.dst_map = b.ordered_map.as<uint32_t>();
+    if ((rc = bucket_sort(ix, sort))) return rc;
+    b.ordered_tiles = ot;
+    b.ordered_built = true;
     return NABO_OK;
 }
 
@@ -220,7 +203,7 @@ static int repack_refs(nabo_index *ix)
     l2.packed_f32 = l2.packed_c16 = l2.packed_c1 = false;
     l2.ymax_pending = false;                      // (a read still in flight belongs to operands that are gone)
     l2.coarse_weak = false;
-    if (++l2.tl_age >= TL_VERDICT_REPACKS) l2.tl_verdict = l2.tl_age = 0;      // (the two-level verdict: asked again now and then)
+    l2.stream_verdict.repack();                   // (the two-level verdict: asked again now and then)
     return ensure_packed(ix, ix->shape.coarse ? 2 : ix->shape.mode == 1 ? 1 : 0);
 }
 

@@ -96,6 +96,66 @@ def test_a_masked_third_of_the_references_and_a_one_row_query(gpu_lib):
     _run(gpu_lib, X[5:6], Y)
 
 
+M_MEMORY = 1100         # at least 1024 rows (the memory's bound), no multiple of a wave's 96 rows or a workgroup's 384
+
+
+@functools.lru_cache(maxsize=None)
+def _memory_case(name):
+    """the two seeded data sets of the memory test with the oracle's answer for all M_MEMORY rows (a shorter query: a prefix)"""
+    if name == "clustered":
+        # four tight clusters of 1250 cells, one anchor cell (0, 1250, 2500, 3750) in each: the file's pca_like data leaves the
+        # verdict "no" at this shape just as the cloud does (seed 11: one-step 344, two-step 1600)
+        rng = np.random.default_rng(17)
+        centres = 20.0 * np.eye(4, 50)
+        Y = centres[np.repeat([0, 1, 2, 3], N // 4)] + rng.standard_normal((N, 50))
+        X = centres[rng.integers(0, 4, M_MEMORY)] + rng.standard_normal((M_MEMORY, 50))
+    else:
+        rng = np.random.default_rng(5)
+        Y, X = rng.standard_normal((N, 50)), rng.standard_normal((M_MEMORY, 50))
+    oi, od = oracle.knn(X, Y, K, 0, nthreads=8)
+    for a in (X, Y, oi, od):
+        a.setflags(write=False)
+    return X, Y, oi, od
+
+
+def _memory_query(ix, X, oi, od):
+    """one query against the oracle, every row; returns (the stream ran, what its counters make the memory say: it stays)"""
+    gi, gd = ix.query(X, K)
+    st, kern = ix.last_stats(), ix.last_kernel()
+    assert np.array_equal(gi, oi[:len(X)]) and np.array_equal(gd, od[:len(X)]), int((gi != oi[:len(X)]).any(axis=1).sum())
+    one, two = st["two_level_one_step_tiles"], st["two_level_two_step_tiles"]
+    print(len(X), "streamed" if "two-level tiles" in kern else "caller order", "one-step", one, "two-step", two)
+    return "two-level tiles" in kern, not one * 3 < two
+
+
+def test_the_memory_a_launch_leaves(gpu_lib):
+    """A launch of the stream whose waves ran fewer than a quarter of their tiles one-step (one_step * 3 < two_step) leaves
+    the verdict "no" (nabo_amd/csrc/two_level_verdict.h): the next query runs caller order -- from 1024 rows on; the verdict
+    outlives 15 further set_ref calls and is forgotten at the 16th.  Counters of the first query of M_MEMORY rows at the
+    commit before the verdict got its header: four tight clusters one-step 1728, two-step 540 (stays; 1000 rows: 1314 and
+    468); one cloud one-step 240, two-step 1704 (leaves; 1000 rows: the same, and both queries stream)."""
+    outcomes = set()
+    for name in ("clustered", "cloud"):
+        X, Y, oi, od = _memory_case(name)
+        ix = gpu_lib.KnnIndex(N, 50, options=TL).set_ref(Y)
+        streamed, stays = _memory_query(ix, X, oi, od)
+        assert streamed
+        outcomes.add(stays)
+        assert _memory_query(ix, X, oi, od)[0] == stays, name
+        if not stays:
+            for _ in range(15):
+                ix.set_ref(Y)
+            assert not _memory_query(ix, X, oi, od)[0]          # the verdict outlives 15 repacks ...
+            ix.set_ref(Y)
+            assert _memory_query(ix, X, oi, od)[0]              # ... and not the 16th
+        ix.close()
+        # below 1024 rows the rule is off: both queries stream, whatever the counters say
+        ix = gpu_lib.KnnIndex(N, 50, options=TL).set_ref(Y)
+        assert _memory_query(ix, X[:1000], oi, od)[0] and _memory_query(ix, X[:1000], oi, od)[0], name
+        ix.close()
+    assert outcomes == {True, False}, outcomes
+
+
 @pytest.mark.parametrize("g", [29, 59, 28, 60])
 def test_the_edges_in_d(gpu_lib, g):
     """one tail component, the last eligible d, and on either side a d the old path serves"""
