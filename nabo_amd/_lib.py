@@ -97,6 +97,10 @@ RENDER_SYMBOLS = ["nabo_render_create", "nabo_render_destroy", "nabo_render_clea
                   "nabo_render_edge_counts", "nabo_render_node_counts", "nabo_render_node_sums", "nabo_render_compose",
                   "nabo_render_last_ms", "nabo_render_alpha_lut", "nabo_render_geometry"]
 
+# every symbol include/nabo_ingest.h declares (Matrix Market counts to the cell and gene indexes; CSR to CSC)
+INGEST_SYMBOLS = ["nabo_mtx_create", "nabo_mtx_feed", "nabo_mtx_finish", "nabo_mtx_get_csr", "nabo_mtx_get_csc", "nabo_mtx_free",
+                  "nabo_mtx_geometry", "nabo_mtx_last_device_ms", "nabo_csr_transpose"]
+
 # what include/nabo_knn_inspect.h declares (a look into an index, for tests and tools)
 INSPECT_SYMBOLS = ["nabo_index_stream_order"]
 
@@ -287,11 +291,20 @@ def lib():
     L.nabo_render_last_ms.argtypes = [vp, C.POINTER(dbl)]
     L.nabo_render_alpha_lut.argtypes = [dbl, i32, vp]
     L.nabo_render_geometry.argtypes = [C.POINTER(i32)] * 6
+    L.nabo_mtx_create.argtypes = [i32, i64, i64, C.POINTER(vp)]
+    L.nabo_mtx_feed.argtypes = [vp, vp, i64]
+    L.nabo_mtx_finish.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.nabo_mtx_get_csr.argtypes = [vp, vp, vp, vp]
+    L.nabo_mtx_get_csc.argtypes = [vp, vp, vp, vp]
+    L.nabo_mtx_free.argtypes = [vp]
+    L.nabo_mtx_geometry.argtypes = [C.POINTER(i32), C.POINTER(i32)]
+    L.nabo_mtx_last_device_ms.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
+    L.nabo_csr_transpose.argtypes = [i32, i64, i64, vp, vp, vp, vp, vp, vp]
     for name in (SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS + UMAP_SYMBOLS
                  + UMAP_TRANSFORM_SYMBOLS + COMMUNITY_SYMBOLS + AGGLOM_SYMBOLS + POTENTIAL_SYMBOLS + BUNDLE_SYMBOLS + RENDER_SYMBOLS
-                 + INSPECT_SYMBOLS):
+                 + INGEST_SYMBOLS + INSPECT_SYMBOLS):
         if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy", "nabo_umap_destroy", "nabo_umap_transform_destroy", "nabo_community_destroy",
-                        "nabo_potential_destroy", "nabo_bundle_destroy", "nabo_render_destroy"):
+                        "nabo_potential_destroy", "nabo_bundle_destroy", "nabo_render_destroy", "nabo_mtx_free"):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L

@@ -95,6 +95,13 @@ hipError_t csr_build_launch(const int64_t *edge_r, const int64_t *edge_t, const 
     return hipGetLastError();
 }
 
+// csr_rowptr_kernel on its own, for sorted 32-bit keys from elsewhere (the gene index of mtx_ingest.hip); E = 0 gives zeros
+hipError_t u32_rowptr_launch(const uint32_t *keys, int64_t E, int64_t n, int64_t *ptr, hipStream_t st)
+{
+    hipLaunchKernelGGL(csr_rowptr_kernel, dim3((unsigned)((E + 256) / 256)), dim3(256), 0, st, keys, E, n, ptr);
+    return hipGetLastError();
+}
+
 // Sorted 64-bit keys (row << 32 | column) -> their row pointer: ptr[r] = the first key whose row is >= r, r = 0 .. n.  Keys
 // that stand for no arc carry row n and sort to the end, so ptr[n] counts the arcs.  For the UMAP graph (umap.hip) and the
 // coarse graphs of the clustering (community.hip); n_keys >= 1.

@@ -195,6 +195,35 @@ hipError_t csr_build_launch(const int64_t *edge_r, const int64_t *edge_t, const 
 // sorted (row << 32 | column) keys, row n for a key that is no arc -> ptr [n + 1]; and the bits their radix sort needs (csr_build.hip)
 hipError_t key_rowptr_launch(const uint64_t *keys, int64_t n_keys, int64_t n, int64_t *ptr, hipStream_t st);
 unsigned key_sort_bits(int64_t n);
+// sorted 32-bit keys in [0, n) -> ptr [n + 1], ptr[r] = the first position whose key is >= r; E = 0 is allowed (csr_build.hip)
+hipError_t u32_rowptr_launch(const uint32_t *keys, int64_t E, int64_t n, int64_t *ptr, hipStream_t st);
+
+// Matrix Market text -> entries in file order, and the sorts that make the two indexes of them (mtx_ingest.hip).
+// One piece of whole lines: text [len] (readable up to a whole 16 bytes), one workgroup per tile of n_tiles =
+// ceil(len / tile); stage_key / stage_val [n_tiles * mtx_tile_entries()], tile_count and tile_base [n_tiles + 1];
+// the piece's entries go to out_key / out_val [nnz] from position `done` on (those at or past nnz are dropped);
+// tile_base[n_tiles] is their number and res the lowest bad line and the number of lines.
+struct MtxPieceResult {
+    unsigned long long err;      // min over the bad lines of (byte offset of the line in the piece << 8 | code); ~0: none
+    unsigned long long n_lines;
+};
+int mtx_tile_entries();
+hipError_t mtx_scan_temp_bytes(int64_t n_tiles, size_t *bytes);
+hipError_t mtx_parse_launch(const uint8_t *text, int64_t len, int64_t n_genes, int64_t n_cells, uint64_t *stage_key, uint32_t *stage_val,
+                            uint32_t *tile_count, uint32_t *tile_base, void *temp, size_t temp_bytes, int64_t done, int64_t nnz,
+                            uint64_t *out_key, uint32_t *out_val, MtxPieceResult *res, hipStream_t st);
+// (major << 32 | minor) keys with 4-byte values, both double-buffered (a: the data, b: scratch; which: 0 / 1, the buffer
+// that holds the data, updated): sorted by the minor's bits [0, bits(n_minor)) alone (STABLE) and, with_major, by the
+// major's bits after that
+hipError_t mtx_sort_temp_bytes(int64_t nnz, int64_t n_major, int64_t n_minor, size_t *bytes);
+hipError_t mtx_sort_launch(uint64_t *key[2], uint32_t *val[2], int *which, int64_t nnz, int64_t n_major, int64_t n_minor, bool with_major,
+                           void *temp, size_t temp_bytes, hipStream_t st);
+// *dup = the lowest key that equals its left neighbour (~0: none)
+hipError_t mtx_dup_launch(const uint64_t *keys, int64_t nnz, unsigned long long *dup, hipStream_t st);
+// lo[i] = the low, hi[i] = the high half of keys[i]; either may be NULL
+hipError_t mtx_split_launch(const uint64_t *keys, int64_t nnz, uint32_t *lo, uint32_t *hi, hipStream_t st);
+// keys[e] = row of e << 32 | idx[e] for the entries of a CSR
+hipError_t mtx_expand_launch(const int64_t *ptr, int64_t n_rows, const int32_t *idx, int64_t nnz, uint64_t *keys, hipStream_t st);
 
 // differential expression: keys of a gene chunk, their sort and the rank kernel (de_rank.hip)
 hipError_t de_temp_bytes(int64_t nnz_max, int64_t keys_max, int64_t n_seg, size_t *bytes);
