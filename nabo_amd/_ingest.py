@@ -220,7 +220,7 @@ def mtx_to_h5(in_dir, h5_fn, batch_size=10000, value_dtype=np.int64):
 
     One departure: a cell without entries gets an EMPTY cell_data dataset.  The reference writes none (except for the
     first cell, by an accident of its loop), and its own Dataset then fails on such a cell."""
-    import h5py
+    import h5py  # noqa: F401  (fail before the matrix is read, not after)
     in_dir = str(in_dir)
     m = read_mtx(in_dir)
     genes, gene_file = read_gene_names(in_dir)
@@ -229,10 +229,19 @@ def mtx_to_h5(in_dir, h5_fn, batch_size=10000, value_dtype=np.int64):
     cells = read_barcodes(in_dir)
     if len(cells) != m.n_cells:
         raise ValueError("Number of cells in barcodes.tsv not same as in the mtx file")
-    dtype = [("idx", np.uint), ("val", value_dtype)]
     if os.path.isfile(h5_fn):
         print("Overwriting %s" % h5_fn, flush=True)
         os.remove(h5_fn)
+    write_dataset_file(h5_fn, m, genes, cells, value_dtype)
+    return None
+
+
+def write_dataset_file(h5_fn, m, genes, cells, value_dtype=np.int64):
+    """A Nabo dataset file of the CountMatrix m: names/{genes,cells}, cell_data/<cell> and gene_data/<gene>, records of
+    dtype [('idx', np.uint), ('val', value_dtype)], one dataset per cell and per gene (an empty one for none without
+    entries).  What mtx_to_h5, extract_cells_from_h5 and merge_h5 write."""
+    import h5py
+    dtype = [("idx", np.uint), ("val", value_dtype)]
     with h5py.File(h5_fn, mode="a", libver="latest") as h5:
         grp = h5.create_group("names")
         grp.create_dataset("genes", chunks=None, data=[x.encode("ascii") for x in genes])

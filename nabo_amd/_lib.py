@@ -101,6 +101,10 @@ RENDER_SYMBOLS = ["nabo_render_create", "nabo_render_destroy", "nabo_render_clea
 INGEST_SYMBOLS = ["nabo_mtx_create", "nabo_mtx_feed", "nabo_mtx_finish", "nabo_mtx_get_csr", "nabo_mtx_get_csc", "nabo_mtx_free",
                   "nabo_mtx_geometry", "nabo_mtx_last_device_ms", "nabo_csr_transpose"]
 
+# every symbol include/nabo_counts.h declares (the Matrix Market writer; the remap behind subsetting and merging counts)
+COUNTS_SYMBOLS = ["nabo_mtxw_create", "nabo_mtxw_read", "nabo_mtxw_last_device_ms", "nabo_mtxw_free", "nabo_mtxw_geometry",
+                  "nabo_counts_remap"]
+
 # what include/nabo_knn_inspect.h declares (a look into an index, for tests and tools)
 INSPECT_SYMBOLS = ["nabo_index_stream_order"]
 
@@ -300,11 +304,17 @@ def lib():
     L.nabo_mtx_geometry.argtypes = [C.POINTER(i32), C.POINTER(i32)]
     L.nabo_mtx_last_device_ms.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
     L.nabo_csr_transpose.argtypes = [i32, i64, i64, vp, vp, vp, vp, vp, vp]
+    L.nabo_mtxw_create.argtypes = [i32, i64, i64, vp, vp, vp, C.c_char_p, i32, i64, i64, C.POINTER(vp), C.POINTER(i64)]
+    L.nabo_mtxw_read.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.nabo_mtxw_last_device_ms.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
+    L.nabo_mtxw_free.argtypes = [vp]
+    L.nabo_mtxw_geometry.argtypes = [C.POINTER(i32)] * 4
+    L.nabo_counts_remap.argtypes = [i32, i64, i64, vp, vp, vp, i64, vp, i64, vp, C.POINTER(i64), vp, vp, vp, vp, vp, vp]
     for name in (SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS + UMAP_SYMBOLS
                  + UMAP_TRANSFORM_SYMBOLS + COMMUNITY_SYMBOLS + AGGLOM_SYMBOLS + POTENTIAL_SYMBOLS + BUNDLE_SYMBOLS + RENDER_SYMBOLS
-                 + INGEST_SYMBOLS + INSPECT_SYMBOLS):
+                 + INGEST_SYMBOLS + COUNTS_SYMBOLS + INSPECT_SYMBOLS):
         if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy", "nabo_umap_destroy", "nabo_umap_transform_destroy", "nabo_community_destroy",
-                        "nabo_potential_destroy", "nabo_bundle_destroy", "nabo_render_destroy", "nabo_mtx_free"):
+                        "nabo_potential_destroy", "nabo_bundle_destroy", "nabo_render_destroy", "nabo_mtx_free", "nabo_mtxw_free"):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L

@@ -26,6 +26,7 @@
 #include "host_common.h"
 #include "launch.h"
 #include "mtx_host.h"
+#include "mtx_stages.h"
 
 namespace nabo {
 
@@ -479,20 +480,7 @@ int mtx_download(nabo_mtx *h, void *dst, const void *src, size_t bytes)
     return NABO_OK;
 }
 
-// sorted (major, minor) keys and their values in buffer `which` -> the (minor, major) order: ptr over the minors, the
-// majors in the other key buffer's first half (the minors in its second), the values in the value buffer *which names after
-int mtx_transpose_stage(DevBuf key[2], DevBuf val[2], int *which, int64_t nnz, int64_t n_major, int64_t n_minor, void *temp, size_t temp_bytes,
-                        int64_t *d_ptr, uint32_t **d_major, hipStream_t st)
-{
-    uint64_t *k[2] = {key[0].as<uint64_t>(), key[1].as<uint64_t>()};
-    uint32_t *v[2] = {val[0].as<uint32_t>(), val[1].as<uint32_t>()};
-    HIP_TRY(nabo::mtx_sort_launch(k, v, which, nnz, n_major, n_minor, false, temp, temp_bytes, st));
-    uint32_t *major = key[1 - *which].as<uint32_t>(), *minor = major + nnz;
-    HIP_TRY(nabo::mtx_split_launch(k[*which], nnz, minor, major, st));
-    HIP_TRY(nabo::u32_rowptr_launch(minor, nnz, n_minor, d_ptr, st));
-    *d_major = major;
-    return NABO_OK;
-}
+using nabo::mtx_transpose_stage;                                // (mtx_stages.h: shared with counts.hip)
 
 }  // namespace
 
