@@ -116,8 +116,12 @@ int nabo_index_destroy(nabo_index *ix);
  * a bucket of the stream's two copies: every bucket of at least "two_level_sub" unmasked references takes that many of them
  * as sub-anchors and both copies sort its cells by their nearest sub-anchor -- 0 = the default, 1 = caller order, at most
  * 64; the sub-anchors are ranked along their first principal direction, "two_level_sub_rank" = 1: by index; the results
- * are the same bits at every setting, the tile counters are not).  When the two-level stream ran, nabo_index_last_kernel reports its
- * tile counters behind the kernel's name: " [two-level tiles: one-step N, refetched N, two-step N]", summed over the waves.
+ * are the same bits at every setting, the tile counters are not), "bucket_skip" (a workgroup of the stream's main launch
+ * skips the sub-buckets of the references that none of its rows can take a neighbour from, by a rigorous lower bound of the
+ * distances along the directions between the buckets' means: 0 = where the stream runs by default, i.e. "two_level" = 1;
+ * 1 = off; 2 = wherever the stream's main launch runs; the results are the same bits at every setting).  When the two-level
+ * stream ran, nabo_index_last_kernel reports its tile counters behind the kernel's name:
+ * " [two-level tiles: one-step N, refetched N, two-step N, skipped N]", summed over the waves.
  * Unknown names: NABO_E_INVALID.
  * The library reads TWO environment variables, once, in nabo_index_create: NABO_L2_MODE = f32 | f16x3 (which Euclidean /
  * cosine filter runs first; default: the one-product pass) and NABO_CANBERRA_MODE = exact | swar | bits; the sharded
@@ -206,8 +210,9 @@ int nabo_index_last_row_pass(const nabo_index *ix, uint8_t *out, int64_t m);
  * [18] the two-level stream (option "two_level"): 2 the main launch takes it (a query of an index may still decide against it:
  * its probe, or the memory of one that did), 1 the operands are in its slot order only, 0 neither, [19] target rows of the main
  * launch (the tail launch takes the rest; all of them without one) -- as planned for an index that takes the two-level stream
- * or has not decided yet: one that decided against it keeps whole workgroups, [3] x [2] rows.  kernel (optional): the kernel's name as nabo_index_last_kernel reports it. */
-#define NABO_PLAN_FIELDS 20
+ * or has not decided yet: one that decided against it keeps whole workgroups, [3] x [2] rows, [20] 1 where the main launch
+ * skips unreachable sub-buckets of the stream (option "bucket_skip"), else 0.  kernel (optional): the kernel's name as nabo_index_last_kernel reports it. */
+#define NABO_PLAN_FIELDS 21
 int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t k, int32_t drop_first, int32_t n_cand,
                     int32_t n_cu, const char *l2_mode, const char *options, int64_t out[NABO_PLAN_FIELDS], char *kernel,
                     size_t kernel_len);

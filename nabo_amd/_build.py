@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libnabo_knn.so")
-SOURCES = ["api.hip", "plan.hip", "set_ref.hip", "bucket_order.hip", "query.hip", "pack.hip", "l2_topk.hip", "l2q_topk.hip", "l2c_topk.hip", "local_seeds.hip", "refine.hip", "canberra.hip", "canberra_f32.hip", "canberra_bits.hip", "score_null.hip", "csr_build.hip", "comm.hip", "sharded.hip", "multi.hip", "host_graph.hip", "paths.hip", "classify.hip", "de_rank.hip", "pca_project.hip", "pca_fit.hip", "cell_qc.hip", "layout.hip", "umap.hip", "umap_transform.hip", "community.hip", "agglom.hip", "potential.hip", "bundle.hip", "render.hip", "mtx_ingest.hip", "counts.hip"]
+SOURCES = ["api.hip", "plan.hip", "set_ref.hip", "bucket_order.hip", "query.hip", "pack.hip", "l2_topk.hip", "l2q_topk.hip", "l2c_topk.hip", "local_seeds.hip", "bucket_skip.hip", "refine.hip", "canberra.hip", "canberra_f32.hip", "canberra_bits.hip", "score_null.hip", "csr_build.hip", "comm.hip", "sharded.hip", "multi.hip", "host_graph.hip", "paths.hip", "classify.hip", "de_rank.hip", "pca_project.hip", "pca_fit.hip", "cell_qc.hip", "layout.hip", "umap.hip", "umap_transform.hip", "community.hip", "agglom.hip", "potential.hip", "bundle.hip", "render.hip", "mtx_ingest.hip", "counts.hip"]
 # per-file extra flags: -fno-honor-nans for the fp32 score kernel (scores are finite or +inf by construction; without it
 # every fminf tree starts with two v_max canonicalisations, and on gfx950 the fp32 MFMA cannot overlap vector-ALU work);
 # canberra_f32.hip with LLVM's iterative-ilp scheduler: the counting loop is four independent packed-f16 chains per
@@ -27,7 +27,7 @@ FILE_FLAGS = {"l2_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-na
               "l2c_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
               "canberra_f32.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]}
 HEADERS = [os.path.join(CSRC, "knn_common.h"), os.path.join(CSRC, "topk_lists.h"), os.path.join(CSRC, "launch.h"),
-           os.path.join(CSRC, "host_common.h"), os.path.join(CSRC, "de_exact.h"), os.path.join(CSRC, "comm.h"), os.path.join(CSRC, "index.h"), os.path.join(CSRC, "local_seeds.h"), os.path.join(CSRC, "bucket_order.h"), os.path.join(CSRC, "two_level_verdict.h"), os.path.join(CSRC, "l2c_slots.h"), os.path.join(CSRC, "l2c_window.h"), os.path.join(CSRC, "simple_graph.h"), os.path.join(CSRC, "row_chunks.h"), os.path.join(CSRC, "umap_common.h"), os.path.join(HERE, "..", "include", "nabo_knn.h"), os.path.join(HERE, "..", "include", "nabo_graph.h"),
+           os.path.join(CSRC, "host_common.h"), os.path.join(CSRC, "de_exact.h"), os.path.join(CSRC, "comm.h"), os.path.join(CSRC, "index.h"), os.path.join(CSRC, "local_seeds.h"), os.path.join(CSRC, "bucket_order.h"), os.path.join(CSRC, "two_level_verdict.h"), os.path.join(CSRC, "l2c_slots.h"), os.path.join(CSRC, "l2c_window.h"), os.path.join(CSRC, "bucket_skip.h"), os.path.join(CSRC, "simple_graph.h"), os.path.join(CSRC, "row_chunks.h"), os.path.join(CSRC, "umap_common.h"), os.path.join(HERE, "..", "include", "nabo_knn.h"), os.path.join(HERE, "..", "include", "nabo_graph.h"),
            os.path.join(HERE, "..", "include", "nabo_cluster.h"), os.path.join(HERE, "..", "include", "nabo_de.h"),
            os.path.join(HERE, "..", "include", "nabo_pca.h"), os.path.join(HERE, "..", "include", "nabo_pca_fit.h"),
            os.path.join(HERE, "..", "include", "nabo_qc.h"), os.path.join(HERE, "..", "include", "nabo_layout.h"),

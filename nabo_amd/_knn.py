@@ -73,7 +73,7 @@ def knn_devices(X, Y, k, devices, metric=EUCLIDEAN, dist_factor=0.25, ref_mask=N
 
 PLAN_FIELDS = ("first_pass", "geometry", "rows_per_wg", "workgroups_main", "workgroups_tail", "splits", "splits_tail", "lkeep",
                "list_len", "tiles_per_split", "tournament_tiles", "tournament_group", "resident_workgroups", "workgroups",
-               "rows_padded", "operand_steps", "pieces", "local_seed_buckets", "two_level", "rows_main")
+               "rows_padded", "operand_steps", "pieces", "local_seed_buckets", "two_level", "rows_main", "bucket_skip")
 
 
 def query_plan(n_ref, g, m, k, metric=EUCLIDEAN, drop_first=False, n_cand=0, n_cu=256, l2_mode=None, options=None):
@@ -177,12 +177,13 @@ class KnnIndex:
         _lib.check(_lib.lib().nabo_index_last_passes(self._h, ps))
         # the two-level stream's tile counters, summed over the waves of its launch (0 when the query did not take it): the
         # library reports them behind the kernel's name
-        tl = re.search(r"\[two-level tiles: one-step (\d+), refetched (\d+), two-step (\d+)\]", self.last_kernel())
-        one, refetched, two = (int(v) for v in tl.groups()) if tl else (0, 0, 0)
+        tl = re.search(r"\[two-level tiles: one-step (\d+), refetched (\d+), two-step (\d+), skipped (\d+)\]", self.last_kernel())
+        one, refetched, two, skipped = (int(v) for v in tl.groups()) if tl else (0, 0, 0, 0)
         return {"ms_pack": ms[0], "ms_topk": ms[1], "ms_refine": ms[2], "ms_fallback": ms[3], "ms_total": ms[4],
                 "fallback_rows": int(cn[0]), "splits": int(cn[1]), "list_len": int(cn[2]), "workgroups": int(cn[3]),
                 "seeded_pass_rows": int(ps[0]), "second_pass_rows": int(ps[1]), "wide_list_rows": int(ps[2]),
-                "two_level_one_step_tiles": one, "two_level_refetched_tiles": refetched, "two_level_two_step_tiles": two}
+                "two_level_one_step_tiles": one, "two_level_refetched_tiles": refetched, "two_level_two_step_tiles": two,
+                "two_level_skipped_tiles": skipped}
 
     PASS_NAMES = ("one_product", "seeded", "second_filter", "wide_lists", "exact", "canberra_filter")
 

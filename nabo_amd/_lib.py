@@ -331,7 +331,8 @@ def so_digest():
 # the launch logic and the compiler flags
 KERNEL_SOURCES = {
     "euclid": ["l2c_topk.hip", "l2q_topk.hip", "topk_lists.h", "knn_common.h", "pack.hip", "index.h", "plan.hip", "set_ref.hip", "query.hip", "api.hip", "_build.py",
-               "local_seeds.hip", "local_seeds.h", "l2c_slots.h", "l2c_window.h", "bucket_order.hip", "bucket_order.h", "two_level_verdict.h"],
+               "local_seeds.hip", "local_seeds.h", "l2c_slots.h", "l2c_window.h", "bucket_order.hip", "bucket_order.h", "two_level_verdict.h",
+               "bucket_skip.hip", "bucket_skip.h"],
     "canberra": ["canberra_f32.hip", "canberra_bits.hip", "knn_common.h", "index.h", "plan.hip", "set_ref.hip", "query.hip", "api.hip", "_build.py"],
 }
 

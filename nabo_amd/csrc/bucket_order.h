@@ -37,6 +37,13 @@ struct BucketRefs {
     // rows with the same tables
     DevBuf sub_anchors, sub_norms, sub_ranks;
     int sub_count = 1, sub_rank_rule = 0;
+    // what a workgroup of the ordered main launch skips by (bucket_skip.h), built behind the ordered copy and with it:
+    // the groups of the stream -- sub-bucket r of bucket b is group b * sub_count + r -- as first position, size and tiles
+    // [skip_groups] int32 each; the buckets' means [buckets][g] and the unit directions between them, by_from [b][g][b'] and
+    // by_to [b'][g][b], float64; ymin [buckets][skip_groups] floats
+    DevBuf skip_first, skip_count, skip_t0, skip_t1, skip_mean_parts, skip_means, skip_by_from, skip_by_to, skip_ymin;
+    int skip_groups = 0;
+    bool skip_built = false;
 };
 
 // The SCRATCH side (nabo_index::Workspace).  The reference build and the queries use the SAME scratch, on the same stream:
@@ -51,7 +58,8 @@ struct BucketScratch {
     // tournament, the probe and the ordered main launch read; nabo_index_stream_order reads the map afterwards):
     struct Rows {
         DevBuf ordered, map, column_ranges;      // the bucket-ordered target tiles, [position] = row, the columns' tile ranges
-        DevBuf tile_counters;                    // the two-level launch's tile counters [3] (l2c_topk.hip)
+        DevBuf tile_counters;                    // the two-level launch's tile counters [4] (l2c_topk.hip)
+        DevBuf runs;                             // the run lists of the main launch's workgroups (bucket_skip.h), where it skips
         bool streamed = false;                   // the last first pass ran the ordered main launch ...
         int64_t positions = 0;                   // ... over this many positions of `ordered`
     } rows;

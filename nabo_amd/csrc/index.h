@@ -53,6 +53,9 @@ struct Options {
     // the order of the cells INSIDE a bucket of the stream's two copies (local_seeds.h): sub-anchors per bucket (0: the
     // default, 1: caller order, at most 64) and how they are ranked (0: along their first principal direction, 1: by index)
     int two_level_sub = 0, two_level_sub_rank = 0;
+    // the ordered main launch skips the sub-buckets its workgroups' rows cannot reach (bucket_skip.h): 0 where the planner
+    // took the stream at its default setting (two_level = 1), 1 off, 2 wherever the ordered main launch runs
+    int bucket_skip = 0;
 };
 bool option_set(Options &o, const char *name, int64_t value);
 
@@ -120,6 +123,7 @@ struct L2Plan {
     bool on_l2c = false;                 // ... on the l2c kernel (geo: its geometry)
     bool slots2 = false;                 // ... in the two-level slot order (two_level_slots: a property of the index)
     bool tl_main = false;                // the main launch streams bucket-ordered operands with the one-step loop (l2c_topk.hip)
+    bool tl_skip = false;                // ... and skips the sub-buckets a workgroup's rows cannot reach (bucket_skip.h)
     bool r1 = false;                     // fp32 filter: one row-block per wave
     int geo = -1, kcq = 0, cslack = 0;
     int rows_per_wg = 256, wg_per_cu = 1, lkeep_max = 32, lkeep = 16, want = 16;
@@ -140,6 +144,7 @@ bool two_level_slots(const IndexShape &sh);
 void shape_refresh(IndexShape &sh);          // kc1 after a change of options (g = 29 under option two_level = 2)
 void lseed_params(const IndexShape &sh, int *C, int *cap);
 int lseed_sub_param(const IndexShape &sh);      // sub-anchors per bucket of the two-level stream's copies (1: no sub-order)
+bool bskip_wanted(const IndexShape &sh);        // the skip tables are built with the ordered copy (option bucket_skip, bucket_skip.h)
 bool lseed_applies(const IndexShape &sh, const L2Plan &P, int S, int64_t rows);
 
 struct CbPlan {

@@ -37,6 +37,7 @@
 #include <hip/hip_fp16.h>
 
 #define NABO_DRAIN_CALL 1             // topk_lists.h: this file drains its lists through a real call
+#include "bucket_skip.h"
 #include "knn_common.h"
 #include "l2c_window.h"
 #include "launch.h"
@@ -333,7 +334,8 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                                                           const uint32_t *__restrict__ ref_map,
                                                           unsigned long long *__restrict__ tl_stats, int tl_share,
                                                           int tl_stretch, const int32_t *__restrict__ tl_bend, int tl_nbend,
-                                                          int tl_burst, int tl_window, int tl_check)
+                                                          int tl_burst, int tl_window, int tl_check,
+                                                          const int32_t *__restrict__ tl_runs)
 {
     // TWO-LEVEL stream (geometry B on two operand steps; row_map != null selects it at run time, every other launch of this
     // instantiation runs the plain loop below): operands in the two-level slot order (l2c_slots.h), targets AND references
@@ -432,7 +434,7 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
     }
     uint32_t scnt = 0;
     const int t_begin = split * tiles_per_split;
-    const int t_end = t_begin + tiles_per_split;
+    int t_end = t_begin + tiles_per_split;              // (a launch with a run list: the end of the run the wave is in)
     lists_init<C>(wl, lkeep, tau0, (uint32_t)t_begin * 32u);
     if (ordered) {
         uint2 *rows = C::rows(wl);
@@ -712,7 +714,21 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                     win_read();
                 }
             };
+            // THE RUN LIST (bucket_skip.h; ordered launches that bring one): the stretches of the stream this workgroup's rows can
+            // take anything from, in order -- what lies between them is skipped.  A run is run like the whole stream was: it
+            // ends through the segments' filter site, the next one starts with its first tile's load; t_end is the run's end
+            // to every loop and to tile_ptr.  Wave-uniform scalar loads outside both hot loops; all four waves of a workgroup
+            // take the same runs, so the progress window sees them move together.  The bucket cursor of the mode control
+            // moves past every end <= its tile and survives the jumps.
+            // (the tiles skipped are the split's tiles less the ones run: no count is kept along the way)
+            const int32_t *runs = ordered && tl_runs ? tl_runs + (int64_t)(int)blockIdx.x * BSKIP_RUN_INTS : nullptr;
             bool one_step = ordered;
+            for (;; runs += 2) {
+            if (runs) {
+                t = __builtin_amdgcn_readfirstlane(runs[0]);
+                t_end = __builtin_amdgcn_readfirstlane(runs[1]);
+                if (t >= t_end) break;                   // the sentinel
+            }
             while (t < t_end) {
                 seg_t0 = t;
                 if (one_step) {
@@ -752,11 +768,14 @@ __global__ __launch_bounds__(64 * WAVES, WPS) void l2c_topk_kernel(const unsigne
                 reset(accO);
                 one_step = !one_step;
             }
+            if (!runs) break;
+            }
             if (win_on && lane == 0) wslot[wave] = L2C_WIN_DONE;        // out of the stream: nobody waits for the flush
             if (tl_stats && lane == 0) {
                 atomicAdd(tl_stats, (unsigned long long)n_one);
                 atomicAdd(tl_stats + 1, (unsigned long long)n_ref);
                 atomicAdd(tl_stats + 2, (unsigned long long)n_two);
+                if (tl_runs) atomicAdd(tl_stats + 3, (unsigned long long)((uint32_t)tiles_per_split - n_one - n_two));
             }
             lists_flush<C, EPL, NB>(wl, scnt, ltile0 * 32, split, S, lkeep, tauv, cand_idx, cand_key, cand_tau, row_map, ref_map);
             return;
@@ -979,7 +998,7 @@ static hipError_t claunch_geo(const unsigned char *Xpk, const unsigned char *Ypk
                        tau_row0, ord ? ord->row_map : nullptr, ord ? ord->ref_map : nullptr, ord ? ord->stats : nullptr,
                        ord ? ord->share_pct : 0, ord ? ord->stretch : 0, ord ? ord->bucket_end : nullptr,
                        ord && ord->bucket_end ? ord->nbucket : 0, ord ? ord->burst : 0, ord ? l2c_win_window(ord->window) : 0,
-                       ord ? ord->check : 0);
+                       ord ? ord->check : 0, ord ? ord->runs : nullptr);
     return hipGetLastError();
 }
 

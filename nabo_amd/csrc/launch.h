@@ -57,14 +57,17 @@ void l2q_topk_geometry(int kc, int *rows_per_wg, int *wg_per_cu, int *lkeep_max)
 // A TWO-LEVEL launch (geometry B, two steps, operands in the two-level slot order): targets and references are bucket-ordered
 // copies -- position p of the targets is the launch's row row_map[p] (0xFFFFFFFF: padding), position j of the stream is
 // reference ref_map[j]; lists and seeds are indexed by the launch's rows, emitted candidates are reference indices.
-// stats [3] (may be null): tiles run one-step, tiles of those refetched inside the loop (a segment's last tile, completed
-// unconditionally, is not counted), tiles run two-step, summed over the waves.
+// stats [4] (may be null): tiles run one-step, tiles of those refetched inside the loop (a segment's last tile, completed
+// unconditionally, is not counted), tiles run two-step, tiles skipped (`runs`), summed over the waves.
 // share_pct / burst: the mode control's refetch share and credit (0: the kernel's defaults).  bucket_end [nbucket] (may be
 // null): the reference buckets' ends in tiles of the stream, non-decreasing (lseed_bucket_ends) -- the mode control keeps its
 // account per bucket and runs two-step to a bucket's end.  stretch > 0, or no table: the control before that one, one
 // account per one-step segment and blind two-step stretches, the first of `stretch` tiles (0: 64).
 // window / check: the workgroup's progress window (l2c_window.h) -- a wave more than `window` tiles ahead of the slowest
 // live wave of its workgroup waits, looking every `check` tiles (0: the defaults; window < 0: none).
+// runs (may be null): per workgroup BSKIP_RUN_INTS int32 (bucket_skip.h), the stretches [begin, end) of the stream the
+// workgroup runs, in order, even bounds, ended by the pair (0, 0) -- the tiles between them are skipped and counted in
+// stats [3].  Null: the whole stream.
 struct L2cOrdered {
     const uint32_t *row_map, *ref_map;
     unsigned long long *stats;
@@ -72,6 +75,7 @@ struct L2cOrdered {
     const int32_t *bucket_end;
     int nbucket, burst;
     int window, check;
+    const int32_t *runs;
 };
 int l2c_pick_kc(int g);
 int l2c_geometry(int kc, int lkeep_want, int pin);
@@ -114,6 +118,16 @@ hipError_t lseed_sub_sort_launch(int kc, bool is_ref, const unsigned char *pk, i
 hipError_t lseed_sub_move_launch(int kc, const unsigned char *src, int64_t npos, const uint32_t *map1, const uint32_t *key2,
                                  const uint32_t *blockoff, const int64_t *sublay, const unsigned char *pad_src, int64_t pad_cell, int C,
                                  const int64_t *lay, unsigned char *dst, uint32_t *dst_map, hipStream_t st);
+// the sub-buckets a workgroup of the ordered main launch cannot need (bucket_skip.hip; the rule: bucket_skip.h)
+size_t bskip_dir_bytes(int C, int g);
+size_t bskip_mean_part_bytes(int C, int g);
+hipError_t bskip_refs_launch(const double *Y, const double *centre, double scale, int g, int C, int S, const int64_t *lay,
+                             const uint32_t *ref_cnt, const int64_t *sublay, const uint32_t *subtot, const uint32_t *ref_map,
+                             int32_t *first, int32_t *count, int32_t *t0, int32_t *t1, double *mean_parts, double *mean, double *by_from,
+                             double *by_to, float *ymin, hipStream_t st);
+hipError_t bskip_runs_launch(const double *X, const double *centre, double scale, int g, int C, int S, const uint32_t *row_map,
+                             const uint32_t *key, const float *tau, const double *by_from, const float *ymin, const int32_t *t0,
+                             const int32_t *t1, int64_t t_end, int64_t wgs, int32_t *runs, hipStream_t st);
 
 // list merges, float64 re-evaluation, exact kernels and row helpers (refine.hip)
 hipError_t merge_lists_launch(const uint32_t *cand_idx, const float *cand_key, const float *cand_tau, int64_t rows, int S, int L,

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "bucket_skip.h"
 #include "index.h"
 #include "l2c_slots.h"
 #include "l2c_window.h"
@@ -54,8 +55,19 @@ static const OptionName SUB_ORDER_OPTION_NAMES[] = {
     {"two_level_sub", &Options::two_level_sub}, {"two_level_sub_rank", &Options::two_level_sub_rank},
 };
 
+// The skip of unreachable sub-buckets in the ordered main launch (bucket_skip.h).  A table of its own:
+// tests/test_bucket_skip_gpu.py runs its values against the oracle.
+static const OptionName BUCKET_SKIP_OPTION_NAMES[] = {
+    {"bucket_skip", &Options::bucket_skip},
+};
+
 bool option_set(Options &o, const char *name, int64_t value)
 {
+    for (const OptionName &e : BUCKET_SKIP_OPTION_NAMES)
+        if (strcmp(e.name, name) == 0) {            // clamped: 0 .. 2
+            o.*(e.field) = (int)(value < 0 ? 0 : value > 2 ? 2 : value);
+            return true;
+        }
     for (const OptionName &e : SUB_ORDER_OPTION_NAMES)
         if (strcmp(e.name, name) == 0) {            // clamped: sub-anchors 0 .. LSEED_MAX_SUB, the ranking rule 0 .. 1
             const int64_t hi = e.field == &Options::two_level_sub ? LSEED_MAX_SUB : 1;
@@ -123,6 +135,16 @@ void lseed_params(const IndexShape &sh, int *C, int *cap)
 
 // Sub-anchors per bucket of the two-level stream's copies: only where the stream's operands exist
 int lseed_sub_param(const IndexShape &sh) { return two_level_slots(sh) ? lseed_sub_count(sh.opt.two_level_sub) : 1; }
+
+// The skip tables are built with the ordered copy wherever a main launch of this index could skip (bskip_planned) and the
+// tables can be built at all (bskip_buildable): the ONE decision ensure_local_seeds and the planner share
+bool bskip_wanted(const IndexShape &sh)
+{
+    int C = 0, cap = 0;
+    lseed_params(sh, &C, &cap);
+    return C > 0 && two_level_slots(sh) && bskip_planned(sh.opt.bucket_skip, true, sh.opt.two_level) &&
+           bskip_buildable(lseed_ordered_tiles(sh.ref_tiles, C), sh.g);
+}
 
 // Local seeds serve a launch of the first one-product pass with ONE reference split (a seed bounds the lkeep-th smallest
 // score over a split's own references only if the sample lies inside it: every bucket does for S = 1), where the tournament
@@ -363,6 +385,7 @@ int plan_l2(const IndexShape &sh, const PassCtx &ctx, int64_t m, int k, int drop
         P->tl_main = P->slots2 && on_l2c && geo == 1 && kcq == 4 && ctx.first() && !cand_mode && gx_main > 0 &&
                      lseed_applies(sh, *P, S, rows_main) && !(gx_tail > 0 && lseed_applies(sh, *P, S2, m - rows_main));
     }
+    P->tl_skip = P->tl_main && bskip_wanted(sh) && rows_per_wg == BSKIP_WG_ROWS;
     // WHOLE ROUNDS for the two-level main launch.  It runs its rows as POSITIONS of the bucket-ordered copy:
     // lseed_columns(rows, C) columns of 128, every bucket padding its rows to whole columns -- gx_main workgroups' worth of
     // rows are up to (C + 1) x 128 positions more, a few workgroups of one more round, each streaming the whole reference set
@@ -520,6 +543,7 @@ int nabo_query_plan(int64_t n_ref, int32_t g, int32_t metric, int64_t m, int32_t
         out[19] = rows_main;
     }
     out[18] = P.tl_main ? 2 : P.slots2 ? 1 : 0;      // two-level: 2 the main launch streams one-step, 1 the slot order only
+    out[20] = P.tl_skip ? 1 : 0;                     // ... and skips the sub-buckets a workgroup's rows cannot reach
     if (kernel && kernel_len) snprintf(kernel, kernel_len, "%s", P.kernel);
     return NABO_OK;
 }

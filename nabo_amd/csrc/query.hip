@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "bucket_skip.h"
 #include "index.h"
 #include "local_seeds.h"
 
@@ -33,6 +34,7 @@ static int note_row_pass(nabo_index *ix, const PassCtx &ctx, const uint32_t *d_r
 // What every route of a query reads (query_body stages it), and what the route leaves for finish_query.
 struct Query {
     const double *dX = nullptr;      // [m, g] targets on the device
+    const double *dXp = nullptr;     // ... as the Euclidean / cosine filter packs them (cosine: the unit rows)
     int64_t m = 0;
     int k = 0, drop = 0, kk = 0;     // kk = k + drop
     int epl = 1, L = 32;             // emitted candidate lists hold L = 32 epl entries
@@ -199,7 +201,8 @@ static int probe_stream(nabo_index *ix, const L2Plan &P, L2Part &p, const L2Seed
     unsigned long long probe[3] = {0, 0, 0};
     L2cOrdered pord = ord;
     pord.window = -1;
-    HIP_TRY(hipMemsetAsync(in.tile_counters.p, 0, sizeof(probe), st));
+    pord.runs = nullptr;
+    HIP_TRY(hipMemsetAsync(in.tile_counters.p, 0, 4 * sizeof(unsigned long long), st));
     HIP_TRY(l2c_topk_launch(P.kcq, P.geo, in.ordered.as<unsigned char>(), l2.buckets.ordered.as<unsigned char>(), TL_PROBE_TILES, 1,
                             TL_PROBE_WORKGROUPS, 0, P.lkeep, p.idx->as<uint32_t>(), nullptr, p.tau->as<float>(), l2.buckets.ordered_tiles, st,
                             prow, seed.tau, seed.stride, 0, &pord));
@@ -220,7 +223,7 @@ static int stream_launch(nabo_index *ix, const L2Plan &P, L2Part &p, const L2See
     auto &l2 = ix->ref.l2;
     auto &in = ix->ws.buckets.rows;
     hipStream_t st = ix->stream;
-    HIP_TRY(hipMemsetAsync(in.tile_counters.p, 0, 3 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(in.tile_counters.p, 0, 4 * sizeof(unsigned long long), st));
     HIP_TRY(l2c_topk_launch(P.kcq, P.geo, in.ordered.as<unsigned char>(), l2.buckets.ordered.as<unsigned char>(), (int)l2.buckets.ordered_tiles, 1,
                             (int)((prow + P.rows_per_wg - 1) / P.rows_per_wg), 0, P.lkeep, p.idx->as<uint32_t>(),
                             p.merge ? p.key->as<float>() : nullptr, p.tau->as<float>(), l2.buckets.ordered_tiles, st, prow, seed.tau,
@@ -251,14 +254,26 @@ static int main_launch_ordered(nabo_index *ix, const Query &q, const L2Plan &P, 
     auto &in = ix->ws.buckets.rows;
     int rc;
     const int64_t prow = ordered_positions(ix, p.end(q.m) - p.row0);
-    if ((rc = in.tile_counters.reserve(3 * sizeof(unsigned long long)))) return rc;
-    const L2cOrdered ord = {in.map.as<uint32_t>(), l2.buckets.ordered_map.as<uint32_t>(), in.tile_counters.as<unsigned long long>(),
+    if ((rc = in.tile_counters.reserve(4 * sizeof(unsigned long long)))) return rc;
+    L2cOrdered ord = {in.map.as<uint32_t>(), l2.buckets.ordered_map.as<uint32_t>(), in.tile_counters.as<unsigned long long>(),
                             sh.opt.two_level_share, sh.opt.two_level_stretch, l2.buckets.bucket_ends.as<int32_t>(), l2.buckets.buckets,
-                            sh.opt.two_level_burst, sh.opt.two_level_window, sh.opt.two_level_check};
-    if (tl_probe_due(l2.stream_verdict, sh.opt.two_level, (prow + P.rows_per_wg - 1) / P.rows_per_wg, l2.buckets.ordered_tiles) &&
-        (rc = probe_stream(ix, P, p, seed, prow, ord)))
+                            sh.opt.two_level_burst, sh.opt.two_level_window, sh.opt.two_level_check, nullptr};
+    const int64_t wgs = (prow + P.rows_per_wg - 1) / P.rows_per_wg;
+    if (tl_probe_due(l2.stream_verdict, sh.opt.two_level, wgs, l2.buckets.ordered_tiles) && (rc = probe_stream(ix, P, p, seed, prow, ord)))
         return rc;
-    return l2.stream_verdict.streams() ? stream_launch(ix, P, p, seed, prow, ord) : plain_launch(ix, q, P, p, seed);
+    if (!l2.stream_verdict.streams()) return plain_launch(ix, q, P, p, seed);
+    // The run lists (bucket_skip.h): which stretches of the stream each workgroup's rows can take anything from, from the
+    // seeds the tournament just wrote and the buckets the rows' sort left in its keys (no sort runs between the two: a plan
+    // with tl_main has no tail launch with local seeds).  On the query's stream, no host wait.
+    const BucketRefs &b = l2.buckets;
+    if (P.tl_skip && b.skip_built && seed.tau && seed.stride == 1) {
+        if ((rc = in.runs.reserve((size_t)wgs * BSKIP_RUN_INTS * sizeof(int32_t)))) return rc;
+        HIP_TRY(bskip_runs_launch(q.dXp + (size_t)p.row0 * sh.g, l2.centre.as<double>(), l2.hscale, sh.g, b.buckets, b.sub_count, in.map.as<uint32_t>(),
+                                  ix->ws.buckets.keys.as<uint32_t>(), seed.tau, b.skip_by_from.as<double>(), b.skip_ymin.as<float>(),
+                                  b.skip_t0.as<int32_t>(), b.skip_t1.as<int32_t>(), b.ordered_tiles, wgs, in.runs.as<int32_t>(), ix->stream));
+        ord.runs = in.runs.as<int32_t>();
+    }
+    return stream_launch(ix, P, p, seed, prow, ord);
 }
 
 // The filter kernels of a pass, main launch then tail: the one-product kernel behind its tournament seeds (l2c_topk.hip),
@@ -434,6 +449,7 @@ static int query_l2(nabo_index *ix, const PassCtx &ctx, Query &q)
         HIP_TRY(normalise_rows_launch(q.dX, m, g, ws.xnbuf.as<double>(), st));
         dXp = ws.xnbuf.as<double>();
     }
+    q.dXp = dXp;
     L2Plan P;
     if ((rc = plan_l2(sh, ctx, m, q.k, q.drop, q.cand_mode, &P))) return rc;
     if (ctx.first()) {
@@ -512,7 +528,7 @@ static int query_l2(nabo_index *ix, const PassCtx &ctx, Query &q)
         return NABO_OK;
     }
     HIP_TRY(hipMemcpyAsync(&q.n_fail, ws.failcnt.p, sizeof(q.n_fail), hipMemcpyDeviceToHost, st));
-    unsigned long long tl_tiles[3] = {0, 0, 0};
+    unsigned long long tl_tiles[4] = {0, 0, 0, 0};
     const bool tl_ran = ctx.first() && ws.buckets.rows.streamed;
     if (tl_ran) HIP_TRY(hipMemcpyAsync(tl_tiles, ws.buckets.rows.tile_counters.p, sizeof(tl_tiles), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -520,9 +536,10 @@ static int query_l2(nabo_index *ix, const PassCtx &ctx, Query &q)
         // the two-level launch's tile counters: into the record (the kernel string carries them to nabo_index_last_kernel),
         // and the memory of a poor outcome: the next queries take the caller-order stream (two_level_verdict.h)
         const size_t len = strlen(ix->last.kernel);
-        snprintf(ix->last.kernel + len, sizeof(ix->last.kernel) - len, " [two-level tiles: one-step %lld, refetched %lld, two-step %lld]",
-                 (long long)tl_tiles[0], (long long)tl_tiles[1], (long long)tl_tiles[2]);
-        if (tl_launch_says_no(m, sh.opt.coarse_adapt, tl_tiles[0], tl_tiles[2])) l2.stream_verdict.give(TwoLevelVerdict::CALLER_ORDER);
+        snprintf(ix->last.kernel + len, sizeof(ix->last.kernel) - len, " [two-level tiles: one-step %lld, refetched %lld, two-step %lld, skipped %lld]",
+                 (long long)tl_tiles[0], (long long)tl_tiles[1], (long long)tl_tiles[2], (long long)tl_tiles[3]);
+        // (a skipped tile is a tile that did not need its second step: it counts with the one-step tiles)
+        if (tl_launch_says_no(m, sh.opt.coarse_adapt, tl_tiles[0] + tl_tiles[3], tl_tiles[2])) l2.stream_verdict.give(TwoLevelVerdict::CALLER_ORDER);
     }
     if (P.use_1 && q.n_fail > 0) {
         // Rows this one-product pass could not certify: from level 0 on the l2c kernel to the SEEDED one-product pass

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "bucket_skip.h"
 #include "index.h"
 #include "local_seeds.h"
 
@@ -45,7 +46,7 @@ int ensure_packed(nabo_index *ix, int want)
         int lc = 0, lcap = 0;
         lseed_params(sh, &lc, &lcap);
         l2.buckets.runs_room = (int64_t)lc * (lcap / 32);
-        l2.buckets.runs_built = l2.buckets.ordered_built = false;
+        l2.buckets.runs_built = l2.buckets.ordered_built = l2.buckets.skip_built = false;
         l2.slots2 = two_level_slots(sh);
         if ((rc = l2.ycpk1.reserve((size_t)(sh.ref_tiles_alloc + l2.buckets.runs_room) * sh.kc1 * 1024 + 128))) return rc;
         l2.hscale = scale = std::ldexp(1.0, e2 + 12);
@@ -98,13 +99,15 @@ int ensure_local_seeds(nabo_index *ix)
     const int S = lseed_sub_param(sh), srank = sh.opt.two_level_sub_rank;
     // (a sub-order asked for since the copy was built, or another one: the ordered copy is built again)
     if (b.ordered_built && (b.sub_count != S || (S > 1 && b.sub_rank_rule != srank))) b.ordered_built = false;
+    // (the skip tables where an option asks for them now and the copy was built without)
+    if (b.ordered_built && !b.skip_built && bskip_wanted(sh)) b.ordered_built = false;
     if (b.runs_built && b.buckets == C && b.cap == cap && l2.packed_c1 && (b.ordered_built || !l2.slots2 || !l2.stream_verdict.streams()))
         return NABO_OK;
     if (!l2.packed_c1 || b.runs_room < (int64_t)C * (cap / 32)) {           // (options changed since the pack: room for the runs)
         l2.packed_c1 = false;
         if ((rc = ensure_packed(ix, 2))) return rc;
     }
-    b.runs_built = b.ordered_built = false;
+    b.runs_built = b.ordered_built = b.skip_built = false;
     b.buckets = C;
     b.cap = cap;
     if ((rc = b.anchors.reserve(lseed_anchor_bytes(sh.kc1, C))) || (rc = b.bucket_count.reserve((size_t)C * sizeof(uint32_t)))) return rc;
@@ -147,6 +150,24 @@ int ensure_local_seeds(nabo_index *ix)
     if ((rc = bucket_sort(ix, sort))) return rc;
     b.ordered_tiles = ot;
     b.ordered_built = true;
+    // What the main launch's workgroups skip by (bucket_skip.h), from the layouts the copy was just sorted with -- scratch the
+    // next sort overwrites -- and the references' float64 rows; on the same stream, behind the sub-order.
+    if (bskip_wanted(sh)) {
+        const BucketScratch &ws = ix->ws.buckets;
+        const int G = C * S;
+        const size_t gi = (size_t)G * sizeof(int32_t);
+        if ((rc = b.skip_first.reserve(gi)) || (rc = b.skip_count.reserve(gi)) || (rc = b.skip_t0.reserve(gi)) || (rc = b.skip_t1.reserve(gi)) ||
+            (rc = b.skip_means.reserve((size_t)C * sh.g * sizeof(double))) || (rc = b.skip_mean_parts.reserve(bskip_mean_part_bytes(C, sh.g))) || (rc = b.skip_by_from.reserve(bskip_dir_bytes(C, sh.g))) ||
+            (rc = b.skip_by_to.reserve(bskip_dir_bytes(C, sh.g))) || (rc = b.skip_ymin.reserve((size_t)C * G * sizeof(float))))
+            return rc;
+        HIP_TRY(bskip_refs_launch(l2.dYp, l2.centre.as<double>(), l2.hscale, sh.g, C, S, ws.layout.as<int64_t>(), b.bucket_count.as<uint32_t>(),
+                                  S > 1 ? ws.sub_layout.as<int64_t>() : nullptr, S > 1 ? ws.sub_totals.as<uint32_t>() : nullptr,
+                                  b.ordered_map.as<uint32_t>(), b.skip_first.as<int32_t>(), b.skip_count.as<int32_t>(), b.skip_t0.as<int32_t>(),
+                                  b.skip_t1.as<int32_t>(), b.skip_mean_parts.as<double>(), b.skip_means.as<double>(), b.skip_by_from.as<double>(), b.skip_by_to.as<double>(),
+                                  b.skip_ymin.as<float>(), st));
+        b.skip_groups = G;
+        b.skip_built = true;
+    }
     return NABO_OK;
 }
 

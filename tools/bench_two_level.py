@@ -4,7 +4,8 @@ where the stream gains nothing: the mode control has to keep its cost to the pro
     python tools/bench_two_level.py [steps] [m n g k] [--cloud] [name=value,...;name=value,...;...]
 Configurations are separated by ';' and run in the order given, the first one again at the end (the spread).  The mode
 control's knobs are index options like any other: "two_level_burst=3,two_level_share=25" is the per-bucket control with that
-account, "two_level_stretch=64" the control before it."""
+account, "two_level_stretch=64" the control before it, "bucket_skip=1" the stream without the skip of unreachable sub-buckets
+(DESIGN.md 4.1f).  Tile counters: one-step, refetched, two-step, skipped; ms_pack holds the reference-side build."""
 import json
 import os
 import sys
@@ -16,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nabo_amd import _knn, _lib  # noqa: E402
 from nabo_amd._synth import pca_like  # noqa: E402
 
+TILE_KEYS = ("two_level_one_step_tiles", "two_level_refetched_tiles", "two_level_two_step_tiles", "two_level_skipped_tiles")
 cloud = "--cloud" in sys.argv
 if cloud:
     sys.argv.remove("--cloud")
@@ -49,9 +51,9 @@ for opts in cfgs + cfgs[:1]:
     ms = (time.perf_counter() - t0) * 1e3 / steps
     mean = lambda key: sum(s[key] for s in st[1:]) / len(st[1:])      # noqa: E731
     print(json.dumps({"data": "cloud" if cloud else "pca_like", "options": opts, "ms_per_step": round(ms, 3),
-                      "ms_topk": round(mean("ms_topk"), 3), "ms_refine": round(mean("ms_refine"), 3),
+                      "ms_pack": round(mean("ms_pack"), 3), "ms_topk": round(mean("ms_topk"), 3), "ms_refine": round(mean("ms_refine"), 3),
                       "seeded_pass_rows": st[-1]["seeded_pass_rows"],
-                      "tiles_first_step": [st[0][a] for a in ("two_level_one_step_tiles", "two_level_refetched_tiles", "two_level_two_step_tiles")],
-                      "tiles_last_step": [st[-1][a] for a in ("two_level_one_step_tiles", "two_level_refetched_tiles", "two_level_two_step_tiles")]}),
+                      "tiles_first_step": [st[0][a] for a in TILE_KEYS],
+                      "tiles_last_step": [st[-1][a] for a in TILE_KEYS]}),
           flush=True)
     ix.close()
