@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libnabo_knn.so")
-SOURCES = ["api.hip", "plan.hip", "set_ref.hip", "bucket_order.hip", "query.hip", "pack.hip", "l2_topk.hip", "l2q_topk.hip", "l2c_topk.hip", "local_seeds.hip", "bucket_skip.hip", "refine.hip", "canberra.hip", "canberra_f32.hip", "canberra_bits.hip", "score_null.hip", "csr_build.hip", "comm.hip", "sharded.hip", "multi.hip", "host_graph.hip", "paths.hip", "classify.hip", "de_rank.hip", "pca_project.hip", "pca_fit.hip", "cell_qc.hip", "layout.hip", "umap.hip", "umap_transform.hip", "community.hip", "agglom.hip", "potential.hip", "bundle.hip", "render.hip", "mtx_ingest.hip", "counts.hip"]
+SOURCES = ["api.hip", "plan.hip", "set_ref.hip", "bucket_order.hip", "query.hip", "pack.hip", "l2_topk.hip", "l2q_topk.hip", "l2c_topk.hip", "local_seeds.hip", "bucket_skip.hip", "refine.hip", "canberra.hip", "canberra_f32.hip", "canberra_bits.hip", "score_null.hip", "csr_build.hip", "comm.hip", "sharded.hip", "multi.hip", "host_graph.hip", "paths.hip", "classify.hip", "de_rank.hip", "pca_project.hip", "pca_fit.hip", "cell_qc.hip", "layout.hip", "umap.hip", "umap_transform.hip", "community.hip", "agglom.hip", "potential.hip", "bundle.hip", "render.hip", "mtx_ingest.hip", "counts.hip", "csv_ingest.hip"]
 # per-file extra flags: -fno-honor-nans for the fp32 score kernel (scores are finite or +inf by construction; without it
 # every fminf tree starts with two v_max canonicalisations, and on gfx950 the fp32 MFMA cannot overlap vector-ALU work);
 # canberra_f32.hip with LLVM's iterative-ilp scheduler: the counting loop is four independent packed-f16 chains per
@@ -36,7 +36,8 @@ HEADERS = [os.path.join(CSRC, "knn_common.h"), os.path.join(CSRC, "topk_lists.h"
            os.path.join(HERE, "..", "include", "nabo_potential.h"), os.path.join(HERE, "..", "include", "nabo_bundle.h"),
            os.path.join(CSRC, "bundle_view.h"), os.path.join(HERE, "..", "include", "nabo_render.h"),
            os.path.join(CSRC, "mtx_host.h"), os.path.join(HERE, "..", "include", "nabo_ingest.h"),
-           os.path.join(CSRC, "mtx_stages.h"), os.path.join(CSRC, "counts_host.h"), os.path.join(HERE, "..", "include", "nabo_counts.h")]
+           os.path.join(CSRC, "mtx_stages.h"), os.path.join(CSRC, "counts_host.h"), os.path.join(HERE, "..", "include", "nabo_counts.h"),
+           os.path.join(CSRC, "csv_number.h"), os.path.join(CSRC, "csv_host.h"), os.path.join(HERE, "..", "include", "nabo_csv.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "--offload-arch=" + ARCH, "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-Wno-inline-asm"]

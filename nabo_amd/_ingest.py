@@ -236,12 +236,13 @@ def mtx_to_h5(in_dir, h5_fn, batch_size=10000, value_dtype=np.int64):
     return None
 
 
-def write_dataset_file(h5_fn, m, genes, cells, value_dtype=np.int64):
+def write_dataset_file(h5_fn, m, genes, cells, value_dtype=np.int64, idx_dtype=np.uint):
     """A Nabo dataset file of the CountMatrix m: names/{genes,cells}, cell_data/<cell> and gene_data/<gene>, records of
-    dtype [('idx', np.uint), ('val', value_dtype)], one dataset per cell and per gene (an empty one for none without
-    entries).  What mtx_to_h5, extract_cells_from_h5 and merge_h5 write."""
+    dtype [('idx', idx_dtype), ('val', value_dtype)], one dataset per cell and per gene (an empty one for none without
+    entries).  What mtx_to_h5, extract_cells_from_h5 and merge_h5 write, and csv_to_h5 with idx_dtype=np.int64 (what the
+    reference's records have there)."""
     import h5py
-    dtype = [("idx", np.uint), ("val", value_dtype)]
+    dtype = [("idx", idx_dtype), ("val", value_dtype)]
     with h5py.File(h5_fn, mode="a", libver="latest") as h5:
         grp = h5.create_group("names")
         grp.create_dataset("genes", chunks=None, data=[x.encode("ascii") for x in genes])

@@ -105,6 +105,10 @@ INGEST_SYMBOLS = ["nabo_mtx_create", "nabo_mtx_feed", "nabo_mtx_finish", "nabo_m
 COUNTS_SYMBOLS = ["nabo_mtxw_create", "nabo_mtxw_read", "nabo_mtxw_last_device_ms", "nabo_mtxw_free", "nabo_mtxw_geometry",
                   "nabo_counts_remap"]
 
+# every symbol include/nabo_csv.h declares (a dense CSV table of numbers to its entries by row and by column)
+CSV_SYMBOLS = ["nabo_csv_create", "nabo_csv_set_first_line", "nabo_csv_feed", "nabo_csv_finish", "nabo_csv_get_rows", "nabo_csv_get_cols",
+               "nabo_csv_get_row_names", "nabo_csv_stats", "nabo_csv_last_device_ms", "nabo_csv_geometry", "nabo_csv_free"]
+
 # what include/nabo_knn_inspect.h declares (a look into an index, for tests and tools)
 INSPECT_SYMBOLS = ["nabo_index_stream_order"]
 
@@ -310,11 +314,22 @@ def lib():
     L.nabo_mtxw_free.argtypes = [vp]
     L.nabo_mtxw_geometry.argtypes = [C.POINTER(i32)] * 4
     L.nabo_counts_remap.argtypes = [i32, i64, i64, vp, vp, vp, i64, vp, i64, vp, C.POINTER(i64), vp, vp, vp, vp, vp, vp]
+    L.nabo_csv_create.argtypes = [i32, i32, i64, i32, i32, i32, dbl, i64, i64, C.POINTER(vp)]
+    L.nabo_csv_set_first_line.argtypes = [vp, i64]
+    L.nabo_csv_feed.argtypes = [vp, vp, i64]
+    L.nabo_csv_finish.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.nabo_csv_get_rows.argtypes = [vp, vp, vp, vp]
+    L.nabo_csv_get_cols.argtypes = [vp, vp, vp, vp]
+    L.nabo_csv_get_row_names.argtypes = [vp, vp, vp]
+    L.nabo_csv_stats.argtypes = [vp, C.POINTER(i64)]
+    L.nabo_csv_last_device_ms.argtypes = [vp, C.POINTER(dbl), C.POINTER(i64)]
+    L.nabo_csv_geometry.argtypes = [C.POINTER(i32)] * 3
+    L.nabo_csv_free.argtypes = [vp]
     for name in (SYMBOLS + GRAPH_SYMBOLS + CLUSTER_SYMBOLS + DE_SYMBOLS + PCA_SYMBOLS + PCA_FIT_SYMBOLS + QC_SYMBOLS + LAYOUT_SYMBOLS + UMAP_SYMBOLS
                  + UMAP_TRANSFORM_SYMBOLS + COMMUNITY_SYMBOLS + AGGLOM_SYMBOLS + POTENTIAL_SYMBOLS + BUNDLE_SYMBOLS + RENDER_SYMBOLS
-                 + INGEST_SYMBOLS + COUNTS_SYMBOLS + INSPECT_SYMBOLS):
+                 + INGEST_SYMBOLS + COUNTS_SYMBOLS + CSV_SYMBOLS + INSPECT_SYMBOLS):
         if name not in ("nabo_version", "nabo_last_error", "nabo_layout_destroy", "nabo_umap_destroy", "nabo_umap_transform_destroy", "nabo_community_destroy",
-                        "nabo_potential_destroy", "nabo_bundle_destroy", "nabo_render_destroy", "nabo_mtx_free", "nabo_mtxw_free"):
+                        "nabo_potential_destroy", "nabo_bundle_destroy", "nabo_render_destroy", "nabo_mtx_free", "nabo_mtxw_free", "nabo_csv_free"):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L
